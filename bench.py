@@ -20,14 +20,19 @@ own sequence in consecutive overlapping windows (one-frame halo, so every
 consecutive pair is matched once), and every step's per-frame tables are
 gathered to rank 0 over RCCL (on by default for world > 1).
 
-Outside the timed region: the device error flags of every batch are checked
-(any overflow fails the run), frames 0, B/2 and B-1 of the timed batch (and
-their matches) are compared bit-exactly with the CPU oracle, and on rank 0
-at N=1 the oracle is timed as the CPU baseline.  Also reported:
-the rooflines of the two HBM passes (orb_blur_fast_kernel, lsd_prep_kernel;
-HIP events on the launch streams) and the end-to-end HBM fraction, a
+A plain run sets up, warms up, times --steps steps, checks the device error
+flags of every batch (any overflow fails the run), writes the last timed
+step's tables when --dump-outputs DIR is given, and prints the result line.
+
+--full adds everything else, outside the timed region: frames 0, B/2 and B-1
+of the timed batch (and their matches) are compared bit-exactly with the CPU
+oracle, and on rank 0 at N=1 the oracle is timed as the CPU baseline (SURVEY
+8d).  Also reported with --full: the per-stage timings, the rooflines of the
+two HBM passes (orb_blur_fast_kernel, lsd_prep_kernel; HIP events on the
+launch streams, which --full also records around the timed launches), a
 batch-64 line (C1/C2), the single-frame latency of the drop-in entry points
 run as Frame runs them, and an overlapped pinned-H2D variant of the step.
+--no-check / --no-cpu-baseline / --no-extra / --no-side drop parts of --full.
 """
 import argparse
 import ctypes
@@ -519,6 +524,13 @@ def main():
                          "world > 1, the north_star's gather of the descriptor tables)")
     ap.add_argument("--no-gather", dest="gather", action="store_false")
     ap.add_argument("--dry-run", action="store_true", help="launcher + reductions on CPU (gloo), no GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: stage timings, rooflines, the oracle "
+                         "check of the timed batch, the CPU baseline, the batch-64 / latency / H2D lines and the "
+                         "BoW / projection / stereo timings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's tables (counts, keypoints, "
+                         "descriptors, keylines, matches; a fixed sample of the batch's frames) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=64, help="frames of the CPU-baseline sample (SURVEY 8(d): 64)")
     ap.add_argument("--cpu-baseline-child", nargs=4, metavar=("FRAMES_NPY", "OUT_JSON", "RUNS", "PAR_S"),
@@ -548,6 +560,9 @@ def main():
         return 2
     rank = int(os.environ.get("RANK", "0"))
     if args.dry_run:
+        if args.dump_outputs:
+            print("bench.py: --dump-outputs needs the GPU run (the dry run computes no tables)", file=sys.stderr)
+            return 2
         return dry_run(args, world, rank)
     if args.c4:
         args.width, args.height = 752, 480
@@ -582,7 +597,12 @@ def run(args, world, rank):
     wstride = (B - 1) if args.c4 else B
     seq = synth.device_sequence(B + (nwin - 1) * wstride, W, H, seed=seed0, device=cuda)
     torch.cuda.synchronize()
-    first_digest = hashlib.sha256(seq[:B].cpu().numpy().tobytes()).hexdigest()[:16]
+    full = args.full
+    # digest of the first window's frames (a download of the whole batch):
+    # with --full, and for every multi-rank run (each rank owns its sequence)
+    first_digest = None
+    if full or world > 1:
+        first_digest = hashlib.sha256(seq[:B].cpu().numpy().tobytes()).hexdigest()[:16]
 
     # Slots: an ORB + line extractor pair with its own output tables, match
     # buffers and stream.  Step k runs on slot k % inflight, so batch k+1's
@@ -624,7 +644,7 @@ def run(args, world, rank):
     # queues, so handles created after many others were destroyed can land
     # on one queue and serialise ORB || lines
     lat_handles = None
-    if rank == 0 and world == 1 and not args.no_extra:
+    if full and rank == 0 and world == 1 and not args.no_extra:
         # (and the batch-64 line's pair and its stream, for the same reason)
         lat_handles = (plvi.ORBextractor(1000, 1.2, 8, 20, 7, W, H, device=dev),
                        plvi.Lineextractor(200, 0, 0.8, 2, 2.0, 0, W, H, device=dev),
@@ -634,9 +654,10 @@ def run(args, world, rank):
     orb, lx, stream, st = s0.orb, s0.lx, s0.stream, s0.st
     kp_p, de_p, co_p, kl_p, lde_p, lco_p = s0.kp_p, s0.de_p, s0.co_p, s0.kl_p, s0.lde_p, s0.lco_p
     outs, lscratch, lm12, lnm = s0.outs, s0.lscratch, s0.lm12, s0.lnm
-    for sl in slots:
-        sl.orb.kernel_timing(True)  # event pair around every blur+FAST launch
-        sl.lx.kernel_timing(True)   # and every lsd_prep launch
+    if full:
+        for sl in slots:
+            sl.orb.kernel_timing(True)  # event pair around every blur+FAST launch
+            sl.lx.kernel_timing(True)   # and every lsd_prep launch
 
     def extract(fptr, n=B, sl=s0):
         plvi.frame_extract_batch(sl.orb, sl.lx, fptr, n, W * H, W, (0, 0), stream=sl.st)
@@ -687,63 +708,68 @@ def run(args, world, rank):
         err_warm[0] |= sl.orb.errors(sl.st)
         err_warm[1] |= sl.lx.errors(sl.st)
 
-    # stage timing (separate from the timed region: events add markers); each
-    # extractor alone so its stage times are uncontended
-    f0 = seq.data_ptr()
-    orb.profile(True)
-    lx.profile(True)
-    lx.kernel_timing(True)  # isolated per-launch times of the LBD Gaussian + Sobel kernels
-    orb.kernel_timing(True)  # and of blur + FAST (the roofline kernel) with nothing beside it
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    match_ms = 0.0
-    nprof = max(3, min(args.steps, 10))
-    for _ in range(nprof):
-        orb.extract_batch(f0, B, W * H, W, (0, 0), stream=st)
-        torch.cuda.synchronize()
-        lx.extract_batch(f0, B, W * H, W, stream=st)
-        torch.cuda.synchronize()
-        ev0.record(stream)
-        match()
-        ev1.record(stream)
-        torch.cuda.synchronize()
-        match_ms += ev0.elapsed_time(ev1)
-    st_orb, runs = orb.profile_read()
-    st_lines, lruns = lx.profile_read()
-    lbd_iso = [lx.kernel_timing_read(k) for k in (1, 2)]
-    bf_iso = orb.kernel_timing_read()
-    pyr_iso = orb.kernel_timing_read(1)
-    orb.kernel_timing(False)
-    lx.kernel_timing(False)
-    orb.profile(False)
-    lx.profile(False)
-
-    def part_fps(fn):
-        fn()
-        torch.cuda.synchronize()
-        ev0.record(stream)
+    def stage_timings():
+        # --full: stage timing (separate from the timed region: events add
+        # markers); each extractor alone so its stage times are uncontended
+        f0 = seq.data_ptr()
+        orb.profile(True)
+        lx.profile(True)
+        lx.kernel_timing(True)  # isolated per-launch times of the LBD Gaussian + Sobel kernels
+        orb.kernel_timing(True)  # and of blur + FAST (the roofline kernel) with nothing beside it
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        match_ms = 0.0
+        nprof = max(3, min(args.steps, 10))
         for _ in range(nprof):
+            orb.extract_batch(f0, B, W * H, W, (0, 0), stream=st)
+            torch.cuda.synchronize()
+            lx.extract_batch(f0, B, W * H, W, stream=st)
+            torch.cuda.synchronize()
+            ev0.record(stream)
+            match()
+            ev1.record(stream)
+            torch.cuda.synchronize()
+            match_ms += ev0.elapsed_time(ev1)
+        st_orb, runs = orb.profile_read()
+        st_lines, lruns = lx.profile_read()
+        iso = {"lbd": [lx.kernel_timing_read(k) for k in (1, 2)], "bf": orb.kernel_timing_read(),
+               "pyr": orb.kernel_timing_read(1)}
+        orb.kernel_timing(False)
+        lx.kernel_timing(False)
+        orb.profile(False)
+        lx.profile(False)
+
+        def part_fps(fn):
             fn()
-        ev1.record(stream)
-        torch.cuda.synchronize()
-        return B * nprof / (ev0.elapsed_time(ev1) * 1e-3)
-    parts = {"orb_only": part_fps(lambda: orb.extract_batch(f0, B, W * H, W, (0, 0), stream=st)),
-             "lines_only": part_fps(lambda: lx.extract_batch(f0, B, W * H, W, stream=st)),
-             "match_only": part_fps(match)}
-    stage_ms = {f"orb.{k}": v / runs for k, v in st_orb.items()}
-    stage_ms.update({f"lines.{k}": v / lruns for k, v in st_lines.items()})
-    stage_ms["match"] = match_ms / nprof
-    side = {}
-    if not args.no_side and world == 1:
-        side = side_stages(args, torch, plvi, synth, lib, orb, st, stream, B, W, H, cap, kp_p, de_p, co_p, nprof,
-                           cuda, seed0)
+            torch.cuda.synchronize()
+            ev0.record(stream)
+            for _ in range(nprof):
+                fn()
+            ev1.record(stream)
+            torch.cuda.synchronize()
+            return B * nprof / (ev0.elapsed_time(ev1) * 1e-3)
+        parts = {"orb_only": part_fps(lambda: orb.extract_batch(f0, B, W * H, W, (0, 0), stream=st)),
+                 "lines_only": part_fps(lambda: lx.extract_batch(f0, B, W * H, W, stream=st)),
+                 "match_only": part_fps(match)}
+        stage_ms = {f"orb.{k}": v / runs for k, v in st_orb.items()}
+        stage_ms.update({f"lines.{k}": v / lruns for k, v in st_lines.items()})
+        stage_ms["match"] = match_ms / nprof
+        side = {}
+        if not args.no_side and world == 1:
+            side = side_stages(args, torch, plvi, synth, lib, orb, st, stream, B, W, H, cap, kp_p, de_p, co_p, nprof,
+                               cuda, seed0)
+        return stage_ms, parts, side, iso
+
+    if full:
+        stage_ms, parts, side, iso = stage_timings()
 
     # ---------------------------------------------------------- timed region
-    # the roofline events cover exactly the timed launches; a spin_kernel on
-    # each side marks the same window in a rocprofv3 kernel trace
-    # (tools/timed_stats.py)
-    for sl in slots:
-        sl.orb.kernel_timing(True)
-        sl.lx.kernel_timing(True)
+    # --full: the roofline events cover exactly the timed launches; a
+    # spin_kernel on each side marks the same window in a rocprofv3 kernel
+    # trace (tools/timed_stats.py)
+    if full:
+        for sl in slots:
+            sl.orb.kernel_timing(True)
+            sl.lx.kernel_timing(True)
     torch.cuda._sleep(1000)
     pdist.barrier(world)
     torch.cuda.synchronize()
@@ -762,11 +788,189 @@ def run(args, world, rank):
     value = frames_total / el
     ms_step = el / args.steps * 1e3
     err = list(err_warm)
-    ktot = kn = ltot = ln = ptot = pn = 0
-    sob = [[0.0, 0], [0.0, 0]]  # LBD Gaussian + Sobel kernels: [total ms, launches] of octave 0 / 1
     for sl in slots:
         err[0] |= sl.orb.errors(sl.st)
         err[1] |= sl.lx.errors(sl.st)
+    # last timed batch's window (for the checks below) and the slot it ran on
+    lo_last = ((step_no[0] - 1) % nwin) * wstride
+    sl_last = slots[(step_no[0] - 1) % len(slots)]
+    if args.dump_outputs:
+        prefix = "" if rank == 0 else f"rank{rank}_"
+        dump_outputs(pathlib.Path(args.dump_outputs), prefix, plvi, sl_last, B, cap, lcap)
+    roofs = rooflines(slots, iso, B, W, H) if full else {}
+    e2e_b = E2E_BYTES_640 if (W, H) == (640, 480) else E2E_BYTES_752 if (W, H) == (752, 480) else None
+    e2e = None if e2e_b is None else {"bytes_per_frame": e2e_b, "achieved": e2e_b * value / world / 1e9,
+                                      "unit": "GB/s per GPU", "frac": e2e_b * value / world / 1e9 / HBM_PEAK_GBS,
+                                      "model": "SURVEY 8(d) reference-materialisation bytes x FPS per GPU"}
+
+    # ---------------------------------------------------------- checks
+    checks, digests = [], {"first_batch_frames": first_digest}
+    if full and not args.no_check:
+        checks = collect_checks(torch, plvi, seq, lo_last, B, W, H, orb, lx, outs, lm12, lnm, cap, lcap, extract,
+                                match)
+    # per-rank digest of the first window's tables (what rank 0 receives)
+    if args.gather:
+        extract(seq.data_ptr())
+        match()
+        torch.cuda.synchronize()
+        h = hashlib.sha256()
+        for src, n in zip((co_p, kp_p, de_p, lco_p, kl_p, lde_p), tab_sizes):
+            h.update(plvi.download(src, np.zeros(n, np.uint8)).tobytes())
+        digests["first_batch_tables"] = h.hexdigest()[:16]
+        if world > 1:
+            gather()
+            wait_gathers()
+            torch.cuda.synchronize()
+            if rank == 0:
+                digests["gathered_tables"] = s0.tg.digests()
+    all_digests = [digests]
+    if world > 1:
+        import torch.distributed as dist
+        all_digests = [None] * world
+        dist.all_gather_object(all_digests, digests)
+
+    extra = {}
+    if full and rank == 0 and world == 1 and not args.no_extra:
+        extra = extra_lines(args, torch, plvi, synth, lib, stream, W, H, seed0, orb, lx, extract, match, seq, B,
+                            lat_handles, slots, fused, nwin, wstride)
+        if "h2d_overlapped" in extra:
+            extra["h2d_overlapped"]["frac_of_resident"] = extra["h2d_overlapped"]["value"] / value
+
+    result = {
+        "metric": METRIC if (W, H) == (640, 480) else METRIC.replace("640×480", f"{W}×{H}"), "value": value,
+        "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "full": full,
+        "data": "synthetic (plvi.synth.device_sequence: seeded scenes, integer camera shifts, sigma-2 noise)",
+        "config": {"workload": ("C4: 752x480 sequence per rank, windows of B frames with a one-frame halo; "
+                                if args.c4 else "C1+C2+C3: ") +
+                               "ORB extract (1000 feats, 1.2, 8 levels, FAST 20/7) || LSD+LBD (200 lines, scale 0.8, "
+                               "2 octaves) as one HIP-stream schedule, then ORB kNN-2 + LineMatcher::match vs "
+                               "previous frame" + (", RCCL gather of per-frame tables to rank 0" if args.gather
+                                                   else ""),
+                   "batch": B, "frames_per_step": new_frames, "width": W, "height": H,
+                   "parallelism": f"sequence-sharded x{world}", "gather": bool(args.gather),
+                   "inflight": len(slots), "schedule": schedule_knobs(B)},
+        "end_to_end_hbm": e2e,
+        "device_errors": {"orb": err[0], "lines": err[1]},
+        "digests": all_digests,
+    }
+    if args.dump_outputs:
+        # the dumped step's frames: [first_frame, first_frame + batch) of this rank's sequence
+        result["dump_outputs"] = {"dir": str(args.dump_outputs), "first_frame": lo_last}
+    if full:
+        result.update(roofs)
+        result.update({"stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
+                       "dominant_stage": max(stage_ms, key=stage_ms.get),
+                       "part_fps": {k: round(v, 1) for k, v in parts.items()},
+                       "side_ms": side})
+    result.update(extra)
+    fail = []
+    if err[0] or err[1]:
+        fail.append(f"device error flags orb={err[0]} lines={err[1]}")
+    if checks:
+        bad = oracle_verify(checks)
+        result["oracle_check"] = {"frames": [lo_last, lo_last + B // 2, lo_last + B - 1], "items": len(checks),
+                                  "mismatches": bad}
+        if bad:
+            fail.append(f"oracle mismatch: {bad}")
+    b64c = result.pop("_b64_checks", None)
+    if b64c:
+        bad = oracle_verify(b64c[1])
+        result["batch64"]["oracle_check"] = {"frames": b64c[0], "items": len(b64c[1]), "mismatches": bad}
+        if bad:
+            fail.append(f"batch-64 oracle mismatch: {bad}")
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        n = min(args.cpu_frames, B)
+        result["cpu_baseline"] = cpu_baseline([seq[i].cpu().numpy() for i in range(n)])
+    if world > 1:
+        import torch.distributed as dist
+        flags = [None] * world
+        dist.all_gather_object(flags, fail)
+        fail = [f"rank {r}: {m}" for r, fl in enumerate(flags) for m in fl]
+        dist.destroy_process_group()
+    if fail:
+        result["failed"] = fail
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    return 1 if fail else 0
+
+
+DUMP_FRAMES = 64          # frames of the batch whose full tables --dump-outputs writes
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _fields_f64(rec):
+    """A structured table (KEYPOINT_DTYPE / KEYLINE_DTYPE) as float64 [..., n_fields]: every field is a
+    32-bit float or int, exact in float64."""
+    return np.stack([rec[f].astype(np.float64) for f in rec.dtype.names], -1)
+
+
+def dump_outputs(out_dir, prefix, plvi, sl, B, cap, lcap):
+    """--dump-outputs: the tables the last timed step left on its slot `sl`
+    (what a caller of plvi_frame_extract_match_batch reads back), as
+    out_dir/<prefix><name>.npy.  Per-frame counts for the whole batch; the
+    keypoint / descriptor / keyline / match tables for a fixed, seeded sample
+    of DUMP_FRAMES frames (`frames`), rows past a frame's count zeroed (the
+    tables hold stale rows there).  Match tables of frame f are those of pair
+    (f, f-1), f >= 1; a line pair without a query row or with fewer than two
+    train rows (no matching done) is written as -1 / 0.  Integers and floats
+    as float64 (exact), descriptor bytes as float32."""
+    kp_p, de_p, co_p, mo_p, _ = sl.orb.outputs()
+    kl_p, lde_p, fn_p, lco_p, _ = sl.lx.outputs()
+    cnt = plvi.download(co_p, np.zeros(B, np.int32))
+    mono = plvi.download(mo_p, np.zeros(B, np.int32))
+    lcnt = plvi.download(lco_p, np.zeros(B, np.int32))
+    lnm = plvi.download(sl.lnm.data_ptr(), np.zeros(B - 1, np.int32))
+    lvalid = (lcnt[1:] >= 1) & (lcnt[:-1] >= 2)
+    # bytes one sampled frame adds to the files below (the sample shrinks where the tables' capacities are large)
+    per_frame = cap * (7 * 8 + 32 * 4 + 4 * 8) + lcap * (17 * 8 + 32 * 4 + 3 * 8 + 8) + 8
+    S = max(1, min(B, DUMP_FRAMES, (DUMP_MAX_BYTES - 5 * 8 * B) // per_frame))
+    sel = np.sort(np.random.default_rng(0).choice(B, S, replace=False))
+    kps = np.zeros((S, cap), plvi.KEYPOINT_DTYPE)
+    desc = np.zeros((S, cap, 32), np.uint8)
+    kls = np.zeros((S, lcap), plvi.KEYLINE_DTYPE)
+    ldesc = np.zeros((S, lcap, 32), np.uint8)
+    lfn = np.zeros((S, lcap, 3), np.float64)
+    knn = np.zeros((4, S, cap), np.int32)
+    lmatch = np.full((S, lcap), -1, np.int32)
+    def dl(ptr, arr):
+        if arr.size:
+            plvi.download(ptr, arr)
+    for i, f in enumerate(sel):
+        f, n, nl = int(f), int(cnt[f]), int(lcnt[f])
+        dl(kp_p + 28 * cap * f, kps[i, :n])
+        dl(de_p + 32 * cap * f, desc[i, :n])
+        dl(kl_p + 68 * lcap * f, kls[i, :nl])
+        dl(lde_p + 32 * lcap * f, ldesc[i, :nl])
+        dl(fn_p + 24 * lcap * f, lfn[i, :nl])
+        if f >= 1:
+            for j, o in enumerate(sl.outs):
+                dl(o.data_ptr() + 4 * cap * (f - 1), knn[j, i, :n])
+            if lvalid[f - 1]:
+                dl(sl.lm12.data_ptr() + 4 * lcap * (f - 1), lmatch[i, :nl])
+    arrays = {"frames": sel.astype(np.float64), "orb_count": cnt.astype(np.float64),
+              "orb_mono_count": mono.astype(np.float64), "line_count": lcnt.astype(np.float64),
+              "line_match_count": np.where(lvalid, lnm, 0).astype(np.float64),
+              "orb_keypoints": _fields_f64(kps), "orb_descriptors": desc.astype(np.float32),
+              "keylines": _fields_f64(kls), "line_descriptors": ldesc.astype(np.float32), "line_functions": lfn,
+              "orb_knn_idx0": knn[0].astype(np.float64), "orb_knn_dist0": knn[1].astype(np.float64),
+              "orb_knn_idx1": knn[2].astype(np.float64), "orb_knn_dist1": knn[3].astype(np.float64),
+              "line_matches": lmatch.astype(np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{prefix}{name}.npy", a)
+
+
+def rooflines(slots, iso, B, W, H):
+    """--full: the rooflines of the HBM passes from the event pairs recorded
+    around the timed launches (kernel_timing on every slot) and, as
+    `isolated`, around the stage-timing runs (iso, from stage_timings())."""
+    ktot = kn = ltot = ln = ptot = pn = 0
+    sob = [[0.0, 0], [0.0, 0]]  # LBD Gaussian + Sobel kernels: [total ms, launches] of octave 0 / 1
+    for sl in slots:
         a, b = sl.orb.kernel_timing_read()
         c, d = sl.lx.kernel_timing_read()
         p_, q_ = sl.orb.kernel_timing_read(1)
@@ -775,10 +979,7 @@ def run(args, world, rank):
             t_, n_ = sl.lx.kernel_timing_read(k + 1)
             sob[k][0] += t_
             sob[k][1] += n_
-    # last timed batch's window (for the checks below)
-    lo_last = ((step_no[0] - 1) % nwin) * wstride
-
-    # ---------------------------------------------------------- rooflines
+    lbd_iso, bf_iso, pyr_iso = iso["lbd"], iso["bf"], iso["pyr"]
     bf_bytes = blur_fast_bytes(W, H) * B
     lp_bytes = lsd_prep_bytes(W, H) * B
     bf_ms = ktot / max(kn, 1)
@@ -847,100 +1048,7 @@ def run(args, world, rank):
             if e[part]["achieved"]:
                 e[part]["frac"] = e[part]["achieved"] / HBM_PEAK_GBS
         roof_lbd[name] = e
-    e2e_b = E2E_BYTES_640 if (W, H) == (640, 480) else E2E_BYTES_752 if (W, H) == (752, 480) else None
-    e2e = None if e2e_b is None else {"bytes_per_frame": e2e_b, "achieved": e2e_b * value / world / 1e9,
-                                      "unit": "GB/s per GPU", "frac": e2e_b * value / world / 1e9 / HBM_PEAK_GBS,
-                                      "model": "SURVEY 8(d) reference-materialisation bytes x FPS per GPU"}
-
-    # ---------------------------------------------------------- checks
-    checks, digests = [], {"first_batch_frames": first_digest}
-    if not args.no_check:
-        checks = collect_checks(torch, plvi, seq, lo_last, B, W, H, orb, lx, outs, lm12, lnm, cap, lcap, extract,
-                                match)
-    # per-rank digest of the first window's tables (what rank 0 receives)
-    if args.gather:
-        extract(seq.data_ptr())
-        match()
-        torch.cuda.synchronize()
-        h = hashlib.sha256()
-        for src, n in zip((co_p, kp_p, de_p, lco_p, kl_p, lde_p), tab_sizes):
-            h.update(plvi.download(src, np.zeros(n, np.uint8)).tobytes())
-        digests["first_batch_tables"] = h.hexdigest()[:16]
-        if world > 1:
-            gather()
-            wait_gathers()
-            torch.cuda.synchronize()
-            if rank == 0:
-                digests["gathered_tables"] = s0.tg.digests()
-    all_digests = [digests]
-    if world > 1:
-        import torch.distributed as dist
-        all_digests = [None] * world
-        dist.all_gather_object(all_digests, digests)
-
-    extra = {}
-    if rank == 0 and world == 1 and not args.no_extra:
-        extra = extra_lines(args, torch, plvi, synth, lib, stream, W, H, seed0, orb, lx, extract, match, seq, B,
-                            lat_handles, slots, fused, nwin, wstride)
-        if "h2d_overlapped" in extra:
-            extra["h2d_overlapped"]["frac_of_resident"] = extra["h2d_overlapped"]["value"] / value
-
-    result = {
-        "metric": METRIC if (W, H) == (640, 480) else METRIC.replace("640×480", f"{W}×{H}"), "value": value,
-        "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-        "data": "synthetic (plvi.synth.device_sequence: seeded scenes, integer camera shifts, sigma-2 noise)",
-        "config": {"workload": ("C4: 752x480 sequence per rank, windows of B frames with a one-frame halo; "
-                                if args.c4 else "C1+C2+C3: ") +
-                               "ORB extract (1000 feats, 1.2, 8 levels, FAST 20/7) || LSD+LBD (200 lines, scale 0.8, "
-                               "2 octaves) as one HIP-stream schedule, then ORB kNN-2 + LineMatcher::match vs "
-                               "previous frame" + (", RCCL gather of per-frame tables to rank 0" if args.gather
-                                                   else ""),
-                   "batch": B, "frames_per_step": new_frames, "width": W, "height": H,
-                   "parallelism": f"sequence-sharded x{world}", "gather": bool(args.gather),
-                   "inflight": len(slots), "schedule": schedule_knobs(B)},
-        "roofline": roof,
-        "roofline_pyramid": roof_pyr,
-        "roofline_lsd_prep": roof_lsd,
-        "roofline_lbd": roof_lbd,
-        "end_to_end_hbm": e2e,
-        "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
-        "dominant_stage": max(stage_ms, key=stage_ms.get),
-        "part_fps": {k: round(v, 1) for k, v in parts.items()},
-        "side_ms": side,
-        "device_errors": {"orb": err[0], "lines": err[1]},
-        "digests": all_digests,
-    }
-    result.update(extra)
-    fail = []
-    if err[0] or err[1]:
-        fail.append(f"device error flags orb={err[0]} lines={err[1]}")
-    if checks:
-        bad = oracle_verify(checks)
-        result["oracle_check"] = {"frames": [lo_last, lo_last + B // 2, lo_last + B - 1], "items": len(checks),
-                                  "mismatches": bad}
-        if bad:
-            fail.append(f"oracle mismatch: {bad}")
-    b64c = result.pop("_b64_checks", None)
-    if b64c:
-        bad = oracle_verify(b64c[1])
-        result["batch64"]["oracle_check"] = {"frames": b64c[0], "items": len(b64c[1]), "mismatches": bad}
-        if bad:
-            fail.append(f"batch-64 oracle mismatch: {bad}")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        n = min(args.cpu_frames, B)
-        result["cpu_baseline"] = cpu_baseline([seq[i].cpu().numpy() for i in range(n)])
-    if world > 1:
-        import torch.distributed as dist
-        flags = [None] * world
-        dist.all_gather_object(flags, fail)
-        fail = [f"rank {r}: {m}" for r, fl in enumerate(flags) for m in fl]
-        dist.destroy_process_group()
-    if fail:
-        result["failed"] = fail
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    return 1 if fail else 0
+    return {"roofline": roof, "roofline_pyramid": roof_pyr, "roofline_lsd_prep": roof_lsd, "roofline_lbd": roof_lbd}
 
 
 def collect_checks(torch, plvi, seq, lo, B, W, H, orb, lx, outs, lm12, lnm, cap, lcap, extract, match):

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/gpurun_out
 for v in $1; do
   if [ "$v" = main ]; then L=""; else L=$R/pl-vi-orbslam3_amd/variants/$v/libplvi_frontend.so; fi
-  PLVI_LIB=$L timeout -k 10 ${AB_T:-300} python $R/bench.py --no-cpu-baseline --no-side --no-extra --no-check \
+  PLVI_LIB=$L timeout -k 10 ${AB_T:-300} python $R/bench.py --full --no-cpu-baseline --no-side --no-extra --no-check \
     --steps 10 --warmup 2 ${@:2} > $R/gpurun_out/ab_$v.json 2> $R/gpurun_out/ab_$v.err
   rc=$?; [ $rc -ne 0 ] && { echo "$v failed rc=$rc"; tail -5 $R/gpurun_out/ab_$v.err; exit $rc; }
   python - $v $R/gpurun_out/ab_$v.json <<'PY'
@@ -20,7 +20,7 @@ done
 # env A/B: AB_ENVS="name:VAR=v,VAR2=v ..." runs the in-tree library under each environment
 for spec in ${AB_ENVS:-}; do
   name=${spec%%:*}; envs=${spec#*:}
-  env ${envs//,/ } timeout -k 10 ${AB_T:-300} python $R/bench.py --no-cpu-baseline --no-side --no-extra --no-check \
+  env ${envs//,/ } timeout -k 10 ${AB_T:-300} python $R/bench.py --full --no-cpu-baseline --no-side --no-extra --no-check \
     --steps 10 --warmup 2 > $R/gpurun_out/ab_$name.json 2> $R/gpurun_out/ab_$name.err
   rc=$?; [ $rc -ne 0 ] && { echo "$name failed rc=$rc"; tail -5 $R/gpurun_out/ab_$name.err; exit $rc; }
   python - $name $R/gpurun_out/ab_$name.json <<'PY'

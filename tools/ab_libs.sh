@@ -4,6 +4,7 @@
 # bench.py --no-cpu-baseline --no-extra --no-side; prints FPS, ms/step, the
 # roofline kernel's in-schedule frac and the oracle check per run.
 set -u
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the roofline and oracle-check fields read below are --full's
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out
 IFS=';' read -ra LS <<< "${LIBS:-base=}"
 for rep in $(seq 1 ${REPS:-2}); do

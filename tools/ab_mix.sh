@@ -5,6 +5,7 @@
 # --no-extra --no-side; prints FPS, ms/step, the roofline kernel's timed launch
 # and frac, the pyramid's, and the oracle check.
 set -u
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the roofline and oracle-check fields read below are --full's
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out
 IFS=';' read -ra CS <<< "${CONFIGS:?}"
 for rep in $(seq 1 ${REPS:-2}); do

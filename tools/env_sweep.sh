@@ -2,6 +2,7 @@
 # schedule-knob sweep of the headline step: each line of $CONFIGS is an env
 # assignment list ("-" = defaults), REPS bench runs each, alternating.
 set -u
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the oracle-check field read below is --full's
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out
 IFS=';' read -ra CS <<< "${CONFIGS:--}"
 for rep in $(seq 1 ${REPS:-2}); do

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for i in $(seq 1 ${REPS:-2}); do
   rm -rf $OUT/profrep
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/profrep -o run --output-format csv -- python3 $R/bench.py > $OUT/profrep_$i.log 2>&1 || { echo "rep $i failed"; tail -3 $OUT/profrep_$i.log; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/profrep -o run --output-format csv -- python3 $R/bench.py --full > $OUT/profrep_$i.log 2>&1 || { echo "rep $i failed"; tail -3 $OUT/profrep_$i.log; exit 1; }
   python3 $R/tools/timed_stats.py $OUT/profrep/run_kernel_trace.csv $OUT/kst_rep$i.csv > /dev/null
   cp $OUT/profrep/run_kernel_stats.csv $OUT/ks_rep$i.csv
   python3 - $OUT/profrep/run_kernel_trace.csv $OUT/launches_rep$i.txt <<'PY'

@@ -16,7 +16,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
   echo "== bench"
-  timeout -k 10 ${BENCH_T:-400} python bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 ${BENCH_T:-400} python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
   rc=$?; cat $OUT/bench.json; tail -5 $OUT/bench.err; fatal $rc bench hard
 fi
 PARGS=${PROF_ARGS:---steps 3 --warmup 1 --no-cpu-baseline}
@@ -24,7 +24,7 @@ cd /tmp && export TMPDIR=/tmp
 if [ "${SKIP_PROF:-0}" != 1 ]; then
   echo "== rocprof stats"
   # the bench command itself (default arguments unless STATS_ARGS is set)
-  timeout -k 10 ${PROF_T:-400} rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 $R/bench.py ${STATS_ARGS:-} > $OUT/prof.log 2>&1
+  timeout -k 10 ${PROF_T:-400} rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 $R/bench.py --full ${STATS_ARGS:-} > $OUT/prof.log 2>&1
   rc=$?; tail -3 $OUT/prof.log; fatal $rc rocprof hard
   python3 $R/tools/timed_stats.py $OUT/prof/run_kernel_trace.csv $OUT/kernel_stats_timed.csv
   # the bench line of the profiled run: its roofline.avg_launch_ms times the
