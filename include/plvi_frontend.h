@@ -106,7 +106,12 @@ typedef struct plvi_orb_params {
 
 /* Create an extractor for frames of width x height, batches of up to
  * max_batch frames, on HIP device `device`.  Replaces the constructor
- * (ORBextractor.cc:408-468). */
+ * (ORBextractor.cc:408-468).  Any size, up to 16 levels, any scale factor
+ * > 1 (2.0 on even sizes takes cv::resize's INTER_AREA path, like the
+ * reference), any thresholds, nfeatures >= 0.  PLVI_E_BADARG where the
+ * reference itself cannot run -- a level without a 30-px cell (below 62 x 62)
+ * or with 0 octree roots (more than twice as tall as wide between the
+ * borders) -- and above 8 octree roots (a limit of this implementation). */
 int plvi_orb_create(const plvi_orb_params* p, int width, int height, int max_batch, int device,
                     plvi_orb_extractor** out);
 int plvi_orb_destroy(plvi_orb_extractor* h);

@@ -335,6 +335,10 @@ static int orb_extract(const ImageU8& image, const OrbParams& P, int lap0, int l
         const float width = (float)(maxBorderX - minBorderX), height = (float)(maxBorderY - minBorderY);
         const int nCols = (int)(width / W), nRows = (int)(height / W);
         if (nCols <= 0 || nRows <= 0) return -2;
+        // DistributeOctTree's root count (:541): 0 roots (a region more than
+        // twice as tall as wide) divides by zero there -- refused like the HIP
+        // path (PLVI_E_BADARG), before this level's octree is built
+        if ((int)std::round((float)(maxBorderX - minBorderX) / (maxBorderY - minBorderY)) <= 0) return -2;
         const int wCell = (int)std::ceil(width / nCols), hCell = (int)std::ceil(height / nRows);
         std::vector<KP> cell;
         for (int i = 0; i < nRows; ++i) {
@@ -417,7 +421,7 @@ extern "C" int oracle_orb_extract(const uint8_t* img, int w, int h, int stride, 
         const KP& k = R.kps[i];
         kps[i] = plvi_keypoint{k.x, k.y, k.size, k.angle, k.response, k.octave, k.class_id};
     }
-    std::memcpy(desc, R.desc.data(), R.desc.size());
+    if (!R.desc.empty()) std::memcpy(desc, R.desc.data(), R.desc.size());
     return mono;
 }
 

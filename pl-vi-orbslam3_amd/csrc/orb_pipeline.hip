@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -25,8 +26,13 @@ static inline int cv_ceil_h(float v) { int i = (int)v; return i + (i < v); }
 // OpenCV 4.2: scale_x = 1/inv_scale_x, fx = (float)((dx+0.5)*scale_x-0.5),
 // sx = cvFloor(fx), border clamps, cvRound(... * INTER_RESIZE_COEF_SCALE)),
 // packed for orb_pyramid_kernel; dx >= xmax columns use S[sx] * 2048 only.
-static int append_xtab(std::vector<uint32_t>& tab, int sw, int dw) {
+// `area` (the level is exactly half of its source in both axes, so cv::resize
+// takes the INTER_AREA fast path): columns of ResizeAreaFastVec_SIMD_8u's
+// scalar tail, dx >= (sw / 2 / 8) * 8, carry kPyrXtabAreaTail; every other
+// column of such a level has sx = 2 dx, a0 = a1 = 1024, the same result.
+static int append_xtab(std::vector<uint32_t>& tab, int sw, int dw, bool area) {
     const double scale_x = 1. / ((double)dw / sw);
+    const int tail0 = area ? (sw / 2 / 8) * 8 : dw;
     for (int dx = 0; dx < dw; ++dx) {
         float fx = (float)((dx + 0.5) * scale_x - 0.5);
         int sx = cv_floor_h(fx);
@@ -36,7 +42,8 @@ static int append_xtab(std::vector<uint32_t>& tab, int sw, int dw) {
         if (clampR && sx >= sw - 1) { fx = 0; sx = sw - 1; }
         const int a0 = cv_round_h((1.f - fx) * 2048), a1 = cv_round_h(fx * 2048);
         if (sx > 1023 || a0 + a1 < 2047 || a0 + a1 > 2049) return PLVI_E_BADARG;
-        tab.push_back(pyr_xtab_pack(sx, a0, a1, clampR));
+        if (area && (sx != 2 * dx || a0 != 1024 || a1 != 1024 || clampR)) return PLVI_E_BADARG;
+        tab.push_back(pyr_xtab_pack(sx, a0, a1, clampR) | (dx >= tail0 ? kPyrXtabAreaTail : 0u));
     }
     return PLVI_OK;
 }
@@ -94,6 +101,10 @@ struct OrbPipeline {
         omono, err, staging;
     size_t pyrSmem = 0;  // orb_pyramid_kernel LDS: column table + source-level row rings
     int xtabN = 0, pyrFrameLds = 0;
+    // levels that are exactly half of their source (cv::resize's INTER_AREA fast
+    // path: scale factor 2 on even sizes) run the *_area pyramid kernels
+    bool areaLevel[kOrbMaxLevels]{};
+    bool pyrHasArea = false;
     int octLcap = 0;      // candidates a (frame, level) octree wave stages in LDS
     int octLdsMax = kOctListLds;  // PLVI_ORB_OCT_LDS (0: every level's octree scans its list in memory)
     size_t octSmem = 0;   // orb_octree_kernel dynamic LDS
@@ -331,7 +342,11 @@ struct OrbPipeline {
                 d.rsx = 1. / ((double)d.w / lv[l - 1].w);
                 d.rsy = 1. / ((double)d.h / lv[l - 1].h);
                 d.xtab = (int)xtab.size();
-                if (append_xtab(xtab, lv[l - 1].w, d.w)) return PLVI_E_BADARG;
+                // resize.cpp: INTER_LINEAR becomes INTER_AREA when both scales are the integer 2
+                const bool area = std::fabs(d.rsx - 2.) < DBL_EPSILON && std::fabs(d.rsy - 2.) < DBL_EPSILON;
+                areaLevel[l] = area;
+                pyrHasArea |= area;
+                if (append_xtab(xtab, lv[l - 1].w, d.w, area)) return PLVI_E_BADARG;
                 // LDS: a kPyrRing-row ring of level 0, two rows of every other source level
                 pyrSmem += (l == 1 ? kPyrRing : 2) * (size_t)((lv[l - 1].w + 3) & ~3);
             }
@@ -430,12 +445,14 @@ struct OrbPipeline {
                     const uint8_t* src = l == 1 ? d_frames : P + s.off;
                     const size_t sfr = l == 1 ? frame_stride : (size_t)s.plane, srow = l == 1 ? row_stride : (size_t)s.w;
                     const int items = ((d.w + 3) >> 2) * d.h;
-                    hipLaunchKernelGGL(orb_resize_level_kernel, dim3((items + 255) / 256, nf), dim3(256), 0, st, src, sfr,
+                    auto* resizeK = areaLevel[l] ? orb_resize_level_area_kernel : orb_resize_level_kernel;
+                    hipLaunchKernelGGL(resizeK, dim3((items + 255) / 256, nf), dim3(256), 0, st, src, sfr,
                                        srow, s.w, s.h, P + d.off, (size_t)d.plane, d.w, d.h, d.rsy,
                                        (const uint32_t*)d_xtab.as<uint32_t>() + d.xtab, resizeGeneric);
                 }
             } else {
-                hipLaunchKernelGGL(orb_pyramid_kernel, dim3((nf + kPyrFrames - 1) / kPyrFrames), dim3(64 * (kPyrFrames + 1)),
+                auto* pyrK = pyrHasArea ? orb_pyramid_area_kernel : orb_pyramid_kernel;
+                hipLaunchKernelGGL(pyrK, dim3((nf + kPyrFrames - 1) / kPyrFrames), dim3(64 * (kPyrFrames + 1)),
                                    pyrSmem, st, d_lv.as<OrbLevelDev>(), L, d_frames, frame_stride, row_stride, nf, P,
                                    (const uint32_t*)d_xtab.as<uint32_t>(), xtabN, pyrFrameLds, resizeGeneric);
             }

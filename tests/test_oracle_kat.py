@@ -115,26 +115,73 @@ def test_resize_half_is_area_fast_path():
     assert np.array_equal(out, exp.astype(np.uint8))
 
 
+def _bilinear_8u(src, dw, dh, dx, dy):
+    """cv::resize INTER_LINEAR 8U at one destination pixel (resize.cpp, OpenCV 4.2: float coefficients
+    rounded to 11 bits, VResizeLinear's 8U specialisation); the pixels used here are off the borders."""
+    sh, sw = src.shape
+    sx_scale = 1.0 / (dw / float(sw))
+    sy_scale = 1.0 / (dh / float(sh))
+    s = src.astype(np.int64)
+    fy = np.float32((dy + 0.5) * sy_scale - 0.5)
+    sy = int(np.floor(fy)); fy = np.float32(fy - np.float32(sy))
+    b0 = int(np.rint(np.float32(1.0 - fy) * np.float32(2048))); b1 = int(np.rint(fy * np.float32(2048)))
+    fx = np.float32((dx + 0.5) * sx_scale - 0.5)
+    sx = int(np.floor(fx)); fx = np.float32(fx - np.float32(sx))
+    a0 = int(np.rint(np.float32(1.0 - fx) * np.float32(2048))); a1 = int(np.rint(fx * np.float32(2048)))
+    H0 = s[sy, sx] * a0 + s[sy, sx + 1] * a1
+    H1 = s[sy + 1, sx] * a0 + s[sy + 1, sx + 1] * a1
+    return (((b0 * (H0 >> 4)) >> 16) + ((b1 * (H1 >> 4)) >> 16) + 2) >> 2
+
+
 def test_resize_bilinear_fixed_point_formula():
     rng = np.random.default_rng(4)
     src = rng.integers(0, 256, size=(480, 640), dtype=np.uint8)
     dw, dh = 533, 400
     out = ol.resize(src, dw, dh)
-    sx_scale = 1.0 / (dw / 640.0)
-    sy_scale = 1.0 / (dh / 480.0)
-    s = src.astype(np.int64)
     for dy in (0, 1, 199, 399):
-        fy = np.float32((dy + 0.5) * sy_scale - 0.5)
-        sy = int(np.floor(fy)); fy = np.float32(fy - np.float32(sy))
-        b0 = int(np.rint(np.float32(1.0 - fy) * np.float32(2048))); b1 = int(np.rint(fy * np.float32(2048)))
         for dx in (0, 1, 266, 532):
-            fx = np.float32((dx + 0.5) * sx_scale - 0.5)
-            sx = int(np.floor(fx)); fx = np.float32(fx - np.float32(sx))
-            a0 = int(np.rint(np.float32(1.0 - fx) * np.float32(2048))); a1 = int(np.rint(fx * np.float32(2048)))
-            H0 = s[sy, sx] * a0 + s[sy, sx + 1] * a1
-            H1 = s[sy + 1, sx] * a0 + s[sy + 1, sx + 1] * a1
-            v = (((b0 * (H0 >> 4)) >> 16) + ((b1 * (H1 >> 4)) >> 16) + 2) >> 2
-            assert out[dy, dx] == v
+            assert out[dy, dx] == _bilinear_8u(src, dw, dh, dx, dy)
+
+
+def test_resize_half_in_one_axis_only_is_bilinear():
+    """322x241 -> 161x120: x scales by exactly 2, y by 241/120, so cv::resize stays on the bilinear path
+    (the INTER_AREA fast path needs both axes): every column, the tail column 160 included, follows the
+    fixed-point formula, and the plane differs from the 2x2 box average the area path would give."""
+    rng = np.random.default_rng(3)
+    src = rng.integers(0, 256, size=(241, 322), dtype=np.uint8)
+    out = ol.resize(src, 161, 120)
+    for dy in (0, 1, 59, 60, 118, 119):
+        for dx in (0, 1, 80, 159, 160):
+            assert out[dy, dx] == _bilinear_8u(src, 161, 120, dx, dy), (dx, dy)
+    s = src[:240].astype(np.int32)
+    box = (s[0::2, 0::2] + s[0::2, 1::2] + s[1::2, 0::2] + s[1::2, 1::2] + 2) >> 2
+    assert (out != box).mean() > 0.5
+
+
+@pytest.mark.parametrize("w,h,scale,nlevels", [(70, 200, 1.2, 1), (61, 61, 1.2, 1), (100, 80, 2.0, 2)])
+def test_oracle_orb_refuses_degenerate_geometry(w, h, scale, nlevels):
+    """Shapes the HIP path refuses with PLVI_E_BADARG return mono -2 and no keypoints: 70x200 has
+    nIni = round(38 / 168) = 0 octree roots (it divided by zero before), 61x61 has no 30-px cell,
+    and level 1 of 100x80 at scale 2.0 (50x40) has none either."""
+    for img in (synth.frame(7, w, h), np.random.default_rng(2).integers(0, 256, (h, w), dtype=np.uint8)):
+        mono, kps, desc = ol.orb_extract(img, 1000, scale, nlevels, 20, 7)
+        assert mono == -2 and len(kps) == 0 and len(desc) == 0
+
+
+def test_oracle_orb_refusals_clean_under_sanitizers():
+    """tests/native/orb_oracle_check.cpp (its own main; the oracle's ORB translation unit and cvprim.cpp
+    compiled with AddressSanitizer + UBSan on the CPU) runs the three refused shapes and 62x62 / 160x120:
+    -2 where refused, keypoints where accepted, and no out-of-bounds access or undefined behaviour."""
+    import subprocess
+    nat = ol.ROOT / "tests" / "native"
+    exe = nat / "_build" / "orb_oracle_check"
+    exe.parent.mkdir(exist_ok=True)
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-o", str(exe), str(nat / "orb_oracle_check.cpp"),
+                    str(ol.ORACLE_DIR / "orb_oracle.cpp"), str(ol.ORACLE_DIR / "cvprim.cpp"), "-lm"], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.count(" ok") == 10 and "BAD" not in r.stdout
 
 
 def test_orb_constructor_tables():

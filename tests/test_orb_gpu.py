@@ -9,22 +9,9 @@ import pytest
 import oracle_lib as ol
 import plvi
 from plvi import synth
-from util import real_frames, structured_frames
+from util import assert_orb_same as _assert_same, real_frames, structured_frames
 
 pytestmark = pytest.mark.gpu
-
-
-def _assert_same(got, exp, tag):
-    mg, kg, dg = got
-    me, ke, de = exp
-    assert mg == me, f"{tag}: monoIndex {mg} != {me}"
-    assert len(kg) == len(ke), f"{tag}: n {len(kg)} != {len(ke)}"
-    for f in ke.dtype.names:
-        a, b = kg[f], ke[f]
-        bad = np.flatnonzero(a.view(np.uint32) != b.view(np.uint32)) if a.dtype.kind == "f" else np.flatnonzero(a != b)
-        assert bad.size == 0, f"{tag}: field {f} differs at {bad[:10]} got {a[bad[:5]]} exp {b[bad[:5]]}"
-    bad = np.flatnonzero((dg != de).any(axis=1))
-    assert bad.size == 0, f"{tag}: descriptors differ at rows {bad[:10]}"
 
 
 @pytest.fixture(scope="module")

@@ -10,6 +10,37 @@ def real_frames():
     return {k: z[k] for k in z.files}
 
 
+def _assert_fields_same(kg, ke, tag):
+    assert len(kg) == len(ke), f"{tag}: n {len(kg)} != {len(ke)}"
+    for f in ke.dtype.names:
+        a, b = kg[f], ke[f]
+        bad = np.flatnonzero(a.view(np.uint32) != b.view(np.uint32)) if a.dtype.kind == "f" else np.flatnonzero(a != b)
+        assert bad.size == 0, f"{tag}: field {f} differs at {bad[:10]} got {a[bad[:5]]} exp {b[bad[:5]]}"
+
+
+def assert_orb_same(got, exp, tag):
+    """(monoIndex, keypoints, descriptors) of the HIP path vs the oracle's: monoIndex exactly, every
+    cv::KeyPoint field bitwise in the reference's slot order, descriptors byte for byte."""
+    mg, kg, dg = got
+    me, ke, de = exp
+    assert mg == me, f"{tag}: monoIndex {mg} != {me}"
+    _assert_fields_same(kg, ke, tag)
+    bad = np.flatnonzero((dg != de).any(axis=1))
+    assert bad.size == 0, f"{tag}: descriptors differ at rows {bad[:10]}"
+
+
+def assert_lines_same(got, exp, tag):
+    """(keylines, descriptors, line functions) of the HIP path vs the oracle's: all 17 KeyLine fields
+    bitwise, LBD descriptors byte for byte, the f64 line equations bitwise."""
+    kg, dg, fg = got
+    ke, de, fe = exp
+    _assert_fields_same(kg, ke, tag)
+    bad = np.flatnonzero((dg != de).any(axis=1))
+    assert bad.size == 0, f"{tag}: descriptors differ at rows {bad[:10]}"
+    bad = np.flatnonzero((fg.view(np.uint64) != fe.view(np.uint64)).any(axis=1))
+    assert bad.size == 0, f"{tag}: line functions differ at rows {bad[:10]}"
+
+
 def near_duplicate_descriptors(rng, n_train, n_query, frac=0.6, p_flip=0.08):
     """C3 generator: 60% of queries are train rows with
     Binomial(256, p) bit flips, the rest uniform random bits."""
