@@ -22,6 +22,7 @@
 #include <mutex>
 #include <vector>
 
+#include "grid_search.h"
 #include "plvi_common.h"
 
 namespace plvi {
@@ -109,10 +110,7 @@ __global__ __launch_bounds__(256) void search_by_bow_kernel(
             for (int j = lane; j < nfn; j += 64) {
                 const int realIdxF = FI[f0 + j];
                 if (s_mk[realIdxF] >= 0) continue;
-                const uint4* df = reinterpret_cast<const uint4*>(FD + (size_t)realIdxF * 32);
-                const uint4 y0 = df[0], y1 = df[1];
-                const int d = __popc(x0.x ^ y0.x) + __popc(x0.y ^ y0.y) + __popc(x0.z ^ y0.z) + __popc(x0.w ^ y0.w) +
-                              __popc(x1.x ^ y1.x) + __popc(x1.y ^ y1.y) + __popc(x1.z ^ y1.z) + __popc(x1.w ^ y1.w);
+                const int d = hamming256(x0, x1, FD + (size_t)realIdxF * 32);
                 // lane-local scan in list order with the reference's update rule
                 BowBest& t = realIdxF < nLeft ? bb : br;
                 if (d < t.b1) {
@@ -146,40 +144,15 @@ __global__ __launch_bounds__(256) void search_by_bow_kernel(
     }
     __syncthreads();
     // rotation histogram (:409-419) and ComputeThreeMaxima + filter (:450-468)
-    const float factor = 1.0f / kBowHisto;
     if (check_orientation) {
         for (int i = tid; i < nF; i += 256) {
             const int k = s_mk[i];
             if (k < 0) continue;
-            float rot = KA[k] - FA[i];
-            if (rot < 0.0f) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == kBowHisto) bin = 0;
-            atomicAdd(&s_hist[bin], 1);
+            atomicAdd(&s_hist[rot_bin(KA[k] - FA[i], kBowHisto)], 1);
         }
         __syncthreads();
         if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < kBowHisto; i++) {
-                const int s = s_hist[i];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    ind3 = ind2; ind2 = ind1; ind1 = i;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    ind3 = ind2; ind2 = i;
-                } else if (s > max3) {
-                    max3 = s;
-                    ind3 = i;
-                }
-            }
-            if (max2 < 0.1f * (float)max1) {
-                ind2 = -1;
-                ind3 = -1;
-            } else if (max3 < 0.1f * (float)max1) {
-                ind3 = -1;
-            }
-            s_keep[0] = ind1; s_keep[1] = ind2; s_keep[2] = ind3;
+            three_maxima(s_hist, kBowHisto, s_keep);
         }
         __syncthreads();
     }
@@ -187,10 +160,7 @@ __global__ __launch_bounds__(256) void search_by_bow_kernel(
     for (int i = tid; i < nF; i += 256) {
         int k = s_mk[i];
         if (k >= 0 && check_orientation) {
-            float rot = KA[k] - FA[i];
-            if (rot < 0.0f) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == kBowHisto) bin = 0;
+            const int bin = rot_bin(KA[k] - FA[i], kBowHisto);
             if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) k = -1;
         }
         match_kf[(size_t)p * f_cap + i] = k;

@@ -18,6 +18,8 @@
 #include <climits>
 #include <vector>
 
+#include "grid_search.h"
+#include "host_stage.h"
 #include "plvi_common.h"
 #include "stl_uset.h"
 #include "plvi_math.h"
@@ -95,10 +97,7 @@ __global__ __launch_bounds__(64) void line_match_grid_kernel(
             if (i2 < 0 || i2 >= n2) continue;
             const double dt = rfma(vx, V2[2 * i2], vy * V2[2 * i2 + 1]);
             if (__builtin_fabs(dt) < 0.75) continue;
-            const uint4* pb = reinterpret_cast<const uint4*>(D2 + (size_t)i2 * 32);
-            const uint4 c0 = pb[0], c1 = pb[1];
-            const int d = __popc(a0.x ^ c0.x) + __popc(a0.y ^ c0.y) + __popc(a0.z ^ c0.z) + __popc(a0.w ^ c0.w) +
-                          __popc(a1.x ^ c1.x) + __popc(a1.y ^ c1.y) + __popc(a1.z ^ c1.z) + __popc(a1.w ^ c1.w);
+            const int d = hamming256(a0, a1, D2 + (size_t)i2 * 32);
             if (d < s_dist[i2]) {
                 s_dist[i2] = d;
                 s_m21[i2] = i1;
@@ -244,10 +243,7 @@ __global__ __launch_bounds__(64) void line_search_proj_kernel(
         for (int c = lane; c < K; c += 64) {
             const int i2 = s_cand[c];
             if (i2 < 0 || i2 >= nc || s_blk[i2]) continue;
-            const uint4* pb = reinterpret_cast<const uint4*>(CD + (size_t)i2 * 32);
-            const uint4 c0 = pb[0], c1 = pb[1];
-            const int d = __popc(a0.x ^ c0.x) + __popc(a0.y ^ c0.y) + __popc(a0.z ^ c0.z) + __popc(a0.w ^ c0.w) +
-                          __popc(a1.x ^ c1.x) + __popc(a1.y ^ c1.y) + __popc(a1.z ^ c1.z) + __popc(a1.w ^ c1.w);
+            const int d = hamming256(a0, a1, CD + (size_t)i2 * 32);
             if (d < b) {  // lane-local candidates come in iteration order
                 b = d;
                 pos = c;
@@ -315,47 +311,29 @@ extern "C" int plvi_line_search_projection(const plvi_line_proj_params* p, const
     if (n_cur == 0) return 0;
     const int ncell = p->grid_cols * p->grid_rows;
     const int nidx = std::max(cell_off[ncell], 1), lc = std::max(n_last, 1);
-    std::vector<size_t> off;
-    size_t tot = 0;
-    auto put = [&](size_t bytes) {
-        off.push_back(tot);
-        tot += (bytes + 255) & ~size_t(255);
-        return off.size() - 1;
-    };
-    const size_t oA = put(4 * (size_t)n_cur), oD = put(32 * (size_t)n_cur), oB = put(n_cur), oCO = put(4 * (size_t)(ncell + 1));
-    const size_t oCI = put(4 * (size_t)nidx), oF = put(lc), oX = put(24 * (size_t)lc), oO = put(4 * (size_t)lc);
-    const size_t oMD = put(32 * (size_t)lc), oM = put(4 * (size_t)n_cur), oN = put(32);
-    DevBuf d;
-    if (d.alloc(tot)) return PLVI_E_HIP;
-    uint8_t* B = d.as<uint8_t>();
-    auto up = [&](size_t slot, const void* src, size_t bytes) -> int {
-        if (src && bytes) PLVI_CHECK(hipMemcpy(B + off[slot], src, bytes, hipMemcpyHostToDevice));
-        return PLVI_OK;
-    };
-    int rc = up(oA, cur_angle, 4 * (size_t)n_cur) | up(oD, cur_desc, 32 * (size_t)n_cur) |
-             up(oCO, cell_off, 4 * (size_t)(ncell + 1)) | up(oCI, cell_idx, 4 * (size_t)cell_off[ncell]);
-    if (cur_blocked) rc |= up(oB, cur_blocked, n_cur);
-    else PLVI_CHECK(hipMemset(B + off[oB], 0, n_cur));
-    if (n_last > 0)
-        rc |= up(oF, last_flags, n_last) | up(oX, x3dc, 24 * (size_t)n_last) | up(oO, last_octave, 4 * (size_t)n_last) |
-              up(oMD, ml_desc, 32 * (size_t)n_last);
-    if (rc) return PLVI_E_HIP;
-    int counts[4] = {n_cur, n_last, 0, 0};
-    PLVI_CHECK(hipMemcpy(B + off[oN], counts, 16, hipMemcpyHostToDevice));
-    int* dN = reinterpret_cast<int*>(B + off[oN]);
-    rc = plvi_line_search_projection_batch(1, p, reinterpret_cast<const float*>(B + off[oA]), B + off[oD], B + off[oB],
-                                           dN, n_cur, reinterpret_cast<const int*>(B + off[oCO]),
-                                           reinterpret_cast<const int*>(B + off[oCI]), nidx, B + off[oF],
-                                           reinterpret_cast<const float*>(B + off[oX]),
-                                           reinterpret_cast<const int*>(B + off[oO]), B + off[oMD], dN + 1, lc,
-                                           reinterpret_cast<int*>(B + off[oM]), dN + 2, dN + 3, nullptr);
-    if (rc) return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    int res[2] = {0, 0};
-    PLVI_CHECK(hipMemcpy(match, B + off[oM], 4 * (size_t)n_cur, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(res, dN + 2, 8, hipMemcpyDeviceToHost));
-    if (res[1]) return PLVI_E_CAPACITY;
-    return res[0];
+    HostStage st;
+    const size_t oA = st.put(4 * (size_t)n_cur), oD = st.put(32 * (size_t)n_cur), oB = st.put(n_cur);
+    const size_t oCO = st.put(4 * (size_t)(ncell + 1)), oCI = st.put(4 * (size_t)nidx), oF = st.put(lc);
+    const size_t oX = st.put(24 * (size_t)lc), oO = st.put(4 * (size_t)lc), oMD = st.put(32 * (size_t)lc);
+    const size_t oM = st.put(4 * (size_t)n_cur), oN = st.put(32);
+    if (st.alloc()) return PLVI_E_HIP;
+    const int counts[4] = {n_cur, n_last, 0, 0};  // [3]: the kernel's error flags
+    if (st.up(oA, cur_angle, 4 * (size_t)n_cur) | st.up(oD, cur_desc, 32 * (size_t)n_cur) |
+        st.up(oCO, cell_off, 4 * (size_t)(ncell + 1)) | st.up(oCI, cell_idx, 4 * (size_t)cell_off[ncell]) |
+        st.up_or_zero(oB, cur_blocked, n_cur) | st.up(oF, last_flags, n_last) | st.up(oX, x3dc, 24 * (size_t)n_last) |
+        st.up(oO, last_octave, 4 * (size_t)n_last) | st.up(oMD, ml_desc, 32 * (size_t)n_last) |
+        st.up(oN, counts, sizeof counts))
+        return PLVI_E_HIP;
+    int* dN = st.at<int>(oN);
+    if (int rc = plvi_line_search_projection_batch(1, p, st.at<float>(oA), st.at<uint8_t>(oD), st.at<uint8_t>(oB), dN,
+                                                   n_cur, st.at<int>(oCO), st.at<int>(oCI), nidx, st.at<uint8_t>(oF),
+                                                   st.at<float>(oX), st.at<int>(oO), st.at<uint8_t>(oMD), dN + 1, lc,
+                                                   st.at<int>(oM), dN + 2, dN + 3, nullptr))
+        return rc;
+    const int nm = st.finish(dN + 2, match, oM, n_cur);
+    int err = 0;
+    if (nm >= 0) PLVI_CHECK(hipMemcpy(&err, dN + 3, 4, hipMemcpyDeviceToHost));
+    return err ? PLVI_E_CAPACITY : nm;
 }
 
 extern "C" int plvi_line_match_grid_batch(int n_pairs, const int* d_lines1, const uint8_t* d_desc1, const int* d_n1,

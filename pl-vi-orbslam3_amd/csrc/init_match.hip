@@ -29,6 +29,7 @@
 #include <climits>
 #include <vector>
 
+#include "grid_search.h"
 #include "plvi_common.h"
 
 namespace plvi {
@@ -37,8 +38,7 @@ int launch_knn2(const uint8_t* q, const int* nq, int nq_cap, const uint8_t* t, c
                 int n_pairs, int* i0, int* d0, int* i1, int* d1, hipStream_t st);
 
 namespace {
-constexpr int kCols = 64, kRows = 48, kCells = kCols * kRows;  // FRAME_GRID_COLS / ROWS (include/Frame.h:47-48)
-constexpr int kThLow = 50, kHisto = 30;                        // ORBmatcher::TH_LOW, HISTO_LENGTH
+constexpr int kThLow = 50, kHisto = 30;  // ORBmatcher::TH_LOW, HISTO_LENGTH
 constexpr unsigned long long kNoKey = ~0ull;
 
 struct InitLds {
@@ -58,13 +58,6 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
     return v;
 }
 
-__device__ __forceinline__ int dist256(const uint4 a0, const uint4 a1, const uint8_t* __restrict__ b) {
-    const uint4* pb = reinterpret_cast<const uint4*>(b);
-    const uint4 b0 = pb[0], b1 = pb[1];
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
 // GetFeaturesInArea(x, y, r, 0, 0) (Frame.cc:1006-1075) + the candidate loop
 // of SearchForInitialization (:728-753) over the window, one wave: returns
 // best key in `best` (dist << 40 | scan position << 16 | i2) and the key of a
@@ -75,25 +68,19 @@ __device__ void init_scan(const plvi_init_params& p, const InitLds& s, const int
                           unsigned long long& sec) {
     best = sec = kNoKey;
     const float r = (float)p.window;
-    const int nMinCellX = max(0, (int)floorf((x - p.min_x - r) * p.inv_w));
-    if (nMinCellX >= kCols) return;
-    const int nMaxCellX = min(kCols - 1, (int)ceilf((x - p.min_x + r) * p.inv_w));
-    if (nMaxCellX < 0) return;
-    const int nMinCellY = max(0, (int)floorf((y - p.min_y - r) * p.inv_h));
-    if (nMinCellY >= kRows) return;
-    const int nMaxCellY = min(kRows - 1, (int)ceilf((y - p.min_y + r) * p.inv_h));
-    if (nMaxCellY < 0) return;
+    GridWindow w;
+    if (!grid_window(p.min_x, p.min_y, p.inv_w, p.inv_h, x, y, r, w)) return;
     unsigned long long k1 = kNoKey, k2 = kNoKey;
     int pos = 0;
-    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-        // cells (ix, nMinCellY..nMaxCellY) are one CSR range, in mGrid scan order
-        const int c0 = s.cell_off[ix * kRows + nMinCellY], c1 = s.cell_off[ix * kRows + nMaxCellY + 1];
+    for (int ix = w.nMinCellX; ix <= w.nMaxCellX; ++ix) {
+        // cells (ix, w.nMinCellY..w.nMaxCellY) are one CSR range, in mGrid scan order
+        const int c0 = s.cell_off[ix * kGridRows + w.nMinCellY], c1 = s.cell_off[ix * kGridRows + w.nMaxCellY + 1];
         for (int k = c0 + lane; k < c1; k += 64) {
             const int i2 = s.cell_idx[k];
             if (!s.k0[i2]) continue;  // octave < 0 or > 0
             const float distx = s.kx[i2] - x, disty = s.ky[i2] - y;
             if (!(fabsf(distx) < r && fabsf(disty) < r)) continue;
-            const int dist = dist256(a0, a1, desc2 + (size_t)32 * i2);
+            const int dist = hamming256(a0, a1, desc2 + (size_t)32 * i2);
             if (md && md[i2] <= dist) continue;
             const unsigned long long key =
                 ((unsigned long long)dist << 40) | ((unsigned long long)(pos + k - c0) << 16) | (unsigned)i2;
@@ -129,7 +116,7 @@ __global__ __launch_bounds__(256) void search_init_kernel(
         s.md = reinterpret_cast<int*>(q); q += 4 * (size_t)cap2;
         s.v21 = reinterpret_cast<int*>(q); q += 4 * (size_t)cap2;
         s.v12 = reinterpret_cast<int*>(q); q += 4 * (size_t)cap1;
-        s.cell_off = reinterpret_cast<int*>(q); q += 4 * (kCells + 1);
+        s.cell_off = reinterpret_cast<int*>(q); q += 4 * (kGridCells + 1);
         s.cell_idx = reinterpret_cast<unsigned short*>(q); q += 2 * (size_t)cap2;
         s.ent = reinterpret_cast<unsigned short*>(q); q += 4 * (size_t)cap1;  // [cap1] i1, [cap1] bin
         s.k0 = q;
@@ -148,9 +135,9 @@ __global__ __launch_bounds__(256) void search_init_kernel(
         s.v21[i] = -1;
     }
     for (int i = tid; i < n1; i += 256) s.v12[i] = -1;
-    const int* CO = cell_off_all + (size_t)pr * (kCells + 1);
-    for (int c = tid; c <= kCells; c += 256) s.cell_off[c] = CO[c];
-    const int ncell = CO[kCells];
+    const int* CO = cell_off_all + (size_t)pr * (kGridCells + 1);
+    for (int c = tid; c <= kGridCells; c += 256) s.cell_off[c] = CO[c];
+    const int ncell = CO[kGridCells];
     for (int k = tid; k < ncell; k += 256) s.cell_idx[k] = (unsigned short)cell_idx_all[(size_t)pr * cap2 + k];
     if (tid < kHisto) s_hist[tid] = 0;
     __syncthreads();
@@ -168,7 +155,6 @@ __global__ __launch_bounds__(256) void search_init_kernel(
     __syncthreads();
     // phase 2: the assignment in F1 order (:755-781), one wave
     if (wv == 0) {
-        const float factor = 1.0f / kHisto;
         int nm = 0, ne = 0;
         for (int i1 = 0; i1 < n1; ++i1) {
             if (K1[i1].octave > 0) continue;
@@ -191,10 +177,7 @@ __global__ __launch_bounds__(256) void search_init_kernel(
                     s.v21[bestIdx2] = i1;
                     s.md[bestIdx2] = bestDist;
                     if (p.check_orientation) {
-                        float rot = K1[i1].angle - K2[bestIdx2].angle;
-                        if (rot < 0.0f) rot += 360.0f;
-                        int bin = (int)roundf(rot * factor);
-                        if (bin == kHisto) bin = 0;
+                        const int bin = rot_bin(K1[i1].angle - K2[bestIdx2].angle, kHisto);
                         s.ent[ne] = (unsigned short)i1;
                         s.ent[cap1 + ne] = (unsigned short)bin;
                         s_hist[bin]++;
@@ -212,27 +195,7 @@ __global__ __launch_bounds__(256) void search_init_kernel(
             for (int i1 = 0; i1 < n1; ++i1) nm += s.v12[i1] >= 0;
             s_ne = ne;
             s_nm = nm;
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;  // ComputeThreeMaxima (:2304-2345)
-            for (int bb = 0; bb < kHisto; bb++) {
-                const int cnt = s_hist[bb];
-                if (cnt > max1) {
-                    max3 = max2; max2 = max1; max1 = cnt;
-                    ind3 = ind2; ind2 = ind1; ind1 = bb;
-                } else if (cnt > max2) {
-                    max3 = max2; max2 = cnt;
-                    ind3 = ind2; ind2 = bb;
-                } else if (cnt > max3) {
-                    max3 = cnt;
-                    ind3 = bb;
-                }
-            }
-            if (max2 < 0.1f * (float)max1) {
-                ind2 = -1;
-                ind3 = -1;
-            } else if (max3 < 0.1f * (float)max1) {
-                ind3 = -1;
-            }
-            s_keep[0] = ind1; s_keep[1] = ind2; s_keep[2] = ind3;
+            three_maxima(s_hist, kHisto, s_keep);
         }
     }
     __syncthreads();
@@ -346,7 +309,7 @@ __global__ __launch_bounds__(256) void line_init_select_kernel(const int* __rest
 }
 
 static size_t init_smem(int cap1, int cap2) {
-    return (size_t)cap1 * (8 + 8 + 4 + 4) + (size_t)cap2 * (4 + 4 + 4 + 4 + 2 + 1) + 4 * (kCells + 1) + 64;
+    return (size_t)cap1 * (8 + 8 + 4 + 4) + (size_t)cap2 * (4 + 4 + 4 + 4 + 2 + 1) + 4 * (kGridCells + 1) + 64;
 }
 
 }  // namespace plvi

@@ -1100,7 +1100,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLVI_DESC_W
         const OrbLevelDev& lv = lvs[l];
         const int cx = (int)kp.x, cy = (int)kp.y;  // integer-valued level coords (>= 19 from every border)
         // level 0's image is the caller's frame unless the pyramid holds a copy
-        // (frames0 != null: the batch's rows are not packed, or PLVI_ORB_L0_COPY)
+        // (frames0 == null: the batch's rows are not packed, or PLVI_ORB_L0_COPY=1)
         const bool view0 = l == 0 && frames0;
         const int W = view0 ? (int)f_row : lv.w, BW = lv.bpitch;
         // ---- stage both boxes: dword loads first, then LDS writes

@@ -24,18 +24,22 @@
 // and re-scans only a point whose best candidate was blocked meanwhile (the
 // argmin over a subset that still contains it is unchanged otherwise);
 // phase 3 is the rotation histogram filter.
+//
+// The window clamps, the candidate walk, the per-image LDS arrays, the
+// histogram helpers and phase 3 are in grid_search.h; each matcher's scan
+// below derives (u, v, radius, levels) and packs what the walk found.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <mutex>
-#include <vector>
 
+#include "grid_search.h"
+#include "host_stage.h"
 #include "plvi_common.h"
 #include "plvi_math.h"
 
 namespace plvi {
 
-constexpr int kGridCols = 64, kGridRows = 48, kGridCells = kGridCols * kGridRows;  // include/Frame.h:47-48
 constexpr int kProjThHigh = 100, kProjHisto = 30;
 constexpr int kGridKeyBits = 13;  // keypoint index bits in the grid sort key (cap <= 8192)
 
@@ -97,74 +101,43 @@ __global__ __launch_bounds__(256) void assign_grid_kernel(const plvi_keypoint* _
     for (int j = tid; j < m; j += 256) CI[j] = (int)(s_key[j] & ((1u << kGridKeyBits) - 1));
 }
 
-struct ProjLds {
-    float *kx, *ky;
-    unsigned char *koct, *blocked, *pre, *nulled;
-    int *cell_off, *assign, *best;
-    unsigned short *cell_idx, *ent;
-};
+// What a scan returns: (bestDist << 16 | bestIdx2), or
+constexpr unsigned kScanSkip = 0xFFFFFFFFu;  // the point is skipped (`continue`d before or at an empty window)
+constexpr unsigned kScanNone = 0xFFFFFFFEu;  // window searched, no candidate (bestIdx2 == -1); two-camera scan only
 
-// GetFeaturesInArea + the candidate loop of SearchByProjection (:1992-2058)
-// for LastFrame point i against the blocked flags `blk`; returns
-// (bestDist << 16 | bestIdx2), or 0xFFFFFFFF when the point is skipped.
-__device__ unsigned proj_scan(const plvi_proj_params& p, const ProjLds& s, const unsigned char* blk, int i,
-                              const float* __restrict__ x3dc, const int* __restrict__ loct,
-                              const uint8_t* __restrict__ mpdesc, const uint8_t* __restrict__ cdesc,
-                              const float* __restrict__ uright, int n_cur) {
-    const float xc = x3dc[3 * i], yc = x3dc[3 * i + 1], zc = x3dc[3 * i + 2];
-    const float invzc = (float)(1.0 / (double)zc);
-    if (invzc < 0) return 0xFFFFFFFFu;
-    const float u = p.fx * xc / zc + p.cx, v = p.fy * yc / zc + p.cy;  // Pinhole::project
-    if (u < p.min_x || u > p.max_x) return 0xFFFFFFFFu;
-    if (v < p.min_y || v > p.max_y) return 0xFFFFFFFFu;
-    const int nLastOctave = loct[i];
-    if (nLastOctave < 0 || nLastOctave >= p.nlevels) return 0xFFFFFFFFu;  // no scale factor: no candidate
-    const float radius = p.th * p.scale_factors[nLastOctave];
-    int minLevel, maxLevel;
+__device__ __forceinline__ unsigned scan_pack(int dist, int idx) { return ((unsigned)dist << 16) | (unsigned)idx; }
+
+// The octave range of SearchByProjection(Frame&, Frame&) (:2028-2035)
+__device__ __forceinline__ void proj_levels(const plvi_proj_params& p, int nLastOctave, int& minLevel, int& maxLevel) {
     if (p.forward) { minLevel = nLastOctave; maxLevel = -1; }
     else if (p.backward) { minLevel = 0; maxLevel = nLastOctave; }
     else { minLevel = nLastOctave - 1; maxLevel = nLastOctave + 1; }
-    const int nMinCellX = max(0, (int)floorf((u - p.min_x - radius) * p.inv_w));
-    if (nMinCellX >= kGridCols) return 0xFFFFFFFFu;
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((u - p.min_x + radius) * p.inv_w));
-    if (nMaxCellX < 0) return 0xFFFFFFFFu;
-    const int nMinCellY = max(0, (int)floorf((v - p.min_y - radius) * p.inv_h));
-    if (nMinCellY >= kGridRows) return 0xFFFFFFFFu;
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((v - p.min_y + radius) * p.inv_h));
-    if (nMaxCellY < 0) return 0xFFFFFFFFu;
-    const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-    const uint4* dm = reinterpret_cast<const uint4*>(mpdesc + (size_t)32 * i);
-    const uint4 m0 = dm[0], m1 = dm[1];
-    int bestDist = 256, bestIdx2 = -1;
-    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-        const int k0 = s.cell_off[ix * kGridRows + nMinCellY], k1 = s.cell_off[ix * kGridRows + nMaxCellY + 1];
-        for (int k = k0; k < k1; ++k) {
-            const int i2 = s.cell_idx[k];
-            if (bCheckLevels) {
-                const int o = s.koct[i2];
-                if (o < minLevel) continue;
-                if (maxLevel >= 0 && o > maxLevel) continue;
-            }
-            const float distx = s.kx[i2] - u, disty = s.ky[i2] - v;
-            if (!(fabsf(distx) < radius && fabsf(disty) < radius)) continue;
-            if (blk[i2]) continue;
-            if (uright && uright[i2] > 0) {
-                const float ur = rfmaf(-p.mbf, invzc, u);  // fused in ORBmatcher.cc.o
-                const float er = fabsf(ur - uright[i2]);
-                if (er > radius) continue;
-            }
-            const uint4* dc = reinterpret_cast<const uint4*>(cdesc + (size_t)32 * i2);
-            const uint4 c0 = dc[0], c1 = dc[1];
-            const int dist = __popc(m0.x ^ c0.x) + __popc(m0.y ^ c0.y) + __popc(m0.z ^ c0.z) + __popc(m0.w ^ c0.w) +
-                             __popc(m1.x ^ c1.x) + __popc(m1.y ^ c1.y) + __popc(m1.z ^ c1.z) + __popc(m1.w ^ c1.w);
-            if (dist < bestDist) {
-                bestDist = dist;
-                bestIdx2 = i2;
-            }
-        }
-    }
-    if (bestIdx2 < 0) return 0xFFFFFFFFu;
-    return ((unsigned)bestDist << 16) | (unsigned)bestIdx2;
+}
+
+// GetFeaturesInArea + the candidate loop of SearchByProjection (:1992-2058)
+// for LastFrame point i against the blocked flags `blk`.
+__device__ unsigned proj_scan(const plvi_proj_params& p, const GridSide& s, const unsigned char* blk, int i,
+                              const float* __restrict__ x3dc, const int* __restrict__ loct,
+                              const uint8_t* __restrict__ mpdesc, const float* __restrict__ uright) {
+    const float xc = x3dc[3 * i], yc = x3dc[3 * i + 1], zc = x3dc[3 * i + 2];
+    const float invzc = (float)(1.0 / (double)zc);
+    if (invzc < 0) return kScanSkip;
+    const float u = p.fx * xc / zc + p.cx, v = p.fy * yc / zc + p.cy;  // Pinhole::project
+    if (u < p.min_x || u > p.max_x) return kScanSkip;
+    if (v < p.min_y || v > p.max_y) return kScanSkip;
+    const int nLastOctave = loct[i];
+    if (nLastOctave < 0 || nLastOctave >= p.nlevels) return kScanSkip;  // no scale factor: no candidate
+    const float radius = p.th * p.scale_factors[nLastOctave];
+    int minLevel, maxLevel;
+    proj_levels(p, nLastOctave, minLevel, maxLevel);
+    GridWindow w;
+    if (!grid_window(p.min_x, p.min_y, p.inv_w, p.inv_h, u, v, radius, w)) return kScanSkip;
+    const UrightReject stereo{uright, rfmaf(-p.mbf, invzc, u), radius};  // ur fused in ORBmatcher.cc.o
+    BestOne best;
+    grid_walk(s, blk, w, u, v, radius, (minLevel > 0) || (maxLevel >= 0), minLevel, maxLevel,
+              mpdesc + (size_t)32 * i, stereo, best);
+    if (best.idx < 0) return kScanSkip;
+    return scan_pack(best.dist, best.idx);
 }
 
 __global__ __launch_bounds__(256) void search_by_projection_kernel(
@@ -176,40 +149,16 @@ __global__ __launch_bounds__(256) void search_by_projection_kernel(
     int* __restrict__ nmatches) {
     extern __shared__ __align__(16) unsigned char lds[];
     const int pr = blockIdx.x, tid = threadIdx.x;
-    const int nc = min(cur_n[pr], cur_cap), nl = min(last_n[pr], last_cap);
-    ProjLds s;
-    {
-        unsigned char* q = lds;
-        s.kx = reinterpret_cast<float*>(q); q += 4 * cur_cap;
-        s.ky = reinterpret_cast<float*>(q); q += 4 * cur_cap;
-        s.assign = reinterpret_cast<int*>(q); q += 4 * cur_cap;
-        s.best = reinterpret_cast<int*>(q); q += 4 * last_cap;
-        s.cell_off = reinterpret_cast<int*>(q); q += 4 * (kGridCells + 1);
-        s.cell_idx = reinterpret_cast<unsigned short*>(q); q += 2 * cur_cap;
-        s.ent = reinterpret_cast<unsigned short*>(q); q += 4 * last_cap;  // [last_cap] idx, [last_cap] bin
-        s.koct = q; q += cur_cap;
-        s.blocked = q; q += cur_cap;
-        s.pre = q; q += cur_cap;
-        s.nulled = q;
-    }
+    const int nl = min(last_n[pr], last_cap);
+    GridSide s;
+    GridGaps g{{(size_t)(4 * last_cap), (size_t)(4 * last_cap)}, {}};
+    unsigned char* q = lds;
+    grid_side_load<true, false>(s, q, pr, cur_cap, ckps, cdesc_all, cur_n, cblocked, cell_off_all, cell_idx_all, tid,
+                                &g);
+    int* best = reinterpret_cast<int*>(g.at[0]);                        // [last_cap]
+    unsigned short* ent = reinterpret_cast<unsigned short*>(g.at[1]);  // [last_cap] idx, [last_cap] bin
     __shared__ int s_hist[kProjHisto], s_keep[3], s_ne, s_nm;
-    const plvi_keypoint* K = ckps + (size_t)pr * cur_cap;
-    const uint8_t* cdesc = cdesc_all + (size_t)pr * cur_cap * 32;
     const float* ur = curight ? curight + (size_t)pr * cur_cap : nullptr;
-    for (int i = tid; i < nc; i += 256) {
-        s.kx[i] = K[i].x;
-        s.ky[i] = K[i].y;
-        s.koct[i] = (unsigned char)K[i].octave;
-        const unsigned char b = cblocked ? cblocked[(size_t)pr * cur_cap + i] : 0;
-        s.blocked[i] = b;
-        s.pre[i] = b;
-        s.nulled[i] = 0;
-        s.assign[i] = -1;
-    }
-    const int* CO = cell_off_all + (size_t)pr * (kGridCells + 1);
-    for (int c = tid; c <= kGridCells; c += 256) s.cell_off[c] = CO[c];
-    const int ncell = CO[kGridCells];
-    for (int k = tid; k < ncell; k += 256) s.cell_idx[k] = (unsigned short)cell_idx_all[(size_t)pr * cur_cap + k];
     if (tid < kProjHisto) s_hist[tid] = 0;
     __syncthreads();
     const float* x3dc = x3dc_all + (size_t)pr * last_cap * 3;
@@ -218,76 +167,37 @@ __global__ __launch_bounds__(256) void search_by_projection_kernel(
     const uint8_t* lflags = lflags_all + (size_t)pr * last_cap;
     // phase 1: every point against the flags on entry
     for (int i = tid; i < nl; i += 256)
-        s.best[i] = (lflags[i] & 1) ? (int)proj_scan(p, s, s.pre, i, x3dc, loct, mpdesc, cdesc, ur, nc) : -1;
+        best[i] = (lflags[i] & 1) ? (int)proj_scan(p, s, s.pre, i, x3dc, loct, mpdesc, ur) : -1;
     __syncthreads();
     // phase 2: the greedy assignment in LastFrame order (:2060-2083)
     if (tid == 0) {
-        const float factor = 1.0f / kProjHisto;
         const float* lang = lang_all + (size_t)pr * last_cap;
         int nm = 0, ne = 0;
         for (int i = 0; i < nl; ++i) {
-            unsigned b = (unsigned)s.best[i];
-            if (b == 0xFFFFFFFFu) continue;
+            unsigned b = (unsigned)best[i];
+            if (b == kScanSkip) continue;
             if (s.blocked[b & 0xFFFFu] != s.pre[b & 0xFFFFu])  // its best was taken meanwhile: re-scan
-                b = proj_scan(p, s, s.blocked, i, x3dc, loct, mpdesc, cdesc, ur, nc);
-            if (b == 0xFFFFFFFFu || (int)(b >> 16) > kProjThHigh) continue;
+                b = proj_scan(p, s, s.blocked, i, x3dc, loct, mpdesc, ur);
+            if (b == kScanSkip || (int)(b >> 16) > kProjThHigh) continue;
             const int i2 = (int)(b & 0xFFFFu);
             s.assign[i2] = i;
             s.blocked[i2] = (lflags[i] & 2) ? 1 : 0;  // the stored MapPoint's Observations() > 0
             ++nm;
             if (p.check_orientation) {
-                float rot = lang[i] - K[i2].angle;
-                if (rot < 0.0f) rot += 360.0f;
-                int bin = (int)roundf(rot * factor);
-                if (bin == kProjHisto) bin = 0;
-                s.ent[last_cap + ne] = (unsigned short)bin;
-                s.ent[ne++] = (unsigned short)i2;
+                const int bin = rot_bin(lang[i] - s.K[i2].angle, kProjHisto);
+                ent[last_cap + ne] = (unsigned short)bin;
+                ent[ne++] = (unsigned short)i2;
                 s_hist[bin]++;
             }
         }
         s_ne = ne;
         s_nm = nm;
-        // ComputeThreeMaxima (:2304-2345)
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int b = 0; b < kProjHisto; b++) {
-            const int c = s_hist[b];
-            if (c > max1) {
-                max3 = max2; max2 = max1; max1 = c;
-                ind3 = ind2; ind2 = ind1; ind1 = b;
-            } else if (c > max2) {
-                max3 = max2; max2 = c;
-                ind3 = ind2; ind2 = b;
-            } else if (c > max3) {
-                max3 = c;
-                ind3 = b;
-            }
-        }
-        if (max2 < 0.1f * (float)max1) {
-            ind2 = -1;
-            ind3 = -1;
-        } else if (max3 < 0.1f * (float)max1) {
-            ind3 = -1;
-        }
-        s_keep[0] = ind1; s_keep[1] = ind2; s_keep[2] = ind3;
+        three_maxima(s_hist, kProjHisto, s_keep);
     }
     __syncthreads();
     // phase 3: entries in dropped bins set mvpMapPoints[idx] = NULL (:2164-2174)
-    if (p.check_orientation) {
-        const int ne = s_ne;
-        int dropped = 0;
-        for (int e = tid; e < ne; e += 256) {
-            const int bin = s.ent[last_cap + e];
-            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
-                s.nulled[s.ent[e]] = 1;
-                ++dropped;
-            }
-        }
-        if (dropped) atomicSub(&s_nm, dropped);
-        __syncthreads();
-    }
-    int* M = match + (size_t)pr * cur_cap;
-    for (int i = tid; i < nc; i += 256) M[i] = s.nulled[i] ? -2 : s.assign[i];
-    if (tid == 0) nmatches[pr] = s_nm;
+    rotation_filter_and_store(s, p.check_orientation, ent, last_cap, s_keep, &s_ne, &s_nm,
+                              match + (size_t)pr * cur_cap, nmatches + pr, tid);
 }
 
 // ---------------------------------------------------------------------------
@@ -328,94 +238,24 @@ __device__ __forceinline__ void cam_project(const plvi_proj_params& p, const Cam
     v = rfmaf(p.fy * r, plvi::plvi_sinf(psi), p.cy);
 }
 
-constexpr unsigned kScanSkip = 0xFFFFFFFFu;   // left pass `continue`d: no right pass either
-constexpr unsigned kScanNone = 0xFFFFFFFEu;   // window searched, no candidate (bestIdx2 == -1)
-
 // GetFeaturesInArea(u, v, radius, levels, bRight) + the candidate loop
-// (:2033-2058 / :2109-2125) of point i on one side.
-__device__ unsigned proj2_scan(const plvi_proj_params& p, const ProjLds& s, const unsigned char* blk, float u, float v,
-                               int nLastOctave, const uint8_t* __restrict__ mpd, const uint8_t* __restrict__ cdesc,
-                               bool left) {
-    if (nLastOctave < 0 || nLastOctave >= p.nlevels) return left ? kScanSkip : kScanNone;  // no scale factor
+// (:2033-2058 / :2109-2125) of point i on one side.  An empty vIndices2
+// `continue`s the left pass (kScanSkip) but only ends the right one.
+__device__ unsigned proj2_scan(const plvi_proj_params& p, const GridSide& s, const unsigned char* blk, float u, float v,
+                               int nLastOctave, const uint8_t* __restrict__ mpd, bool left) {
+    const unsigned empty = left ? kScanSkip : kScanNone;
+    if (nLastOctave < 0 || nLastOctave >= p.nlevels) return empty;  // no scale factor
     const float radius = p.th * p.scale_factors[nLastOctave];
     int minLevel, maxLevel;
-    if (p.forward) { minLevel = nLastOctave; maxLevel = -1; }
-    else if (p.backward) { minLevel = 0; maxLevel = nLastOctave; }
-    else { minLevel = nLastOctave - 1; maxLevel = nLastOctave + 1; }
-    const unsigned empty = left ? kScanSkip : kScanNone;
-    const int nMinCellX = max(0, (int)floorf((u - p.min_x - radius) * p.inv_w));
-    if (nMinCellX >= kGridCols) return empty;
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((u - p.min_x + radius) * p.inv_w));
-    if (nMaxCellX < 0) return empty;
-    const int nMinCellY = max(0, (int)floorf((v - p.min_y - radius) * p.inv_h));
-    if (nMinCellY >= kGridRows) return empty;
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((v - p.min_y + radius) * p.inv_h));
-    if (nMaxCellY < 0) return empty;
-    const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-    const uint4* dm = reinterpret_cast<const uint4*>(mpd);
-    const uint4 m0 = dm[0], m1 = dm[1];
-    int bestDist = 256, bestIdx2 = -1;
-    bool any = false;  // vIndices2 non-empty
-    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-        const int k0 = s.cell_off[ix * kGridRows + nMinCellY], k1 = s.cell_off[ix * kGridRows + nMaxCellY + 1];
-        for (int k = k0; k < k1; ++k) {
-            const int i2 = s.cell_idx[k];
-            if (bCheckLevels) {
-                const int o = s.koct[i2];
-                if (o < minLevel) continue;
-                if (maxLevel >= 0 && o > maxLevel) continue;
-            }
-            const float distx = s.kx[i2] - u, disty = s.ky[i2] - v;
-            if (!(fabsf(distx) < radius && fabsf(disty) < radius)) continue;
-            any = true;
-            if (blk[i2]) continue;
-            const uint4* dc = reinterpret_cast<const uint4*>(cdesc + (size_t)32 * i2);
-            const uint4 c0 = dc[0], c1 = dc[1];
-            const int dist = __popc(m0.x ^ c0.x) + __popc(m0.y ^ c0.y) + __popc(m0.z ^ c0.z) + __popc(m0.w ^ c0.w) +
-                             __popc(m1.x ^ c1.x) + __popc(m1.y ^ c1.y) + __popc(m1.z ^ c1.z) + __popc(m1.w ^ c1.w);
-            if (dist < bestDist) {
-                bestDist = dist;
-                bestIdx2 = i2;
-            }
-        }
-    }
+    proj_levels(p, nLastOctave, minLevel, maxLevel);
+    GridWindow w;
+    if (!grid_window(p.min_x, p.min_y, p.inv_w, p.inv_h, u, v, radius, w)) return empty;
+    BestOne best;
+    const bool any = grid_walk(s, blk, w, u, v, radius, (minLevel > 0) || (maxLevel >= 0), minLevel, maxLevel, mpd,
+                               NoReject{}, best);  // any: vIndices2 non-empty
     if (!any) return empty;
-    if (bestIdx2 < 0) return kScanNone;
-    return ((unsigned)bestDist << 16) | (unsigned)bestIdx2;
-}
-
-struct ProjSide {
-    ProjLds s;
-    const plvi_keypoint* K;
-    const uint8_t* desc;
-    int n;
-};
-
-__device__ void proj_side_load(ProjSide& d, unsigned char*& q, int cap, const uint8_t* blocked, const int* CO,
-                               const int* CI, int tid) {
-    d.s.kx = reinterpret_cast<float*>(q); q += 4 * cap;
-    d.s.ky = reinterpret_cast<float*>(q); q += 4 * cap;
-    d.s.assign = reinterpret_cast<int*>(q); q += 4 * cap;
-    d.s.cell_off = reinterpret_cast<int*>(q); q += 4 * (kGridCells + 1);
-    d.s.cell_idx = reinterpret_cast<unsigned short*>(q); q += 2 * cap;
-    d.s.koct = q; q += cap;
-    d.s.blocked = q; q += cap;
-    d.s.pre = q; q += cap;
-    d.s.nulled = q; q += cap;
-    q = reinterpret_cast<unsigned char*>(((uintptr_t)q + 15) & ~(uintptr_t)15);
-    for (int i = tid; i < d.n; i += 256) {
-        d.s.kx[i] = d.K[i].x;
-        d.s.ky[i] = d.K[i].y;
-        d.s.koct[i] = (unsigned char)d.K[i].octave;
-        const unsigned char b = blocked ? (blocked[i] != 0) : 0;
-        d.s.blocked[i] = b;
-        d.s.pre[i] = b;
-        d.s.nulled[i] = 0;
-        d.s.assign[i] = -1;
-    }
-    for (int c = tid; c <= kGridCells; c += 256) d.s.cell_off[c] = CO[c];
-    const int ncell = CO[kGridCells];
-    for (int k = tid; k < ncell; k += 256) d.s.cell_idx[k] = (unsigned short)CI[k];
+    if (best.idx < 0) return kScanNone;
+    return scan_pack(best.dist, best.idx);
 }
 
 __global__ __launch_bounds__(256) void search_by_projection2_kernel(
@@ -430,23 +270,17 @@ __global__ __launch_bounds__(256) void search_by_projection2_kernel(
     extern __shared__ __align__(16) unsigned char lds[];
     const int pr = blockIdx.x, tid = threadIdx.x;
     const int nl = min(last_n[pr], last_cap);
-    ProjSide S[2];
-    S[0].n = min(l_n[pr], l_cap);
-    S[1].n = min(r_n[pr], r_cap);
-    S[0].K = lkps + (size_t)pr * l_cap;
-    S[1].K = rkps + (size_t)pr * r_cap;
-    S[0].desc = ldesc_all + (size_t)pr * l_cap * 32;
-    S[1].desc = rdesc_all + (size_t)pr * r_cap * 32;
+    GridSide S[2];
     unsigned* best;          // [2][last_cap]
     unsigned short* ent;     // [2 * last_cap] keypoint, [2 * last_cap] bin | side << 15
     {
         unsigned char* q = lds;
         best = reinterpret_cast<unsigned*>(q); q += 8 * (size_t)last_cap;
         ent = reinterpret_cast<unsigned short*>(q); q += 8 * (size_t)last_cap;
-        proj_side_load(S[0], q, l_cap, lblocked ? lblocked + (size_t)pr * l_cap : nullptr,
-                       lcell_off_all + (size_t)pr * (kGridCells + 1), lcell_idx_all + (size_t)pr * l_cap, tid);
-        proj_side_load(S[1], q, r_cap, rblocked ? rblocked + (size_t)pr * r_cap : nullptr,
-                       rcell_off_all + (size_t)pr * (kGridCells + 1), rcell_idx_all + (size_t)pr * r_cap, tid);
+        grid_side_load<true, true>(S[0], q, pr, l_cap, lkps, ldesc_all, l_n, lblocked, lcell_off_all, lcell_idx_all,
+                                   tid);
+        grid_side_load<true, true>(S[1], q, pr, r_cap, rkps, rdesc_all, r_n, rblocked, rcell_off_all, rcell_idx_all,
+                                   tid);
     }
     __shared__ int s_hist[kProjHisto], s_keep[3], s_ne, s_nm;
     if (tid < kProjHisto) s_hist[tid] = 0;
@@ -473,8 +307,8 @@ __global__ __launch_bounds__(256) void search_by_projection2_kernel(
         float ul, vl, ur, vr;
         if ((lflags[i] & 1) && project(i, ul, vl, ur, vr)) {
             const uint8_t* mpd = mpdesc + (size_t)32 * i;
-            bl = proj2_scan(p, S[0].s, S[0].s.pre, ul, vl, loct[i], mpd, S[0].desc, true);
-            if (bl != kScanSkip) br = proj2_scan(p, S[1].s, S[1].s.pre, ur, vr, loct[i], mpd, S[1].desc, false);
+            bl = proj2_scan(p, S[0], S[0].pre, ul, vl, loct[i], mpd, true);
+            if (bl != kScanSkip) br = proj2_scan(p, S[1], S[1].pre, ur, vr, loct[i], mpd, false);
         }
         best[i] = bl;
         best[last_cap + i] = br;
@@ -482,33 +316,38 @@ __global__ __launch_bounds__(256) void search_by_projection2_kernel(
     __syncthreads();
     // phase 2: LastFrame order, left (:2060-2083) then right (:2127-2148)
     if (tid == 0) {
-        const float factor = 1.0f / kProjHisto;
         const float* lang = lang_all + (size_t)pr * last_cap;
         int nm = 0, ne = 0;
         for (int i = 0; i < nl; ++i) {
             if (best[i] == kScanSkip) continue;
-            float ul, vl, ur, vr;
-            bool projected = false;
+            // a side whose best was taken meanwhile is re-scanned (the sides'
+            // flags are separate, so both are known here); one projection for
+            // both, and the side loop unrolled: S[c] by constant index stays
+            // in registers
+            bool stale[2];
+#pragma unroll
             for (int c = 0; c < 2; ++c) {
-                ProjSide& A = S[c];
+                const unsigned b = best[c * last_cap + i];
+                stale[c] = b != kScanSkip && b != kScanNone && S[c].blocked[b & 0xFFFFu] != S[c].pre[b & 0xFFFFu];
+            }
+            float ul, vl, ur, vr;
+            if (stale[0] || stale[1]) project(i, ul, vl, ur, vr);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                GridSide& A = S[c];
                 unsigned b = best[c * last_cap + i];
                 if (b == kScanSkip || b == kScanNone) continue;  // no unblocked candidate stays so
-                if (A.s.blocked[b & 0xFFFFu] != A.s.pre[b & 0xFFFFu]) {  // its best was taken meanwhile: re-scan
-                    if (!projected) projected = project(i, ul, vl, ur, vr);
-                    b = proj2_scan(p, A.s, A.s.blocked, c ? ur : ul, c ? vr : vl, loct[i], mpdesc + (size_t)32 * i,
-                                   A.desc, c == 0);
+                if (stale[c]) {
+                    b = proj2_scan(p, A, A.blocked, c ? ur : ul, c ? vr : vl, loct[i], mpdesc + (size_t)32 * i, c == 0);
                     if (b == kScanSkip || b == kScanNone) continue;
                 }
                 if ((int)(b >> 16) > kProjThHigh) continue;
                 const int i2 = (int)(b & 0xFFFFu);
-                A.s.assign[i2] = i;
-                A.s.blocked[i2] = (lflags[i] & 2) ? 1 : 0;  // the stored MapPoint's Observations() > 0
+                A.assign[i2] = i;
+                A.blocked[i2] = (lflags[i] & 2) ? 1 : 0;  // the stored MapPoint's Observations() > 0
                 ++nm;
                 if (p.check_orientation) {
-                    float rot = lang[i] - A.K[i2].angle;
-                    if (rot < 0.0f) rot += 360.0f;
-                    int bin = (int)roundf(rot * factor);
-                    if (bin == kProjHisto) bin = 0;
+                    const int bin = rot_bin(lang[i] - A.K[i2].angle, kProjHisto);
                     ent[2 * last_cap + ne] = (unsigned short)(bin | c << 15);
                     ent[ne++] = (unsigned short)i2;
                     s_hist[bin]++;
@@ -517,27 +356,7 @@ __global__ __launch_bounds__(256) void search_by_projection2_kernel(
         }
         s_ne = ne;
         s_nm = nm;
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;  // ComputeThreeMaxima (:2304-2345)
-        for (int b = 0; b < kProjHisto; b++) {
-            const int c = s_hist[b];
-            if (c > max1) {
-                max3 = max2; max2 = max1; max1 = c;
-                ind3 = ind2; ind2 = ind1; ind1 = b;
-            } else if (c > max2) {
-                max3 = max2; max2 = c;
-                ind3 = ind2; ind2 = b;
-            } else if (c > max3) {
-                max3 = c;
-                ind3 = b;
-            }
-        }
-        if (max2 < 0.1f * (float)max1) {
-            ind2 = -1;
-            ind3 = -1;
-        } else if (max3 < 0.1f * (float)max1) {
-            ind3 = -1;
-        }
-        s_keep[0] = ind1; s_keep[1] = ind2; s_keep[2] = ind3;
+        three_maxima(s_hist, kProjHisto, s_keep);
     }
     __syncthreads();
     // phase 3: entries in dropped bins set mvpMapPoints[idx] = NULL (:2155-2175)
@@ -547,7 +366,8 @@ __global__ __launch_bounds__(256) void search_by_projection2_kernel(
         for (int e = tid; e < ne; e += 256) {
             const int code = ent[2 * last_cap + e], bin = code & 0x7FFF;
             if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
-                S[code >> 15].s.nulled[ent[e]] = 1;
+                unsigned char* nulled = (code >> 15) ? S[1].nulled : S[0].nulled;
+                nulled[ent[e]] = 1;
                 ++dropped;
             }
         }
@@ -556,8 +376,8 @@ __global__ __launch_bounds__(256) void search_by_projection2_kernel(
     }
     int* ML = match_l + (size_t)pr * l_cap;
     int* MR = match_r + (size_t)pr * r_cap;
-    for (int i = tid; i < S[0].n; i += 256) ML[i] = S[0].s.nulled[i] ? -2 : S[0].s.assign[i];
-    for (int i = tid; i < S[1].n; i += 256) MR[i] = S[1].s.nulled[i] ? -2 : S[1].s.assign[i];
+    for (int i = tid; i < S[0].n; i += 256) ML[i] = S[0].nulled[i] ? -2 : S[0].assign[i];
+    for (int i = tid; i < S[1].n; i += 256) MR[i] = S[1].nulled[i] ? -2 : S[1].assign[i];
     if (tid == 0) nmatches[pr] = s_nm;
 }
 
@@ -574,12 +394,12 @@ __global__ __launch_bounds__(256) void search_by_projection2_kernel(
 // level-aware ratio test and the assignment.
 // fbit: the MapPoint flag that enables this scan; use_th: the radius is
 // scaled by th (the left camera's branch only, :69-70 -- not :148)
-__device__ void local_scan(const plvi_local_params& p, const ProjLds& s, const unsigned char* blk, int m,
+__device__ void local_scan(const plvi_local_params& p, const GridSide& s, const unsigned char* blk, int m,
                            const unsigned char* __restrict__ fl, const float* __restrict__ proj,
                            const int* __restrict__ lvl, const uint8_t* __restrict__ mpdesc,
-                           const uint8_t* __restrict__ cdesc, const float* __restrict__ uright, unsigned* b1,
-                           unsigned* b2, unsigned char fbit = 1, bool use_th = true) {
-    *b1 = *b2 = 0xFFFFFFFFu;
+                           const float* __restrict__ uright, unsigned* b1, unsigned* b2, unsigned char fbit = 1,
+                           bool use_th = true) {
+    *b1 = *b2 = kScanSkip;
     if (!(fl[m] & fbit)) return;
     const float x = proj[4 * m], y = proj[4 * m + 1], xr = proj[4 * m + 2], vcos = proj[4 * m + 3];
     const int L = lvl[m];
@@ -588,52 +408,14 @@ __device__ void local_scan(const plvi_local_params& p, const ProjLds& s, const u
     if (use_th && p.th != 1.0) r *= p.th;
     const float radius = r * p.scale_factors[L];
     const int minLevel = L - 1, maxLevel = L;
-    const int nMinCellX = max(0, (int)floorf((x - p.min_x - radius) * p.inv_w));
-    if (nMinCellX >= kGridCols) return;
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - p.min_x + radius) * p.inv_w));
-    if (nMaxCellX < 0) return;
-    const int nMinCellY = max(0, (int)floorf((y - p.min_y - radius) * p.inv_h));
-    if (nMinCellY >= kGridRows) return;
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - p.min_y + radius) * p.inv_h));
-    if (nMaxCellY < 0) return;
-    const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-    const uint4* dm = reinterpret_cast<const uint4*>(mpdesc + (size_t)32 * m);
-    const uint4 m0 = dm[0], m1 = dm[1];
-    int bestDist = 256, bestDist2 = 256, bestIdx = -1, secondIdx = -1;
-    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-        const int k0 = s.cell_off[ix * kGridRows + nMinCellY], k1 = s.cell_off[ix * kGridRows + nMaxCellY + 1];
-        for (int k = k0; k < k1; ++k) {
-            const int idx = s.cell_idx[k];
-            if (bCheckLevels) {
-                const int o = s.koct[idx];
-                if (o < minLevel) continue;
-                if (maxLevel >= 0 && o > maxLevel) continue;
-            }
-            const float distx = s.kx[idx] - x, disty = s.ky[idx] - y;
-            if (!(fabsf(distx) < radius && fabsf(disty) < radius)) continue;
-            if (blk[idx]) continue;
-            if (uright && uright[idx] > 0) {
-                const float er = fabsf(xr - uright[idx]);
-                if (er > radius) continue;
-            }
-            const uint4* dc = reinterpret_cast<const uint4*>(cdesc + (size_t)32 * idx);
-            const uint4 c0 = dc[0], c1 = dc[1];
-            const int dist = __popc(m0.x ^ c0.x) + __popc(m0.y ^ c0.y) + __popc(m0.z ^ c0.z) + __popc(m0.w ^ c0.w) +
-                             __popc(m1.x ^ c1.x) + __popc(m1.y ^ c1.y) + __popc(m1.z ^ c1.z) + __popc(m1.w ^ c1.w);
-            if (dist < bestDist) {
-                bestDist2 = bestDist;
-                secondIdx = bestIdx;
-                bestDist = dist;
-                bestIdx = idx;
-            } else if (dist < bestDist2) {
-                bestDist2 = dist;
-                secondIdx = idx;
-            }
-        }
-    }
-    if (bestIdx < 0) return;
-    *b1 = ((unsigned)bestDist << 16) | (unsigned)bestIdx;
-    if (secondIdx >= 0) *b2 = ((unsigned)bestDist2 << 16) | (unsigned)secondIdx;
+    GridWindow w;
+    if (!grid_window(p.min_x, p.min_y, p.inv_w, p.inv_h, x, y, radius, w)) return;
+    BestTwo best;
+    grid_walk(s, blk, w, x, y, radius, (minLevel > 0) || (maxLevel >= 0), minLevel, maxLevel,
+              mpdesc + (size_t)32 * m, UrightReject{uright, xr, radius}, best);
+    if (best.idx < 0) return;
+    *b1 = scan_pack(best.dist, best.idx);
+    if (best.idx2 >= 0) *b2 = scan_pack(best.dist2, best.idx2);
 }
 
 __global__ __launch_bounds__(256) void search_local_kernel(
@@ -644,60 +426,37 @@ __global__ __launch_bounds__(256) void search_local_kernel(
     const int* __restrict__ mp_n, int mp_cap, int* __restrict__ match, int* __restrict__ nmatches) {
     extern __shared__ __align__(16) unsigned char lds[];
     const int fr = blockIdx.x, tid = threadIdx.x;
-    const int nc = min(cur_n[fr], cur_cap), nm = min(mp_n[fr], mp_cap);
-    ProjLds s;
-    unsigned *best1, *best2;
-    {
-        unsigned char* q = lds;
-        s.kx = reinterpret_cast<float*>(q); q += 4 * cur_cap;
-        s.ky = reinterpret_cast<float*>(q); q += 4 * cur_cap;
-        s.assign = reinterpret_cast<int*>(q); q += 4 * cur_cap;
-        best1 = reinterpret_cast<unsigned*>(q); q += 4 * mp_cap;
-        best2 = reinterpret_cast<unsigned*>(q); q += 4 * mp_cap;
-        s.cell_off = reinterpret_cast<int*>(q); q += 4 * (kGridCells + 1);
-        s.cell_idx = reinterpret_cast<unsigned short*>(q); q += 2 * cur_cap;
-        s.koct = q; q += cur_cap;
-        s.blocked = q; q += cur_cap;
-        s.pre = q;
-    }
-    const plvi_keypoint* K = ckps + (size_t)fr * cur_cap;
-    const uint8_t* cdesc = cdesc_all + (size_t)fr * cur_cap * 32;
+    const int nm = min(mp_n[fr], mp_cap);
+    GridSide s;
+    GridGaps g{{(size_t)(8 * mp_cap), 0}, {}};
+    unsigned char* q = lds;
+    grid_side_load<false, false>(s, q, fr, cur_cap, ckps, cdesc_all, cur_n, cblocked, cell_off_all, cell_idx_all, tid,
+                                 &g);
+    unsigned* best1 = reinterpret_cast<unsigned*>(g.at[0]);  // [mp_cap]
+    unsigned* best2 = best1 + mp_cap;                        // [mp_cap]
     const float* ur = curight ? curight + (size_t)fr * cur_cap : nullptr;
-    for (int i = tid; i < nc; i += 256) {
-        s.kx[i] = K[i].x;
-        s.ky[i] = K[i].y;
-        s.koct[i] = (unsigned char)K[i].octave;
-        const unsigned char b = cblocked ? cblocked[(size_t)fr * cur_cap + i] : 0;
-        s.blocked[i] = b;
-        s.pre[i] = b;
-        s.assign[i] = -1;
-    }
-    const int* CO = cell_off_all + (size_t)fr * (kGridCells + 1);
-    for (int c = tid; c <= kGridCells; c += 256) s.cell_off[c] = CO[c];
-    const int ncell = CO[kGridCells];
-    for (int k = tid; k < ncell; k += 256) s.cell_idx[k] = (unsigned short)cell_idx_all[(size_t)fr * cur_cap + k];
     __syncthreads();
     const unsigned char* fl = flags_all + (size_t)fr * mp_cap;
     const float* proj = proj_all + (size_t)fr * mp_cap * 4;
     const int* lvl = level_all + (size_t)fr * mp_cap;
     const uint8_t* mpdesc = mpdesc_all + (size_t)fr * mp_cap * 32;
     // phase 1: every MapPoint against the flags on entry
-    for (int m = tid; m < nm; m += 256) local_scan(p, s, s.pre, m, fl, proj, lvl, mpdesc, cdesc, ur, &best1[m], &best2[m]);
+    for (int m = tid; m < nm; m += 256) local_scan(p, s, s.pre, m, fl, proj, lvl, mpdesc, ur, &best1[m], &best2[m]);
     __syncthreads();
     // phase 2: the assignment in vpMapPoints order (:98-117)
     if (tid == 0) {
         int nmt = 0;
         for (int m = 0; m < nm; ++m) {
             unsigned b1 = best1[m], b2 = best2[m];
-            if (b1 == 0xFFFFFFFFu) continue;
-            const int i1 = (int)(b1 & 0xFFFFu), i2 = b2 == 0xFFFFFFFFu ? -1 : (int)(b2 & 0xFFFFu);
+            if (b1 == kScanSkip) continue;
+            const int i1 = (int)(b1 & 0xFFFFu), i2 = b2 == kScanSkip ? -1 : (int)(b2 & 0xFFFFu);
             if (s.blocked[i1] != s.pre[i1] || (i2 >= 0 && s.blocked[i2] != s.pre[i2])) {
-                local_scan(p, s, s.blocked, m, fl, proj, lvl, mpdesc, cdesc, ur, &b1, &b2);  // blocked meanwhile
-                if (b1 == 0xFFFFFFFFu) continue;
+                local_scan(p, s, s.blocked, m, fl, proj, lvl, mpdesc, ur, &b1, &b2);  // blocked meanwhile
+                if (b1 == kScanSkip) continue;
             }
             const int bestDist = (int)(b1 >> 16), bestIdx = (int)(b1 & 0xFFFFu);
-            const int bestDist2 = b2 == 0xFFFFFFFFu ? 256 : (int)(b2 >> 16);
-            const int bestLevel = s.koct[bestIdx], bestLevel2 = b2 == 0xFFFFFFFFu ? -1 : s.koct[b2 & 0xFFFFu];
+            const int bestDist2 = b2 == kScanSkip ? 256 : (int)(b2 >> 16);
+            const int bestLevel = s.koct[bestIdx], bestLevel2 = b2 == kScanSkip ? -1 : s.koct[b2 & 0xFFFFu];
             if (bestDist <= kProjThHigh) {
                 if (bestLevel == bestLevel2 && bestDist > p.nnratio * bestDist2) continue;
                 if (bestLevel != bestLevel2 || bestDist <= p.nnratio * bestDist2) {
@@ -711,7 +470,7 @@ __global__ __launch_bounds__(256) void search_local_kernel(
     }
     __syncthreads();
     int* M = match + (size_t)fr * cur_cap;
-    for (int i = tid; i < nc; i += 256) M[i] = s.assign[i];
+    for (int i = tid; i < s.n; i += 256) M[i] = s.assign[i];
 }
 
 // ---------------------------------------------------------------------------
@@ -729,38 +488,6 @@ __global__ __launch_bounds__(256) void search_local_kernel(
 // sides of every MapPoint in parallel against the entry flags, phase 2 walks
 // the MapPoints in order, left then right, re-scanning a side whose best or
 // second candidate was blocked meanwhile.
-struct LocalSide {
-    ProjLds s;
-    const uint8_t* desc;
-    const int* pair;  // mvLeftToRightMatch / mvRightToLeftMatch (NULL = none)
-    int n;
-};
-
-__device__ void local_side_load(LocalSide& d, unsigned char*& q, int cap, const plvi_keypoint* K,
-                                const uint8_t* blocked, const int* CO, const int* CI, int tid) {
-    d.s.kx = reinterpret_cast<float*>(q); q += 4 * cap;
-    d.s.ky = reinterpret_cast<float*>(q); q += 4 * cap;
-    d.s.assign = reinterpret_cast<int*>(q); q += 4 * cap;
-    d.s.cell_off = reinterpret_cast<int*>(q); q += 4 * (kGridCells + 1);
-    d.s.cell_idx = reinterpret_cast<unsigned short*>(q); q += 2 * cap;
-    d.s.koct = q; q += cap;
-    d.s.blocked = q; q += cap;
-    d.s.pre = q; q += cap;
-    q = reinterpret_cast<unsigned char*>(((uintptr_t)q + 15) & ~(uintptr_t)15);
-    for (int i = tid; i < d.n; i += 256) {
-        d.s.kx[i] = K[i].x;
-        d.s.ky[i] = K[i].y;
-        d.s.koct[i] = (unsigned char)K[i].octave;
-        const unsigned char b = blocked ? blocked[i] : 0;
-        d.s.blocked[i] = b;
-        d.s.pre[i] = b;
-        d.s.assign[i] = -1;
-    }
-    for (int c = tid; c <= kGridCells; c += 256) d.s.cell_off[c] = CO[c];
-    const int ncell = CO[kGridCells];
-    for (int k = tid; k < ncell; k += 256) d.s.cell_idx[k] = (unsigned short)CI[k];
-}
-
 __global__ __launch_bounds__(256) void search_local2_kernel(
     plvi_local_params p, const plvi_keypoint* __restrict__ lkps, const uint8_t* __restrict__ ldesc_all,
     const int* __restrict__ l_n, int l_cap, const uint8_t* __restrict__ lblocked, const int* __restrict__ l2r_all,
@@ -774,21 +501,18 @@ __global__ __launch_bounds__(256) void search_local2_kernel(
     extern __shared__ __align__(16) unsigned char lds[];
     const int fr = blockIdx.x, tid = threadIdx.x;
     const int nm = min(mp_n[fr], mp_cap);
-    LocalSide S[2];
-    S[0].n = min(l_n[fr], l_cap);
-    S[1].n = min(r_n[fr], r_cap);
-    S[0].desc = ldesc_all + (size_t)fr * l_cap * 32;
-    S[1].desc = rdesc_all + (size_t)fr * r_cap * 32;
-    S[0].pair = l2r_all ? l2r_all + (size_t)fr * l_cap : nullptr;
-    S[1].pair = r2l_all ? r2l_all + (size_t)fr * r_cap : nullptr;
+    GridSide S[2];
+    // mvLeftToRightMatch / mvRightToLeftMatch (NULL = none)
+    const int* pair[2] = {l2r_all ? l2r_all + (size_t)fr * l_cap : nullptr,
+                          r2l_all ? r2l_all + (size_t)fr * r_cap : nullptr};
     unsigned* best;  // [4][mp_cap]: left best / second, right best / second
     {
         unsigned char* q = lds;
         best = reinterpret_cast<unsigned*>(q); q += 16 * (size_t)mp_cap;
-        local_side_load(S[0], q, l_cap, lkps + (size_t)fr * l_cap, lblocked ? lblocked + (size_t)fr * l_cap : nullptr,
-                        lcell_off_all + (size_t)fr * (kGridCells + 1), lcell_idx_all + (size_t)fr * l_cap, tid);
-        local_side_load(S[1], q, r_cap, rkps + (size_t)fr * r_cap, rblocked ? rblocked + (size_t)fr * r_cap : nullptr,
-                        rcell_off_all + (size_t)fr * (kGridCells + 1), rcell_idx_all + (size_t)fr * r_cap, tid);
+        grid_side_load<false, false>(S[0], q, fr, l_cap, lkps, ldesc_all, l_n, lblocked, lcell_off_all, lcell_idx_all,
+                                     tid);
+        grid_side_load<false, false>(S[1], q, fr, r_cap, rkps, rdesc_all, r_n, rblocked, rcell_off_all, rcell_idx_all,
+                                     tid);
     }
     __syncthreads();
     const unsigned char* fl = flags_all + (size_t)fr * mp_cap;
@@ -799,8 +523,8 @@ __global__ __launch_bounds__(256) void search_local2_kernel(
     // phase 1: both sides of every MapPoint against the flags on entry
     for (int m = tid; m < nm; m += 256)
         for (int c = 0; c < 2; ++c)
-            local_scan(p, S[c].s, S[c].s.pre, m, fl, proj[c], lvl[c], mpdesc, S[c].desc, nullptr,
-                       &best[(2 * c) * mp_cap + m], &best[(2 * c + 1) * mp_cap + m], fbit[c], c == 0);
+            local_scan(p, S[c], S[c].pre, m, fl, proj[c], lvl[c], mpdesc, nullptr, &best[(2 * c) * mp_cap + m],
+                       &best[(2 * c + 1) * mp_cap + m], fbit[c], c == 0);
     __syncthreads();
     // phase 2: vpMapPoints order, left (:62-143) then right (:145-211)
     // A stereo partner is overwritten unchecked (:133, :200), so a keypoint
@@ -812,29 +536,29 @@ __global__ __launch_bounds__(256) void search_local2_kernel(
         for (int m = 0; m < nm; ++m) {
             const unsigned char obs = (fl[m] & 2) ? 1 : 0;  // the stored MapPoint's Observations() > 0
             for (int c = 0; c < 2; ++c) {
-                LocalSide& A = S[c];
-                LocalSide& B = S[1 - c];
+                GridSide& A = S[c];
+                GridSide& B = S[1 - c];
                 unsigned b1 = best[(2 * c) * mp_cap + m], b2 = best[(2 * c + 1) * mp_cap + m];
-                if (b1 == 0xFFFFFFFFu && !unblocked[c]) continue;
-                const int i1 = (int)(b1 & 0xFFFFu), i2 = b2 == 0xFFFFFFFFu ? -1 : (int)(b2 & 0xFFFFu);
-                if (unblocked[c] || A.s.blocked[i1] != A.s.pre[i1] || (i2 >= 0 && A.s.blocked[i2] != A.s.pre[i2])) {
-                    local_scan(p, A.s, A.s.blocked, m, fl, proj[c], lvl[c], mpdesc, A.desc, nullptr, &b1, &b2, fbit[c],
+                if (b1 == kScanSkip && !unblocked[c]) continue;
+                const int i1 = (int)(b1 & 0xFFFFu), i2 = b2 == kScanSkip ? -1 : (int)(b2 & 0xFFFFu);
+                if (unblocked[c] || A.blocked[i1] != A.pre[i1] || (i2 >= 0 && A.blocked[i2] != A.pre[i2])) {
+                    local_scan(p, A, A.blocked, m, fl, proj[c], lvl[c], mpdesc, nullptr, &b1, &b2, fbit[c],
                                c == 0);  // blocked meanwhile
-                    if (b1 == 0xFFFFFFFFu) continue;
+                    if (b1 == kScanSkip) continue;
                 }
                 const int bestDist = (int)(b1 >> 16), bestIdx = (int)(b1 & 0xFFFFu);
-                const int bestDist2 = b2 == 0xFFFFFFFFu ? 256 : (int)(b2 >> 16);
-                const int bestLevel = A.s.koct[bestIdx], bestLevel2 = b2 == 0xFFFFFFFFu ? -1 : A.s.koct[b2 & 0xFFFFu];
+                const int bestDist2 = b2 == kScanSkip ? 256 : (int)(b2 >> 16);
+                const int bestLevel = A.koct[bestIdx], bestLevel2 = b2 == kScanSkip ? -1 : A.koct[b2 & 0xFFFFu];
                 if (bestDist > kProjThHigh) continue;
                 if (bestLevel == bestLevel2 && bestDist > p.nnratio * bestDist2) break;  // :127 / :197: next MapPoint
-                A.s.assign[bestIdx] = m;
-                A.s.blocked[bestIdx] = obs;
+                A.assign[bestIdx] = m;
+                A.blocked[bestIdx] = obs;
                 ++nmt;
-                const int o = A.pair ? A.pair[bestIdx] : -1;
+                const int o = pair[c] ? pair[c][bestIdx] : -1;
                 if (o >= 0 && o < B.n) {  // the stereo observation in the other image
-                    B.s.assign[o] = m;
-                    if (B.s.blocked[o] && !obs) unblocked[1 - c] = true;
-                    B.s.blocked[o] = obs;
+                    B.assign[o] = m;
+                    if (B.blocked[o] && !obs) unblocked[1 - c] = true;
+                    B.blocked[o] = obs;
                     ++nmt;
                 }
             }
@@ -844,8 +568,8 @@ __global__ __launch_bounds__(256) void search_local2_kernel(
     __syncthreads();
     int* ML = match_l + (size_t)fr * l_cap;
     int* MR = match_r + (size_t)fr * r_cap;
-    for (int i = tid; i < S[0].n; i += 256) ML[i] = S[0].s.assign[i];
-    for (int i = tid; i < S[1].n; i += 256) MR[i] = S[1].s.assign[i];
+    for (int i = tid; i < S[0].n; i += 256) ML[i] = S[0].assign[i];
+    for (int i = tid; i < S[1].n; i += 256) MR[i] = S[1].assign[i];
 }
 
 // ---------------------------------------------------------------------------
@@ -857,52 +581,25 @@ __global__ __launch_bounds__(256) void search_local2_kernel(
 // walks the MapPoints in KF order -- every assignment blocks its keypoint for
 // the later points (:2240-2242), so a point whose best was taken meanwhile is
 // re-scanned -- and phase 3 is the rotation filter.
-__device__ unsigned reloc_scan(const plvi_reloc_params& p, const ProjLds& s, const unsigned char* blk, int i,
+__device__ unsigned reloc_scan(const plvi_reloc_params& p, const GridSide& s, const unsigned char* blk, int i,
                                const float* __restrict__ x3dc, const float* __restrict__ dist,
-                               const int* __restrict__ lvl, const uint8_t* __restrict__ mpdesc,
-                               const uint8_t* __restrict__ cdesc) {
+                               const int* __restrict__ lvl, const uint8_t* __restrict__ mpdesc) {
     const float xc = x3dc[3 * i], yc = x3dc[3 * i + 1], zc = x3dc[3 * i + 2];
     const float u = p.fx * xc / zc + p.cx, v = p.fy * yc / zc + p.cy;  // Pinhole::project (no depth test here)
-    if (u < p.min_x || u > p.max_x) return 0xFFFFFFFFu;
-    if (v < p.min_y || v > p.max_y) return 0xFFFFFFFFu;
+    if (u < p.min_x || u > p.max_x) return kScanSkip;
+    if (v < p.min_y || v > p.max_y) return kScanSkip;
     const float dist3D = dist[3 * i], minDistance = dist[3 * i + 1], maxDistance = dist[3 * i + 2];
-    if (dist3D < minDistance || dist3D > maxDistance) return 0xFFFFFFFFu;
+    if (dist3D < minDistance || dist3D > maxDistance) return kScanSkip;
     const int L = lvl[i];
-    if (L < 0 || L >= p.nlevels) return 0xFFFFFFFFu;  // PredictScale clamps to [0, mnScaleLevels)
+    if (L < 0 || L >= p.nlevels) return kScanSkip;  // PredictScale clamps to [0, mnScaleLevels)
     const float radius = p.th * p.scale_factors[L];
-    const int minLevel = L - 1, maxLevel = L + 1;
-    const int nMinCellX = max(0, (int)floorf((u - p.min_x - radius) * p.inv_w));
-    if (nMinCellX >= kGridCols) return 0xFFFFFFFFu;
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((u - p.min_x + radius) * p.inv_w));
-    if (nMaxCellX < 0) return 0xFFFFFFFFu;
-    const int nMinCellY = max(0, (int)floorf((v - p.min_y - radius) * p.inv_h));
-    if (nMinCellY >= kGridRows) return 0xFFFFFFFFu;
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((v - p.min_y + radius) * p.inv_h));
-    if (nMaxCellY < 0) return 0xFFFFFFFFu;
-    const uint4* dm = reinterpret_cast<const uint4*>(mpdesc + (size_t)32 * i);
-    const uint4 m0 = dm[0], m1 = dm[1];
-    int bestDist = 256, bestIdx2 = -1;
-    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-        const int k0 = s.cell_off[ix * kGridRows + nMinCellY], k1 = s.cell_off[ix * kGridRows + nMaxCellY + 1];
-        for (int k = k0; k < k1; ++k) {
-            const int i2 = s.cell_idx[k];
-            const int o = s.koct[i2];  // bCheckLevels holds: maxLevel >= 0
-            if (o < minLevel || o > maxLevel) continue;
-            const float distx = s.kx[i2] - u, disty = s.ky[i2] - v;
-            if (!(fabsf(distx) < radius && fabsf(disty) < radius)) continue;
-            if (blk[i2]) continue;
-            const uint4* dc = reinterpret_cast<const uint4*>(cdesc + (size_t)32 * i2);
-            const uint4 c0 = dc[0], c1 = dc[1];
-            const int d = __popc(m0.x ^ c0.x) + __popc(m0.y ^ c0.y) + __popc(m0.z ^ c0.z) + __popc(m0.w ^ c0.w) +
-                          __popc(m1.x ^ c1.x) + __popc(m1.y ^ c1.y) + __popc(m1.z ^ c1.z) + __popc(m1.w ^ c1.w);
-            if (d < bestDist) {
-                bestDist = d;
-                bestIdx2 = i2;
-            }
-        }
-    }
-    if (bestIdx2 < 0) return 0xFFFFFFFFu;
-    return ((unsigned)bestDist << 16) | (unsigned)bestIdx2;
+    GridWindow w;
+    if (!grid_window(p.min_x, p.min_y, p.inv_w, p.inv_h, u, v, radius, w)) return kScanSkip;
+    BestOne best;
+    grid_walk(s, blk, w, u, v, radius, true, L - 1, L + 1, mpdesc + (size_t)32 * i, NoReject{},
+              best);  // bCheckLevels holds: maxLevel >= 0
+    if (best.idx < 0) return kScanSkip;
+    return scan_pack(best.dist, best.idx);
 }
 
 __global__ __launch_bounds__(256) void search_reloc_kernel(
@@ -914,39 +611,15 @@ __global__ __launch_bounds__(256) void search_reloc_kernel(
     int kf_cap, int* __restrict__ match, int* __restrict__ nmatches) {
     extern __shared__ __align__(16) unsigned char lds[];
     const int pr = blockIdx.x, tid = threadIdx.x;
-    const int nc = min(cur_n[pr], cur_cap), nk = min(kf_n[pr], kf_cap);
-    ProjLds s;
-    {
-        unsigned char* q = lds;
-        s.kx = reinterpret_cast<float*>(q); q += 4 * cur_cap;
-        s.ky = reinterpret_cast<float*>(q); q += 4 * cur_cap;
-        s.assign = reinterpret_cast<int*>(q); q += 4 * cur_cap;
-        s.best = reinterpret_cast<int*>(q); q += 4 * kf_cap;
-        s.cell_off = reinterpret_cast<int*>(q); q += 4 * (kGridCells + 1);
-        s.cell_idx = reinterpret_cast<unsigned short*>(q); q += 2 * cur_cap;
-        s.ent = reinterpret_cast<unsigned short*>(q); q += 4 * kf_cap;  // [kf_cap] idx, [kf_cap] bin
-        s.koct = q; q += cur_cap;
-        s.blocked = q; q += cur_cap;
-        s.pre = q; q += cur_cap;
-        s.nulled = q;
-    }
+    const int nk = min(kf_n[pr], kf_cap);
+    GridSide s;
+    GridGaps g{{(size_t)(4 * kf_cap), (size_t)(4 * kf_cap)}, {}};
+    unsigned char* q = lds;
+    grid_side_load<true, true>(s, q, pr, cur_cap, ckps, cdesc_all, cur_n, cblocked, cell_off_all, cell_idx_all, tid,
+                               &g);
+    int* best = reinterpret_cast<int*>(g.at[0]);                        // [kf_cap]
+    unsigned short* ent = reinterpret_cast<unsigned short*>(g.at[1]);  // [kf_cap] idx, [kf_cap] bin
     __shared__ int s_hist[kProjHisto], s_keep[3], s_ne, s_nm;
-    const plvi_keypoint* K = ckps + (size_t)pr * cur_cap;
-    const uint8_t* cdesc = cdesc_all + (size_t)pr * cur_cap * 32;
-    for (int i = tid; i < nc; i += 256) {
-        s.kx[i] = K[i].x;
-        s.ky[i] = K[i].y;
-        s.koct[i] = (unsigned char)K[i].octave;
-        const unsigned char b = cblocked ? (cblocked[(size_t)pr * cur_cap + i] != 0) : 0;
-        s.blocked[i] = b;
-        s.pre[i] = b;
-        s.nulled[i] = 0;
-        s.assign[i] = -1;
-    }
-    const int* CO = cell_off_all + (size_t)pr * (kGridCells + 1);
-    for (int c = tid; c <= kGridCells; c += 256) s.cell_off[c] = CO[c];
-    const int ncell = CO[kGridCells];
-    for (int k = tid; k < ncell; k += 256) s.cell_idx[k] = (unsigned short)cell_idx_all[(size_t)pr * cur_cap + k];
     if (tid < kProjHisto) s_hist[tid] = 0;
     __syncthreads();
     const float* x3dc = x3dc_all + (size_t)pr * kf_cap * 3;
@@ -956,95 +629,69 @@ __global__ __launch_bounds__(256) void search_reloc_kernel(
     const uint8_t* kfl = kflags_all + (size_t)pr * kf_cap;
     // phase 1: every KF MapPoint against mvpMapPoints on entry
     for (int i = tid; i < nk; i += 256)
-        s.best[i] = (kfl[i] & 1) ? (int)reloc_scan(p, s, s.pre, i, x3dc, dist, lvl, mpdesc, cdesc) : -1;
+        best[i] = (kfl[i] & 1) ? (int)reloc_scan(p, s, s.pre, i, x3dc, dist, lvl, mpdesc) : -1;
     __syncthreads();
     // phase 2: the assignment in KF order (:2260-2277)
     if (tid == 0) {
-        const float factor = 1.0f / kProjHisto;
         const float* kang = kang_all + (size_t)pr * kf_cap;
         int nm = 0, ne = 0;
         for (int i = 0; i < nk; ++i) {
-            unsigned b = (unsigned)s.best[i];
-            if (b == 0xFFFFFFFFu) continue;
+            unsigned b = (unsigned)best[i];
+            if (b == kScanSkip) continue;
             if (s.blocked[b & 0xFFFFu] != s.pre[b & 0xFFFFu])  // its best was taken meanwhile: re-scan
-                b = reloc_scan(p, s, s.blocked, i, x3dc, dist, lvl, mpdesc, cdesc);
-            if (b == 0xFFFFFFFFu || (int)(b >> 16) > p.orb_dist) continue;
+                b = reloc_scan(p, s, s.blocked, i, x3dc, dist, lvl, mpdesc);
+            if (b == kScanSkip || (int)(b >> 16) > p.orb_dist) continue;
             const int i2 = (int)(b & 0xFFFFu);
             s.assign[i2] = i;
             s.blocked[i2] = 1;
             ++nm;
             if (p.check_orientation) {
-                float rot = kang[i] - K[i2].angle;
-                if (rot < 0.0f) rot += 360.0f;
-                int bin = (int)roundf(rot * factor);
-                if (bin == kProjHisto) bin = 0;
-                s.ent[kf_cap + ne] = (unsigned short)bin;
-                s.ent[ne++] = (unsigned short)i2;
+                const int bin = rot_bin(kang[i] - s.K[i2].angle, kProjHisto);
+                ent[kf_cap + ne] = (unsigned short)bin;
+                ent[ne++] = (unsigned short)i2;
                 s_hist[bin]++;
             }
         }
         s_ne = ne;
         s_nm = nm;
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;  // ComputeThreeMaxima (:2304-2345)
-        for (int b = 0; b < kProjHisto; b++) {
-            const int c = s_hist[b];
-            if (c > max1) {
-                max3 = max2; max2 = max1; max1 = c;
-                ind3 = ind2; ind2 = ind1; ind1 = b;
-            } else if (c > max2) {
-                max3 = max2; max2 = c;
-                ind3 = ind2; ind2 = b;
-            } else if (c > max3) {
-                max3 = c;
-                ind3 = b;
-            }
-        }
-        if (max2 < 0.1f * (float)max1) {
-            ind2 = -1;
-            ind3 = -1;
-        } else if (max3 < 0.1f * (float)max1) {
-            ind3 = -1;
-        }
-        s_keep[0] = ind1; s_keep[1] = ind2; s_keep[2] = ind3;
+        three_maxima(s_hist, kProjHisto, s_keep);
     }
     __syncthreads();
     // phase 3: entries in dropped bins set mvpMapPoints[idx] = NULL (:2284-2296)
-    if (p.check_orientation) {
-        const int ne = s_ne;
-        int dropped = 0;
-        for (int e = tid; e < ne; e += 256) {
-            const int bin = s.ent[kf_cap + e];
-            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
-                s.nulled[s.ent[e]] = 1;
-                ++dropped;
-            }
-        }
-        if (dropped) atomicSub(&s_nm, dropped);
-        __syncthreads();
-    }
-    int* M = match + (size_t)pr * cur_cap;
-    for (int i = tid; i < nc; i += 256) M[i] = s.nulled[i] ? -2 : s.assign[i];
-    if (tid == 0) nmatches[pr] = s_nm;
+    rotation_filter_and_store(s, p.check_orientation, ent, kf_cap, s_keep, &s_ne, &s_nm, match + (size_t)pr * cur_cap,
+                              nmatches + pr, tid);
 }
 
-static size_t local_smem(int cur_cap, int mp_cap) {
-    return (size_t)cur_cap * (4 + 4 + 4 + 2 + 1 + 1 + 1) + (size_t)mp_cap * 8 + 4 * (kGridCells + 1) + 64;
+// Dynamic LDS of the kernels above: grid_side_load's arrays per image (with
+// or without `nulled`), the per-point tables, 64 bytes of slack.
+static size_t side_smem(int cap, bool nulled) {
+    return (size_t)cap * (4 + 4 + 4 + 2 + 1 + 1 + 1 + (nulled ? 1 : 0)) + 4 * (kGridCells + 1);
 }
+static size_t align16(size_t n) { return (n + 15) & ~size_t(15); }
+
+static size_t local_smem(int cur_cap, int mp_cap) { return side_smem(cur_cap, false) + (size_t)mp_cap * 8 + 64; }
 
 static size_t local2_smem(int l_cap, int r_cap, int mp_cap) {
-    auto side = [](int cap) { return ((size_t)cap * (4 + 4 + 4 + 2 + 1 + 1 + 1) + 4 * (kGridCells + 1) + 15) & ~size_t(15); };
-    return 16 * (size_t)mp_cap + side(l_cap) + side(r_cap) + 64;
+    return 16 * (size_t)mp_cap + align16(side_smem(l_cap, false)) + align16(side_smem(r_cap, false)) + 64;
 }
 
 static size_t proj2_smem(int l_cap, int r_cap, int last_cap) {
-    auto side = [](int cap) {
-        return ((size_t)cap * (4 + 4 + 4 + 2 + 1 + 1 + 1 + 1) + 4 * (kGridCells + 1) + 15) & ~size_t(15);
-    };
-    return 16 * (size_t)last_cap + side(l_cap) + side(r_cap) + 64;
+    return 16 * (size_t)last_cap + align16(side_smem(l_cap, true)) + align16(side_smem(r_cap, true)) + 64;
 }
 
 static size_t proj_smem(int cur_cap, int last_cap) {
-    return (size_t)cur_cap * (4 + 4 + 4 + 2 + 1 + 1 + 1 + 1) + (size_t)last_cap * (4 + 4) + 4 * (kGridCells + 1) + 64;
+    return side_smem(cur_cap, true) + (size_t)last_cap * (4 + 4) + 64;
+}
+
+// Launches a matcher kernel, one 256-thread block per pair with `smem` bytes
+// of dynamic LDS; PLVI_E_CAPACITY where that does not fit a CU.
+template <auto Kernel, class... Args>
+static int launch_matcher(int n_blocks, size_t smem, void* stream, const Args&... args) {
+    if (!lds_fits<Kernel>(smem)) return PLVI_E_CAPACITY;
+    PLVI_CHECK(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(Kernel, dim3(n_blocks), dim3(256), smem, (hipStream_t)stream, args...);
+    PLVI_CHECK(hipGetLastError());
+    return PLVI_OK;
 }
 
 static int grid_pow2(int cap) {
@@ -1073,6 +720,16 @@ extern "C" int plvi_assign_grid_batch(const plvi_keypoint* d_kps, const int* d_c
     return PLVI_OK;
 }
 
+// The grid of one staged image (keypoints in slot oK, count at d_n) into the
+// slots oCO / oCI, with the matcher's own image bounds.
+template <class Params>
+static int stage_grid(const HostStage& st, const Params* p, size_t oK, const int* d_n, int cap, size_t oCO,
+                      size_t oCI) {
+    const plvi_grid_params gp{p->min_x, p->min_y, p->inv_w, p->inv_h};
+    return plvi_assign_grid_batch(st.at<const plvi_keypoint>(oK), d_n, cap, 1, &gp, st.at<int>(oCO), st.at<int>(oCI),
+                                  nullptr);
+}
+
 extern "C" int plvi_search_by_projection_batch(int n_pairs, const plvi_proj_params* p, const plvi_keypoint* d_cur_kps,
                                                const uint8_t* d_cur_desc, const int* d_cur_n, int cur_cap,
                                                const uint8_t* d_cur_blocked, const float* d_cur_uright,
@@ -1084,15 +741,11 @@ extern "C" int plvi_search_by_projection_batch(int n_pairs, const plvi_proj_para
     if (!p || n_pairs < 0 || cur_cap < 1 || last_cap < 1 || cur_cap > 65535 || last_cap > 65535) return PLVI_E_BADARG;
     if (p->nlevels < 1 || p->nlevels > 16) return PLVI_E_BADARG;
     if (n_pairs == 0) return PLVI_OK;
-    const size_t smem = proj_smem(cur_cap, last_cap);
-    if (!lds_fits<search_by_projection_kernel>(smem)) return PLVI_E_CAPACITY;
-    PLVI_CHECK(hipFuncSetAttribute((const void*)search_by_projection_kernel,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(search_by_projection_kernel, dim3(n_pairs), dim3(256), smem, (hipStream_t)stream, *p, d_cur_kps,
-                       d_cur_desc, d_cur_n, cur_cap, d_cur_blocked, d_cur_uright, d_cell_off, d_cell_idx, d_x3dc,
-                       d_last_octave, d_last_angle, d_mp_desc, d_last_flags, d_last_n, last_cap, d_match, d_nmatches);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    return launch_matcher<search_by_projection_kernel>(n_pairs, proj_smem(cur_cap, last_cap), stream, *p, d_cur_kps,
+                                                       d_cur_desc, d_cur_n, cur_cap, d_cur_blocked, d_cur_uright,
+                                                       d_cell_off, d_cell_idx, d_x3dc, d_last_octave, d_last_angle,
+                                                       d_mp_desc, d_last_flags, d_last_n, last_cap, d_match,
+                                                       d_nmatches);
 }
 
 // One pair from host memory, synchronous (grid built on the device too).
@@ -1105,52 +758,28 @@ extern "C" int plvi_search_by_projection(const plvi_proj_params* p, const plvi_k
     if (!p || n_cur < 0 || n_last < 0 || (n_cur > 0 && (!cur_kps || !cur_desc || !match))) return PLVI_E_BADARG;
     if (n_cur == 0) return 0;
     const int cc = n_cur, lc = std::max(n_last, 1);
-    std::vector<size_t> off;
-    size_t tot = 0;
-    auto put = [&](size_t bytes) {
-        off.push_back(tot);
-        tot += (bytes + 255) & ~size_t(255);
-        return off.size() - 1;
-    };
-    const size_t oK = put(sizeof(plvi_keypoint) * cc), oD = put(32 * (size_t)cc), oB = put(cc), oU = put(4 * (size_t)cc);
-    const size_t oCO = put(4 * (size_t)(kGridCells + 1)), oCI = put(4 * (size_t)cc), oX = put(12 * (size_t)lc);
-    const size_t oLO = put(4 * (size_t)lc), oLA = put(4 * (size_t)lc), oMD = put(32 * (size_t)lc), oLF = put(lc);
-    const size_t oM = put(4 * (size_t)cc), oN = put(16);
-    DevBuf d;
-    if (d.alloc(tot)) return PLVI_E_HIP;
-    uint8_t* B = d.as<uint8_t>();
-    auto up = [&](size_t slot, const void* src, size_t bytes) -> int {
-        if (src && bytes) PLVI_CHECK(hipMemcpy(B + off[slot], src, bytes, hipMemcpyHostToDevice));
-        return PLVI_OK;
-    };
-    int rc = up(oK, cur_kps, sizeof(plvi_keypoint) * cc) | up(oD, cur_desc, 32 * (size_t)cc);
-    if (cur_blocked) rc |= up(oB, cur_blocked, cc);
-    else PLVI_CHECK(hipMemset(B + off[oB], 0, cc));
-    if (cur_uright) rc |= up(oU, cur_uright, 4 * (size_t)cc);
-    if (n_last > 0)
-        rc |= up(oX, x3dc, 12 * (size_t)n_last) | up(oLO, last_octave, 4 * (size_t)n_last) |
-              up(oLA, last_angle, 4 * (size_t)n_last) | up(oMD, mp_desc, 32 * (size_t)n_last) |
-              up(oLF, last_flags, n_last);
-    if (rc) return PLVI_E_HIP;
-    int counts[2] = {n_cur, n_last};
-    PLVI_CHECK(hipMemcpy(B + off[oN], counts, 8, hipMemcpyHostToDevice));
-    int* dN = reinterpret_cast<int*>(B + off[oN]);
-    plvi_grid_params gp{p->min_x, p->min_y, p->inv_w, p->inv_h};
-    rc = plvi_assign_grid_batch(reinterpret_cast<const plvi_keypoint*>(B + off[oK]), dN, cc, 1, &gp,
-                                reinterpret_cast<int*>(B + off[oCO]), reinterpret_cast<int*>(B + off[oCI]), nullptr);
-    if (rc) return rc;
-    rc = plvi_search_by_projection_batch(
-        1, p, reinterpret_cast<const plvi_keypoint*>(B + off[oK]), B + off[oD], dN, cc, B + off[oB],
-        cur_uright ? reinterpret_cast<const float*>(B + off[oU]) : nullptr, reinterpret_cast<const int*>(B + off[oCO]),
-        reinterpret_cast<const int*>(B + off[oCI]), reinterpret_cast<const float*>(B + off[oX]),
-        reinterpret_cast<const int*>(B + off[oLO]), reinterpret_cast<const float*>(B + off[oLA]), B + off[oMD],
-        B + off[oLF], dN + 1, lc, reinterpret_cast<int*>(B + off[oM]), dN + 2, nullptr);
-    if (rc) return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    int nm = 0;
-    PLVI_CHECK(hipMemcpy(match, B + off[oM], 4 * (size_t)n_cur, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(&nm, dN + 2, 4, hipMemcpyDeviceToHost));
-    return nm;
+    HostStage st;
+    const size_t oK = st.put(sizeof(plvi_keypoint) * cc), oD = st.put(32 * (size_t)cc), oB = st.put(cc);
+    const size_t oU = st.put(4 * (size_t)cc), oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)cc);
+    const size_t oX = st.put(12 * (size_t)lc), oLO = st.put(4 * (size_t)lc), oLA = st.put(4 * (size_t)lc);
+    const size_t oMD = st.put(32 * (size_t)lc), oLF = st.put(lc), oM = st.put(4 * (size_t)cc), oN = st.put(16);
+    if (st.alloc()) return PLVI_E_HIP;
+    const int counts[2] = {n_cur, n_last};
+    if (st.up(oK, cur_kps, sizeof(plvi_keypoint) * cc) | st.up(oD, cur_desc, 32 * (size_t)cc) |
+        st.up_or_zero(oB, cur_blocked, cc) | st.up(oU, cur_uright, 4 * (size_t)cc) |
+        st.up(oX, x3dc, 12 * (size_t)n_last) | st.up(oLO, last_octave, 4 * (size_t)n_last) |
+        st.up(oLA, last_angle, 4 * (size_t)n_last) | st.up(oMD, mp_desc, 32 * (size_t)n_last) |
+        st.up(oLF, last_flags, n_last) | st.up(oN, counts, sizeof counts))
+        return PLVI_E_HIP;
+    int* dN = st.at<int>(oN);
+    if (int rc = stage_grid(st, p, oK, dN, cc, oCO, oCI)) return rc;
+    if (int rc = plvi_search_by_projection_batch(
+            1, p, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, cc, st.at<uint8_t>(oB),
+            cur_uright ? st.at<float>(oU) : nullptr, st.at<int>(oCO), st.at<int>(oCI), st.at<float>(oX),
+            st.at<int>(oLO), st.at<float>(oLA), st.at<uint8_t>(oMD), st.at<uint8_t>(oLF), dN + 1, lc, st.at<int>(oM),
+            dN + 2, nullptr))
+        return rc;
+    return st.finish(dN + 2, match, oM, n_cur);
 }
 
 extern "C" int plvi_search_reloc_batch(int n_pairs, const plvi_reloc_params* p, const plvi_keypoint* d_cur_kps,
@@ -1162,15 +791,11 @@ extern "C" int plvi_search_reloc_batch(int n_pairs, const plvi_reloc_params* p, 
     if (!p || n_pairs < 0 || cur_cap < 1 || kf_cap < 1 || cur_cap > 65535 || kf_cap > 65535) return PLVI_E_BADARG;
     if (p->nlevels < 1 || p->nlevels > 16 || p->orb_dist < 0 || p->orb_dist > 255) return PLVI_E_BADARG;
     if (n_pairs == 0) return PLVI_OK;
-    const size_t smem = proj_smem(cur_cap, kf_cap);  // same carve-up as the frame-to-frame matcher
-    if (!lds_fits<search_reloc_kernel>(smem)) return PLVI_E_CAPACITY;
-    PLVI_CHECK(hipFuncSetAttribute((const void*)search_reloc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)smem));
-    hipLaunchKernelGGL(search_reloc_kernel, dim3(n_pairs), dim3(256), smem, (hipStream_t)stream, *p, d_cur_kps,
-                       d_cur_desc, d_cur_n, cur_cap, d_cur_blocked, d_cell_off, d_cell_idx, d_kf_flags, d_x3dc, d_dist,
-                       d_level, d_kf_angle, d_mp_desc, d_kf_n, kf_cap, d_match, d_nmatches);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    // same carve-up as the frame-to-frame matcher
+    return launch_matcher<search_reloc_kernel>(n_pairs, proj_smem(cur_cap, kf_cap), stream, *p, d_cur_kps, d_cur_desc,
+                                               d_cur_n, cur_cap, d_cur_blocked, d_cell_off, d_cell_idx, d_kf_flags,
+                                               d_x3dc, d_dist, d_level, d_kf_angle, d_mp_desc, d_kf_n, kf_cap, d_match,
+                                               d_nmatches);
 }
 
 // One pair from host memory, synchronous (grid built on the device).
@@ -1183,51 +808,28 @@ extern "C" int plvi_search_reloc(const plvi_reloc_params* p, const plvi_keypoint
     if (p->nlevels < 1 || p->nlevels > 16 || p->orb_dist < 0 || p->orb_dist > 255) return PLVI_E_BADARG;
     if (n_cur == 0) return 0;
     const int cc = n_cur, kc = std::max(n_kf, 1);
-    std::vector<size_t> off;
-    size_t tot = 0;
-    auto put = [&](size_t bytes) {
-        off.push_back(tot);
-        tot += (bytes + 255) & ~size_t(255);
-        return off.size() - 1;
-    };
-    const size_t oK = put(sizeof(plvi_keypoint) * cc), oD = put(32 * (size_t)cc), oB = put(cc);
-    const size_t oCO = put(4 * (size_t)(kGridCells + 1)), oCI = put(4 * (size_t)cc), oF = put(kc);
-    const size_t oX = put(12 * (size_t)kc), oS = put(12 * (size_t)kc), oL = put(4 * (size_t)kc);
-    const size_t oA = put(4 * (size_t)kc), oMD = put(32 * (size_t)kc), oM = put(4 * (size_t)cc), oN = put(16);
-    DevBuf d;
-    if (d.alloc(tot)) return PLVI_E_HIP;
-    uint8_t* B = d.as<uint8_t>();
-    auto up = [&](size_t slot, const void* src, size_t bytes) -> int {
-        if (src && bytes) PLVI_CHECK(hipMemcpy(B + off[slot], src, bytes, hipMemcpyHostToDevice));
-        return PLVI_OK;
-    };
-    int rc = up(oK, cur_kps, sizeof(plvi_keypoint) * cc) | up(oD, cur_desc, 32 * (size_t)cc);
-    if (cur_blocked) rc |= up(oB, cur_blocked, cc);
-    else PLVI_CHECK(hipMemset(B + off[oB], 0, cc));
-    if (n_kf > 0)
-        rc |= up(oF, kf_flags, n_kf) | up(oX, x3dc, 12 * (size_t)n_kf) | up(oS, dist, 12 * (size_t)n_kf) |
-              up(oL, level, 4 * (size_t)n_kf) | up(oA, kf_angle, 4 * (size_t)n_kf) |
-              up(oMD, mp_desc, 32 * (size_t)n_kf);
-    if (rc) return PLVI_E_HIP;
-    int counts[2] = {n_cur, n_kf};
-    PLVI_CHECK(hipMemcpy(B + off[oN], counts, 8, hipMemcpyHostToDevice));
-    int* dN = reinterpret_cast<int*>(B + off[oN]);
-    plvi_grid_params gp{p->min_x, p->min_y, p->inv_w, p->inv_h};
-    rc = plvi_assign_grid_batch(reinterpret_cast<const plvi_keypoint*>(B + off[oK]), dN, cc, 1, &gp,
-                                reinterpret_cast<int*>(B + off[oCO]), reinterpret_cast<int*>(B + off[oCI]), nullptr);
-    if (rc) return rc;
-    rc = plvi_search_reloc_batch(1, p, reinterpret_cast<const plvi_keypoint*>(B + off[oK]), B + off[oD], dN, cc,
-                                 B + off[oB], reinterpret_cast<const int*>(B + off[oCO]),
-                                 reinterpret_cast<const int*>(B + off[oCI]), B + off[oF],
-                                 reinterpret_cast<const float*>(B + off[oX]), reinterpret_cast<const float*>(B + off[oS]),
-                                 reinterpret_cast<const int*>(B + off[oL]), reinterpret_cast<const float*>(B + off[oA]),
-                                 B + off[oMD], dN + 1, kc, reinterpret_cast<int*>(B + off[oM]), dN + 2, nullptr);
-    if (rc) return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    int nm = 0;
-    PLVI_CHECK(hipMemcpy(match, B + off[oM], 4 * (size_t)n_cur, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(&nm, dN + 2, 4, hipMemcpyDeviceToHost));
-    return nm;
+    HostStage st;
+    const size_t oK = st.put(sizeof(plvi_keypoint) * cc), oD = st.put(32 * (size_t)cc), oB = st.put(cc);
+    const size_t oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)cc), oF = st.put(kc);
+    const size_t oX = st.put(12 * (size_t)kc), oS = st.put(12 * (size_t)kc), oL = st.put(4 * (size_t)kc);
+    const size_t oA = st.put(4 * (size_t)kc), oMD = st.put(32 * (size_t)kc), oM = st.put(4 * (size_t)cc);
+    const size_t oN = st.put(16);
+    if (st.alloc()) return PLVI_E_HIP;
+    const int counts[2] = {n_cur, n_kf};
+    if (st.up(oK, cur_kps, sizeof(plvi_keypoint) * cc) | st.up(oD, cur_desc, 32 * (size_t)cc) |
+        st.up_or_zero(oB, cur_blocked, cc) | st.up(oF, kf_flags, n_kf) | st.up(oX, x3dc, 12 * (size_t)n_kf) |
+        st.up(oS, dist, 12 * (size_t)n_kf) | st.up(oL, level, 4 * (size_t)n_kf) |
+        st.up(oA, kf_angle, 4 * (size_t)n_kf) | st.up(oMD, mp_desc, 32 * (size_t)n_kf) |
+        st.up(oN, counts, sizeof counts))
+        return PLVI_E_HIP;
+    int* dN = st.at<int>(oN);
+    if (int rc = stage_grid(st, p, oK, dN, cc, oCO, oCI)) return rc;
+    if (int rc = plvi_search_reloc_batch(1, p, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, cc,
+                                         st.at<uint8_t>(oB), st.at<int>(oCO), st.at<int>(oCI), st.at<uint8_t>(oF),
+                                         st.at<float>(oX), st.at<float>(oS), st.at<int>(oL), st.at<float>(oA),
+                                         st.at<uint8_t>(oMD), dN + 1, kc, st.at<int>(oM), dN + 2, nullptr))
+        return rc;
+    return st.finish(dN + 2, match, oM, n_cur);
 }
 
 extern "C" int plvi_search_local_batch(int n_frames, const plvi_local_params* p, const plvi_keypoint* d_kps,
@@ -1239,15 +841,9 @@ extern "C" int plvi_search_local_batch(int n_frames, const plvi_local_params* p,
     if (!p || n_frames < 0 || cap < 1 || mp_cap < 1 || cap > 65535) return PLVI_E_BADARG;
     if (p->nlevels < 1 || p->nlevels > 16) return PLVI_E_BADARG;
     if (n_frames == 0) return PLVI_OK;
-    const size_t smem = local_smem(cap, mp_cap);
-    if (!lds_fits<search_local_kernel>(smem)) return PLVI_E_CAPACITY;
-    PLVI_CHECK(hipFuncSetAttribute((const void*)search_local_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)smem));
-    hipLaunchKernelGGL(search_local_kernel, dim3(n_frames), dim3(256), smem, (hipStream_t)stream, *p, d_kps, d_desc,
-                       d_n, cap, d_blocked, d_uright, d_cell_off, d_cell_idx, d_mp_flags, d_mp_proj, d_mp_level,
-                       d_mp_desc, d_mp_n, mp_cap, d_match, d_nmatches);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    return launch_matcher<search_local_kernel>(n_frames, local_smem(cap, mp_cap), stream, *p, d_kps, d_desc, d_n, cap,
+                                               d_blocked, d_uright, d_cell_off, d_cell_idx, d_mp_flags, d_mp_proj,
+                                               d_mp_level, d_mp_desc, d_mp_n, mp_cap, d_match, d_nmatches);
 }
 
 // One frame from host memory, synchronous (grid built on the device).
@@ -1258,51 +854,26 @@ extern "C" int plvi_search_local(const plvi_local_params* p, const plvi_keypoint
     if (!p || n < 0 || n_mp < 0 || (n > 0 && (!kps || !desc || !match))) return PLVI_E_BADARG;
     if (n == 0) return 0;
     const int cc = n, mc = std::max(n_mp, 1);
-    std::vector<size_t> off;
-    size_t tot = 0;
-    auto put = [&](size_t bytes) {
-        off.push_back(tot);
-        tot += (bytes + 255) & ~size_t(255);
-        return off.size() - 1;
-    };
-    const size_t oK = put(sizeof(plvi_keypoint) * cc), oD = put(32 * (size_t)cc), oB = put(cc), oU = put(4 * (size_t)cc);
-    const size_t oCO = put(4 * (size_t)(kGridCells + 1)), oCI = put(4 * (size_t)cc), oF = put(mc);
-    const size_t oP = put(16 * (size_t)mc), oL = put(4 * (size_t)mc), oMD = put(32 * (size_t)mc);
-    const size_t oM = put(4 * (size_t)cc), oN = put(16);
-    DevBuf d;
-    if (d.alloc(tot)) return PLVI_E_HIP;
-    uint8_t* B = d.as<uint8_t>();
-    auto up = [&](size_t slot, const void* src, size_t bytes) -> int {
-        if (src && bytes) PLVI_CHECK(hipMemcpy(B + off[slot], src, bytes, hipMemcpyHostToDevice));
-        return PLVI_OK;
-    };
-    int rc = up(oK, kps, sizeof(plvi_keypoint) * cc) | up(oD, desc, 32 * (size_t)cc);
-    if (blocked) rc |= up(oB, blocked, cc);
-    else PLVI_CHECK(hipMemset(B + off[oB], 0, cc));
-    if (uright) rc |= up(oU, uright, 4 * (size_t)cc);
-    if (n_mp > 0)
-        rc |= up(oF, mp_flags, n_mp) | up(oP, mp_proj, 16 * (size_t)n_mp) | up(oL, mp_level, 4 * (size_t)n_mp) |
-              up(oMD, mp_desc, 32 * (size_t)n_mp);
-    if (rc) return PLVI_E_HIP;
-    int counts[2] = {n, n_mp};
-    PLVI_CHECK(hipMemcpy(B + off[oN], counts, 8, hipMemcpyHostToDevice));
-    int* dN = reinterpret_cast<int*>(B + off[oN]);
-    plvi_grid_params gp{p->min_x, p->min_y, p->inv_w, p->inv_h};
-    rc = plvi_assign_grid_batch(reinterpret_cast<const plvi_keypoint*>(B + off[oK]), dN, cc, 1, &gp,
-                                reinterpret_cast<int*>(B + off[oCO]), reinterpret_cast<int*>(B + off[oCI]), nullptr);
-    if (rc) return rc;
-    rc = plvi_search_local_batch(1, p, reinterpret_cast<const plvi_keypoint*>(B + off[oK]), B + off[oD], dN, cc,
-                                 B + off[oB], uright ? reinterpret_cast<const float*>(B + off[oU]) : nullptr,
-                                 reinterpret_cast<const int*>(B + off[oCO]), reinterpret_cast<const int*>(B + off[oCI]),
-                                 B + off[oF], reinterpret_cast<const float*>(B + off[oP]),
-                                 reinterpret_cast<const int*>(B + off[oL]), B + off[oMD], dN + 1, mc,
-                                 reinterpret_cast<int*>(B + off[oM]), dN + 2, nullptr);
-    if (rc) return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    int nmt = 0;
-    PLVI_CHECK(hipMemcpy(match, B + off[oM], 4 * (size_t)n, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(&nmt, dN + 2, 4, hipMemcpyDeviceToHost));
-    return nmt;
+    HostStage st;
+    const size_t oK = st.put(sizeof(plvi_keypoint) * cc), oD = st.put(32 * (size_t)cc), oB = st.put(cc);
+    const size_t oU = st.put(4 * (size_t)cc), oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)cc);
+    const size_t oF = st.put(mc), oP = st.put(16 * (size_t)mc), oL = st.put(4 * (size_t)mc);
+    const size_t oMD = st.put(32 * (size_t)mc), oM = st.put(4 * (size_t)cc), oN = st.put(16);
+    if (st.alloc()) return PLVI_E_HIP;
+    const int counts[2] = {n, n_mp};
+    if (st.up(oK, kps, sizeof(plvi_keypoint) * cc) | st.up(oD, desc, 32 * (size_t)cc) |
+        st.up_or_zero(oB, blocked, cc) | st.up(oU, uright, 4 * (size_t)cc) | st.up(oF, mp_flags, n_mp) |
+        st.up(oP, mp_proj, 16 * (size_t)n_mp) | st.up(oL, mp_level, 4 * (size_t)n_mp) |
+        st.up(oMD, mp_desc, 32 * (size_t)n_mp) | st.up(oN, counts, sizeof counts))
+        return PLVI_E_HIP;
+    int* dN = st.at<int>(oN);
+    if (int rc = stage_grid(st, p, oK, dN, cc, oCO, oCI)) return rc;
+    if (int rc = plvi_search_local_batch(1, p, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, cc,
+                                         st.at<uint8_t>(oB), uright ? st.at<float>(oU) : nullptr, st.at<int>(oCO),
+                                         st.at<int>(oCI), st.at<uint8_t>(oF), st.at<float>(oP), st.at<int>(oL),
+                                         st.at<uint8_t>(oMD), dN + 1, mc, st.at<int>(oM), dN + 2, nullptr))
+        return rc;
+    return st.finish(dN + 2, match, oM, n);
 }
 
 extern "C" int plvi_search_local_stereo_batch(
@@ -1317,16 +888,11 @@ extern "C" int plvi_search_local_stereo_batch(
         return PLVI_E_BADARG;
     if (p->nlevels < 1 || p->nlevels > 16) return PLVI_E_BADARG;
     if (n_frames == 0) return PLVI_OK;
-    const size_t smem = local2_smem(cap, cap_r, mp_cap);
-    if (!lds_fits<search_local2_kernel>(smem)) return PLVI_E_CAPACITY;
-    PLVI_CHECK(hipFuncSetAttribute((const void*)search_local2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)smem));
-    hipLaunchKernelGGL(search_local2_kernel, dim3(n_frames), dim3(256), smem, (hipStream_t)stream, *p, d_kps, d_desc,
-                       d_n, cap, d_blocked, d_l2r, d_cell_off, d_cell_idx, d_kps_r, d_desc_r, d_n_r, cap_r,
-                       d_blocked_r, d_r2l, d_cell_off_r, d_cell_idx_r, d_mp_flags, d_mp_proj, d_mp_level, d_mp_proj_r,
-                       d_mp_level_r, d_mp_desc, d_mp_n, mp_cap, d_match, d_match_r, d_nmatches);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    return launch_matcher<search_local2_kernel>(n_frames, local2_smem(cap, cap_r, mp_cap), stream, *p, d_kps, d_desc,
+                                                d_n, cap, d_blocked, d_l2r, d_cell_off, d_cell_idx, d_kps_r, d_desc_r,
+                                                d_n_r, cap_r, d_blocked_r, d_r2l, d_cell_off_r, d_cell_idx_r,
+                                                d_mp_flags, d_mp_proj, d_mp_level, d_mp_proj_r, d_mp_level_r, d_mp_desc,
+                                                d_mp_n, mp_cap, d_match, d_match_r, d_nmatches);
 }
 
 // One two-camera frame from host memory, synchronous (both grids built on the device).
@@ -1342,63 +908,38 @@ extern "C" int plvi_search_local_stereo(const plvi_local_params* p, const plvi_k
         return PLVI_E_BADARG;
     if (n + n_r == 0) return 0;
     const int cl = std::max(n, 1), cr = std::max(n_r, 1), mc = std::max(n_mp, 1);
-    std::vector<size_t> off;
-    size_t tot = 0;
-    auto put = [&](size_t bytes) {
-        off.push_back(tot);
-        tot += (bytes + 255) & ~size_t(255);
-        return off.size() - 1;
-    };
-    const size_t oK = put(sizeof(plvi_keypoint) * cl), oD = put(32 * (size_t)cl), oB = put(cl), oP2 = put(4 * (size_t)cl);
-    const size_t oCO = put(4 * (size_t)(kGridCells + 1)), oCI = put(4 * (size_t)cl), oM = put(4 * (size_t)cl);
-    const size_t rK = put(sizeof(plvi_keypoint) * cr), rD = put(32 * (size_t)cr), rB = put(cr), rP2 = put(4 * (size_t)cr);
-    const size_t rCO = put(4 * (size_t)(kGridCells + 1)), rCI = put(4 * (size_t)cr), rM = put(4 * (size_t)cr);
-    const size_t oF = put(mc), oP = put(16 * (size_t)mc), oL = put(4 * (size_t)mc), oPR = put(16 * (size_t)mc),
-                 oLR = put(4 * (size_t)mc), oMD = put(32 * (size_t)mc), oN = put(16);
-    DevBuf d;
-    if (d.alloc(tot)) return PLVI_E_HIP;
-    uint8_t* B = d.as<uint8_t>();
-    PLVI_CHECK(hipMemset(B, 0, tot));
-    auto up = [&](size_t slot, const void* src, size_t bytes) -> int {
-        if (src && bytes) PLVI_CHECK(hipMemcpy(B + off[slot], src, bytes, hipMemcpyHostToDevice));
-        return PLVI_OK;
-    };
-    int rc = up(oK, kps, sizeof(plvi_keypoint) * n) | up(oD, desc, 32 * (size_t)n) | up(oB, blocked, n) |
-             up(rK, kps_r, sizeof(plvi_keypoint) * n_r) | up(rD, desc_r, 32 * (size_t)n_r) | up(rB, blocked_r, n_r);
-    // no stereo pairs = every entry -1
-    std::vector<int> none(std::max(n, n_r), -1);
-    rc |= up(oP2, l2r ? l2r : none.data(), 4 * (size_t)n) | up(rP2, r2l ? r2l : none.data(), 4 * (size_t)n_r);
-    if (n_mp > 0)
-        rc |= up(oF, mp_flags, n_mp) | up(oP, mp_proj, 16 * (size_t)n_mp) | up(oL, mp_level, 4 * (size_t)n_mp) |
-              up(oPR, mp_proj_r, 16 * (size_t)n_mp) | up(oLR, mp_level_r, 4 * (size_t)n_mp) |
-              up(oMD, mp_desc, 32 * (size_t)n_mp);
-    if (rc) return PLVI_E_HIP;
-    int counts[4] = {n, n_r, n_mp, 0};
-    PLVI_CHECK(hipMemcpy(B + off[oN], counts, 16, hipMemcpyHostToDevice));
-    int* dN = reinterpret_cast<int*>(B + off[oN]);
-    plvi_grid_params gp{p->min_x, p->min_y, p->inv_w, p->inv_h};
-    rc = plvi_assign_grid_batch(reinterpret_cast<const plvi_keypoint*>(B + off[oK]), dN, cl, 1, &gp,
-                                reinterpret_cast<int*>(B + off[oCO]), reinterpret_cast<int*>(B + off[oCI]), nullptr);
-    if (rc) return rc;
-    rc = plvi_assign_grid_batch(reinterpret_cast<const plvi_keypoint*>(B + off[rK]), dN + 1, cr, 1, &gp,
-                                reinterpret_cast<int*>(B + off[rCO]), reinterpret_cast<int*>(B + off[rCI]), nullptr);
-    if (rc) return rc;
-    rc = plvi_search_local_stereo_batch(
-        1, p, reinterpret_cast<const plvi_keypoint*>(B + off[oK]), B + off[oD], dN, cl, B + off[oB],
-        reinterpret_cast<const int*>(B + off[oP2]), reinterpret_cast<const int*>(B + off[oCO]),
-        reinterpret_cast<const int*>(B + off[oCI]), reinterpret_cast<const plvi_keypoint*>(B + off[rK]), B + off[rD],
-        dN + 1, cr, B + off[rB], reinterpret_cast<const int*>(B + off[rP2]), reinterpret_cast<const int*>(B + off[rCO]),
-        reinterpret_cast<const int*>(B + off[rCI]), B + off[oF], reinterpret_cast<const float*>(B + off[oP]),
-        reinterpret_cast<const int*>(B + off[oL]), reinterpret_cast<const float*>(B + off[oPR]),
-        reinterpret_cast<const int*>(B + off[oLR]), B + off[oMD], dN + 2, mc, reinterpret_cast<int*>(B + off[oM]),
-        reinterpret_cast<int*>(B + off[rM]), dN + 3, nullptr);
-    if (rc) return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    int nmt = 0;
-    if (n) PLVI_CHECK(hipMemcpy(match, B + off[oM], 4 * (size_t)n, hipMemcpyDeviceToHost));
-    if (n_r) PLVI_CHECK(hipMemcpy(match_r, B + off[rM], 4 * (size_t)n_r, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(&nmt, dN + 3, 4, hipMemcpyDeviceToHost));
-    return nmt;
+    HostStage st;
+    const size_t oK = st.put(sizeof(plvi_keypoint) * cl), oD = st.put(32 * (size_t)cl), oB = st.put(cl);
+    const size_t oP2 = st.put(4 * (size_t)cl), oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)cl);
+    const size_t oM = st.put(4 * (size_t)cl);
+    const size_t rK = st.put(sizeof(plvi_keypoint) * cr), rD = st.put(32 * (size_t)cr), rB = st.put(cr);
+    const size_t rP2 = st.put(4 * (size_t)cr), rCO = st.put(4 * (size_t)(kGridCells + 1)), rCI = st.put(4 * (size_t)cr);
+    const size_t rM = st.put(4 * (size_t)cr);
+    const size_t oF = st.put(mc), oP = st.put(16 * (size_t)mc), oL = st.put(4 * (size_t)mc);
+    const size_t oPR = st.put(16 * (size_t)mc), oLR = st.put(4 * (size_t)mc), oMD = st.put(32 * (size_t)mc);
+    const size_t oN = st.put(16);
+    if (int rc = st.alloc(true)) return rc;
+    const std::vector<int> none(std::max(n, n_r), -1);  // no stereo pairs = every entry -1
+    const int counts[4] = {n, n_r, n_mp, 0};
+    if (st.up(oK, kps, sizeof(plvi_keypoint) * n) | st.up(oD, desc, 32 * (size_t)n) | st.up(oB, blocked, n) |
+        st.up(rK, kps_r, sizeof(plvi_keypoint) * n_r) | st.up(rD, desc_r, 32 * (size_t)n_r) |
+        st.up(rB, blocked_r, n_r) | st.up(oP2, l2r ? l2r : none.data(), 4 * (size_t)n) |
+        st.up(rP2, r2l ? r2l : none.data(), 4 * (size_t)n_r) | st.up(oF, mp_flags, n_mp) |
+        st.up(oP, mp_proj, 16 * (size_t)n_mp) | st.up(oL, mp_level, 4 * (size_t)n_mp) |
+        st.up(oPR, mp_proj_r, 16 * (size_t)n_mp) | st.up(oLR, mp_level_r, 4 * (size_t)n_mp) |
+        st.up(oMD, mp_desc, 32 * (size_t)n_mp) | st.up(oN, counts, sizeof counts))
+        return PLVI_E_HIP;
+    int* dN = st.at<int>(oN);
+    if (int rc = stage_grid(st, p, oK, dN, cl, oCO, oCI)) return rc;
+    if (int rc = stage_grid(st, p, rK, dN + 1, cr, rCO, rCI)) return rc;
+    if (int rc = plvi_search_local_stereo_batch(
+            1, p, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, cl, st.at<uint8_t>(oB), st.at<int>(oP2),
+            st.at<int>(oCO), st.at<int>(oCI), st.at<plvi_keypoint>(rK), st.at<uint8_t>(rD), dN + 1, cr,
+            st.at<uint8_t>(rB), st.at<int>(rP2), st.at<int>(rCO), st.at<int>(rCI), st.at<uint8_t>(oF),
+            st.at<float>(oP), st.at<int>(oL), st.at<float>(oPR), st.at<int>(oLR), st.at<uint8_t>(oMD), dN + 2, mc,
+            st.at<int>(oM), st.at<int>(rM), dN + 3, nullptr))
+        return rc;
+    return st.finish(dN + 3, match, oM, n, match_r, rM, n_r);
 }
 
 extern "C" int plvi_search_by_projection_stereo_batch(
@@ -1413,18 +954,14 @@ extern "C" int plvi_search_by_projection_stereo_batch(
         return PLVI_E_BADARG;
     if (p->nlevels < 1 || p->nlevels > 16) return PLVI_E_BADARG;
     if (n_pairs == 0) return PLVI_OK;
-    const size_t smem = proj2_smem(cap, cap_r, last_cap);
-    if (!lds_fits<search_by_projection2_kernel>(smem)) return PLVI_E_CAPACITY;
     CamModel cm{0, 0.f, 0.f, 0.f, 0.f};
     if (kb8) cm = CamModel{1, kb8[0], kb8[1], kb8[2], kb8[3]};
-    PLVI_CHECK(hipFuncSetAttribute((const void*)search_by_projection2_kernel,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(search_by_projection2_kernel, dim3(n_pairs), dim3(256), smem, (hipStream_t)stream, *p, cm, d_kps,
-                       d_desc, d_n, cap, d_blocked, d_cell_off, d_cell_idx, d_kps_r, d_desc_r, d_n_r, cap_r,
-                       d_blocked_r, d_cell_off_r, d_cell_idx_r, d_x3dc, d_x3dr, d_last_octave, d_last_angle, d_mp_desc,
-                       d_last_flags, d_last_n, last_cap, d_match, d_match_r, d_nmatches);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    return launch_matcher<search_by_projection2_kernel>(n_pairs, proj2_smem(cap, cap_r, last_cap), stream, *p, cm,
+                                                        d_kps, d_desc, d_n, cap, d_blocked, d_cell_off, d_cell_idx,
+                                                        d_kps_r, d_desc_r, d_n_r, cap_r, d_blocked_r, d_cell_off_r,
+                                                        d_cell_idx_r, d_x3dc, d_x3dr, d_last_octave, d_last_angle,
+                                                        d_mp_desc, d_last_flags, d_last_n, last_cap, d_match, d_match_r,
+                                                        d_nmatches);
 }
 
 // One pair from host memory, synchronous (both grids built on the device).
@@ -1439,57 +976,29 @@ extern "C" int plvi_search_by_projection_stereo(const plvi_proj_params* p, const
     if ((n > 0 && (!kps || !desc || !match)) || (n_r > 0 && (!kps_r || !desc_r || !match_r))) return PLVI_E_BADARG;
     if (n_last > 0 && (!x3dc || !x3dr || !last_octave || !last_angle || !mp_desc || !last_flags)) return PLVI_E_BADARG;
     const int cl = std::max(n, 1), cr = std::max(n_r, 1), lc = std::max(n_last, 1);
-    std::vector<size_t> off;
-    size_t tot = 0;
-    auto put = [&](size_t bytes) {
-        off.push_back(tot);
-        tot += (bytes + 255) & ~size_t(255);
-        return off.size() - 1;
-    };
-    const size_t oK = put(sizeof(plvi_keypoint) * cl), oD = put(32 * (size_t)cl), oB = put(cl);
-    const size_t oCO = put(4 * (size_t)(kGridCells + 1)), oCI = put(4 * (size_t)cl), oM = put(4 * (size_t)cl);
-    const size_t rK = put(sizeof(plvi_keypoint) * cr), rD = put(32 * (size_t)cr), rB = put(cr);
-    const size_t rCO = put(4 * (size_t)(kGridCells + 1)), rCI = put(4 * (size_t)cr), rM = put(4 * (size_t)cr);
-    const size_t oX = put(12 * (size_t)lc), oXR = put(12 * (size_t)lc), oO = put(4 * (size_t)lc),
-                 oA = put(4 * (size_t)lc), oMD = put(32 * (size_t)lc), oF = put(lc), oN = put(16);
-    DevBuf d;
-    if (d.alloc(tot)) return PLVI_E_HIP;
-    uint8_t* B = d.as<uint8_t>();
-    PLVI_CHECK(hipMemset(B, 0, tot));
-    auto up = [&](size_t slot, const void* src, size_t bytes) -> int {
-        if (src && bytes) PLVI_CHECK(hipMemcpy(B + off[slot], src, bytes, hipMemcpyHostToDevice));
-        return PLVI_OK;
-    };
-    int rc = up(oK, kps, sizeof(plvi_keypoint) * n) | up(oD, desc, 32 * (size_t)n) | up(oB, blocked, n) |
-             up(rK, kps_r, sizeof(plvi_keypoint) * n_r) | up(rD, desc_r, 32 * (size_t)n_r) | up(rB, blocked_r, n_r) |
-             up(oX, x3dc, 12 * (size_t)n_last) | up(oXR, x3dr, 12 * (size_t)n_last) |
-             up(oO, last_octave, 4 * (size_t)n_last) | up(oA, last_angle, 4 * (size_t)n_last) |
-             up(oMD, mp_desc, 32 * (size_t)n_last) | up(oF, last_flags, n_last);
-    if (rc) return PLVI_E_HIP;
-    int counts[4] = {n, n_r, n_last, 0};
-    PLVI_CHECK(hipMemcpy(B + off[oN], counts, 16, hipMemcpyHostToDevice));
-    int* dN = reinterpret_cast<int*>(B + off[oN]);
-    plvi_grid_params gp{p->min_x, p->min_y, p->inv_w, p->inv_h};
-    rc = plvi_assign_grid_batch(reinterpret_cast<const plvi_keypoint*>(B + off[oK]), dN, cl, 1, &gp,
-                                reinterpret_cast<int*>(B + off[oCO]), reinterpret_cast<int*>(B + off[oCI]), nullptr);
-    if (rc) return rc;
-    rc = plvi_assign_grid_batch(reinterpret_cast<const plvi_keypoint*>(B + off[rK]), dN + 1, cr, 1, &gp,
-                                reinterpret_cast<int*>(B + off[rCO]), reinterpret_cast<int*>(B + off[rCI]), nullptr);
-    if (rc) return rc;
-    rc = plvi_search_by_projection_stereo_batch(
-        1, p, kb8, reinterpret_cast<const plvi_keypoint*>(B + off[oK]), B + off[oD], dN, cl, B + off[oB],
-        reinterpret_cast<const int*>(B + off[oCO]), reinterpret_cast<const int*>(B + off[oCI]),
-        reinterpret_cast<const plvi_keypoint*>(B + off[rK]), B + off[rD], dN + 1, cr, B + off[rB],
-        reinterpret_cast<const int*>(B + off[rCO]), reinterpret_cast<const int*>(B + off[rCI]),
-        reinterpret_cast<const float*>(B + off[oX]), reinterpret_cast<const float*>(B + off[oXR]),
-        reinterpret_cast<const int*>(B + off[oO]), reinterpret_cast<const float*>(B + off[oA]), B + off[oMD],
-        B + off[oF], dN + 2, lc, reinterpret_cast<int*>(B + off[oM]), reinterpret_cast<int*>(B + off[rM]), dN + 3,
-        nullptr);
-    if (rc) return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    int nmt = 0;
-    if (n) PLVI_CHECK(hipMemcpy(match, B + off[oM], 4 * (size_t)n, hipMemcpyDeviceToHost));
-    if (n_r) PLVI_CHECK(hipMemcpy(match_r, B + off[rM], 4 * (size_t)n_r, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(&nmt, dN + 3, 4, hipMemcpyDeviceToHost));
-    return nmt;
+    HostStage st;
+    const size_t oK = st.put(sizeof(plvi_keypoint) * cl), oD = st.put(32 * (size_t)cl), oB = st.put(cl);
+    const size_t oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)cl), oM = st.put(4 * (size_t)cl);
+    const size_t rK = st.put(sizeof(plvi_keypoint) * cr), rD = st.put(32 * (size_t)cr), rB = st.put(cr);
+    const size_t rCO = st.put(4 * (size_t)(kGridCells + 1)), rCI = st.put(4 * (size_t)cr), rM = st.put(4 * (size_t)cr);
+    const size_t oX = st.put(12 * (size_t)lc), oXR = st.put(12 * (size_t)lc), oO = st.put(4 * (size_t)lc);
+    const size_t oA = st.put(4 * (size_t)lc), oMD = st.put(32 * (size_t)lc), oF = st.put(lc), oN = st.put(16);
+    if (int rc = st.alloc(true)) return rc;
+    const int counts[4] = {n, n_r, n_last, 0};
+    if (st.up(oK, kps, sizeof(plvi_keypoint) * n) | st.up(oD, desc, 32 * (size_t)n) | st.up(oB, blocked, n) |
+        st.up(rK, kps_r, sizeof(plvi_keypoint) * n_r) | st.up(rD, desc_r, 32 * (size_t)n_r) |
+        st.up(rB, blocked_r, n_r) | st.up(oX, x3dc, 12 * (size_t)n_last) | st.up(oXR, x3dr, 12 * (size_t)n_last) |
+        st.up(oO, last_octave, 4 * (size_t)n_last) | st.up(oA, last_angle, 4 * (size_t)n_last) |
+        st.up(oMD, mp_desc, 32 * (size_t)n_last) | st.up(oF, last_flags, n_last) | st.up(oN, counts, sizeof counts))
+        return PLVI_E_HIP;
+    int* dN = st.at<int>(oN);
+    if (int rc = stage_grid(st, p, oK, dN, cl, oCO, oCI)) return rc;
+    if (int rc = stage_grid(st, p, rK, dN + 1, cr, rCO, rCI)) return rc;
+    if (int rc = plvi_search_by_projection_stereo_batch(
+            1, p, kb8, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, cl, st.at<uint8_t>(oB), st.at<int>(oCO),
+            st.at<int>(oCI), st.at<plvi_keypoint>(rK), st.at<uint8_t>(rD), dN + 1, cr, st.at<uint8_t>(rB),
+            st.at<int>(rCO), st.at<int>(rCI), st.at<float>(oX), st.at<float>(oXR), st.at<int>(oO), st.at<float>(oA),
+            st.at<uint8_t>(oMD), st.at<uint8_t>(oF), dN + 2, lc, st.at<int>(oM), st.at<int>(rM), dN + 3, nullptr))
+        return rc;
+    return st.finish(dN + 3, match, oM, n, match_r, rM, n_r);
 }
