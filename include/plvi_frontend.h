@@ -282,7 +282,17 @@ int plvi_lines_kernel_timing_read_kind(plvi_line_extractor* h, int kind, float* 
  * and distance, idx1/d1 = second.  Missing entries are -1 / INT32_MAX.
  * Batched over n_pairs independent (query,train) pairs; all pointers device.
  * q: [n_pairs][nq_cap][32], t: [n_pairs][nt_cap][32]; nq/nt: per-pair counts
- * (device int arrays).  Outputs [n_pairs][nq_cap]. */
+ * (device int arrays).  Outputs [n_pairs][nq_cap].
+ *
+ * The count contract, common to every batched entry point of this header
+ * that takes a device count array next to a table capacity (per pair or
+ * per frame; keypoint, line, MapPoint and FeatureVector node counts alike):
+ *   1. a count outside [0, cap] is read as clamped to that range;
+ *   2. input rows at or past the clamped count are never read;
+ *   3. output rows at or past it are never written (the per-pair result
+ *      counts are always written).
+ * Tables may therefore carry anything in their padding rows, and outputs may
+ * be packed with stride cap without clearing them first. */
 int plvi_hamming_knn2_batch(const uint8_t* d_q, const int* d_nq, int nq_cap, const uint8_t* d_t, const int* d_nt,
                             int nt_cap, int n_pairs, int* d_idx0, int* d_d0, int* d_idx1, int* d_d1, void* stream);
 
@@ -315,7 +325,8 @@ int plvi_line_match_inout(const uint8_t* desc1, int n1, const uint8_t* desc2, in
  * desc1[p] (n1[p] rows, stride cap1) against desc2[p] (n2[p] rows, stride
  * cap2).  d_scratch must hold 4*n_pairs*(cap1+cap2) ints.  Outputs
  * matches_12 [n_pairs][cap1] and per-pair match counts.  Pairs with fewer
- * than 2 rows on the train side produce no matches. */
+ * than 2 rows on the train side produce no matches.  n1 / n2 follow the
+ * count contract (plvi_hamming_knn2_batch). */
 int plvi_line_match_batch(const uint8_t* d_desc1, const int* d_n1, int cap1, const uint8_t* d_desc2, const int* d_n2,
                           int cap2, int n_pairs, float nnr, int* d_scratch, int* d_matches_12, int* d_nmatch,
                           void* stream);
@@ -345,8 +356,10 @@ int plvi_search_by_bow(float nnratio, int check_orientation, const uint8_t* kf_d
 /* Batched device variant: pair p uses rows p*kf_cap / p*f_cap of the
  * keypoint arrays, p*node_cap (node ids) and p*(node_cap+1) (offsets) of
  * the CSR arrays, counts kf_nnodes[p], f_nnodes[p], f_n[p].  Outputs
- * match_kf [n_pairs][f_cap], nmatches [n_pairs].  Needs
- * 4*f_cap + 8*node_cap <= 65536 bytes of LDS. */
+ * match_kf [n_pairs][f_cap], nmatches [n_pairs].  f_n follows the count
+ * contract (plvi_hamming_knn2_batch) against f_cap, both node counts against
+ * node_cap.  Needs 4*f_cap + 8*node_cap <= 65536 bytes of LDS (an odd f_cap
+ * is rounded up to even inside, which this bound already covers). */
 int plvi_search_by_bow_batch(int n_pairs, float nnratio, int check_orientation, int kf_cap, int f_cap, int node_cap,
                              const uint8_t* d_kf_desc, const float* d_kf_angle, const uint8_t* d_kf_live,
                              const int* d_kf_node, const int* d_kf_off, const int* d_kf_nnodes, const int* d_kf_idx,
@@ -396,7 +409,8 @@ int plvi_line_match_grid(const int* lines1, const uint8_t* desc1, int n1, int gr
 
 /* Batched device variant: pair p uses lines1 + p*cap1*4, desc1 + p*cap1*32,
  * cell_off + p*(ncell+1), cell_idx + p*idx_cap, desc2 + p*cap2*32,
- * directions2 + p*cap2*2, counts n1[p], n2[p].  Outputs matches_12
+ * directions2 + p*cap2*2, counts n1[p], n2[p] (count contract of
+ * plvi_hamming_knn2_batch; cap1, cap2 <= 2048).  Outputs matches_12
  * [n_pairs][cap1], nmatches [n_pairs]; *d_err |= 1 when a candidate set
  * exceeds 1024 lines (d_err may be NULL: no report). */
 int plvi_line_match_grid_batch(int n_pairs, const int* d_lines1, const uint8_t* d_desc1, const int* d_n1, int cap1,
@@ -435,7 +449,10 @@ int plvi_line_search_projection_batch(int n_pairs, const plvi_line_proj_params* 
                                       const uint8_t* d_ml_desc, const int* d_last_n, int last_cap, int* d_match,
                                       int* d_nmatches, int* d_err, void* stream);
 /* d_err (may be NULL): |= 1 when a candidate set overflows, |= 2 when a last-frame
- * octave is outside [0, nlevels) (that line is skipped). */
+ * octave is outside [0, nlevels) (that line is skipped).  Pair p uses rows
+ * p*cur_cap / p*last_cap (x3dc: p*last_cap*6), cell_off + p*(ncell+1) and
+ * cell_idx + p*idx_cap; cur_n / last_n follow the count contract
+ * (plvi_hamming_knn2_batch), match rows [0, cur_n) are fully written. */
 /* One pair from host memory, synchronous (n_cur <= 2048).  Returns the
  * count or an error (PLVI_E_CAPACITY when a candidate set exceeds 1024). */
 int plvi_line_search_projection(const plvi_line_proj_params* p, const float* cur_angle, const uint8_t* cur_desc,
@@ -487,7 +504,10 @@ int plvi_vocab_transform_features(plvi_vocabulary* h, const uint8_t* desc, int n
 /* Batched device variant over n_frames descriptor tables [n_frames][cap][32]
  * with counts d_count (e.g. plvi_orb_outputs): outputs [n_frames][cap]
  * (fv_off [n_frames][cap+1]) and per-frame counts.  d_feat_word/d_feat_nid
- * (nullable) receive the per-descriptor descent.  Asynchronous. */
+ * (nullable) receive the per-descriptor descent.  d_count follows the count
+ * contract (plvi_hamming_knn2_batch) with one addition: a count above cap is
+ * not clamped silently, it also sets bit 0 of the handle's internal error
+ * word (the synchronous wrappers then return PLVI_E_OVERFLOW).  Asynchronous. */
 int plvi_vocab_transform_batch(plvi_vocabulary* h, const uint8_t* d_desc, const int* d_count, int cap, int n_frames,
                                int levelsup, unsigned* d_bow_word, double* d_bow_value, int* d_bow_n,
                                unsigned* d_fv_node, int* d_fv_off, unsigned* d_fv_idx, int* d_fv_n,
@@ -532,7 +552,9 @@ typedef struct plvi_grid_params {
 /* AssignFeaturesToGrid of n_frames keypoint tables [n_frames][cap]
  * (mvKeysUn; counts d_count) as CSR: cell (ix, iy) = ix*48 + iy lists its
  * keypoints at d_cell_idx[f*cap + d_cell_off[f*3073 + cell] ...] in index
- * order (= mGrid[ix][iy]).  cap <= 8192.  Asynchronous. */
+ * order (= mGrid[ix][iy]).  cap <= 8192.  d_count follows the count contract
+ * (plvi_hamming_knn2_batch); d_cell_off is written whole for every frame,
+ * d_cell_idx up to the frame's in-grid count.  Asynchronous. */
 int plvi_assign_grid_batch(const plvi_keypoint* d_kps, const int* d_count, int cap, int n_frames,
                            const plvi_grid_params* gp, int* d_cell_off, int* d_cell_idx, void* stream);
 
@@ -560,7 +582,8 @@ typedef struct plvi_proj_params {
  * mvpMapPoints[i2] holds on return, -2 = set to NULL by the rotation filter,
  * -1 = untouched; nmatches [p] = the return value.  cur_cap, last_cap <= 65535
  * and the LDS footprint (~19 B per current + 8 B per last keypoint + 12 KB)
- * <= 160 KB. */
+ * <= 160 KB.  d_cur_n / d_last_n follow the count contract
+ * (plvi_hamming_knn2_batch). */
 int plvi_search_by_projection_batch(int n_pairs, const plvi_proj_params* p, const plvi_keypoint* d_cur_kps,
                                     const uint8_t* d_cur_desc, const int* d_cur_n, int cur_cap,
                                     const uint8_t* d_cur_blocked, const float* d_cur_uright, const int* d_cell_off,
@@ -591,7 +614,8 @@ int plvi_search_by_projection(const plvi_proj_params* p, const plvi_keypoint* cu
  * filter, which sees both images' matches in one histogram), nmatches [p].
  * A searched point whose octave is outside [0, nlevels) gets no candidate in
  * either image (the reference would index mvScaleFactors out of range).
- * p->mbf is unused.  Asynchronous on `stream`. */
+ * p->mbf is unused.  d_n / d_n_r / d_last_n follow the count contract
+ * (plvi_hamming_knn2_batch).  Asynchronous on `stream`. */
 int plvi_search_by_projection_stereo_batch(int n_pairs, const plvi_proj_params* p, const float* kb8,
                                            const plvi_keypoint* d_kps, const uint8_t* d_desc, const int* d_n, int cap,
                                            const uint8_t* d_blocked, const int* d_cell_off, const int* d_cell_idx,
@@ -649,7 +673,8 @@ typedef struct plvi_reloc_params {
  * MapPoint index stored in mvpMapPoints[i2] by the call, -2 = set to NULL by
  * the rotation filter, -1 = untouched; nmatches [p] = the return value.
  * cur_cap, kf_cap <= 65535 and ~19 B per current + 8 B per KF point + 12 KB of
- * LDS <= 160 KB.  Asynchronous on `stream`. */
+ * LDS <= 160 KB.  d_cur_n / d_kf_n follow the count contract
+ * (plvi_hamming_knn2_batch).  Asynchronous on `stream`. */
 int plvi_search_reloc_batch(int n_pairs, const plvi_reloc_params* p, const plvi_keypoint* d_cur_kps,
                             const uint8_t* d_cur_desc, const int* d_cur_n, int cur_cap, const uint8_t* d_cur_blocked,
                             const int* d_cell_off, const int* d_cell_idx, const uint8_t* d_kf_flags,
@@ -686,7 +711,8 @@ typedef struct plvi_local_params {
  * stored in F.mvpMapPoints[idx] by the call, or -1; nmatches [f] = the
  * return value.  A MapPoint whose level is outside [0, nlevels) gets no
  * candidate.  cap <= 65535 and ~17 B per keypoint + 8 B per MapPoint +
- * 12 KB of LDS <= 160 KB. */
+ * 12 KB of LDS <= 160 KB.  d_n / d_mp_n follow the count contract
+ * (plvi_hamming_knn2_batch). */
 int plvi_search_local_batch(int n_frames, const plvi_local_params* p, const plvi_keypoint* d_kps, const uint8_t* d_desc,
                             const int* d_n, int cap, const uint8_t* d_blocked, const float* d_uright,
                             const int* d_cell_off, const int* d_cell_idx, const uint8_t* d_mp_flags,
@@ -714,7 +740,8 @@ int plvi_search_local(const plvi_local_params* p, const plvi_keypoint* kps, cons
  * (unused), mTrackViewCosR; level_r = mnTrackScaleLevelR (-1: no right
  * search).  Outputs match [f][cap] / match_r [f][cap_r] = the MapPoint
  * index stored in mvpMapPoints[idx] / mvpMapPoints[Nleft + idx] by the
- * call, or -1; nmatches [f] = the return value.  Asynchronous on `stream`. */
+ * call, or -1; nmatches [f] = the return value.  d_n / d_n_r / d_mp_n follow
+ * the count contract (plvi_hamming_knn2_batch).  Asynchronous on `stream`. */
 int plvi_search_local_stereo_batch(int n_frames, const plvi_local_params* p, const plvi_keypoint* d_kps,
                                    const uint8_t* d_desc, const int* d_n, int cap, const uint8_t* d_blocked,
                                    const int* d_l2r, const int* d_cell_off, const int* d_cell_idx,
@@ -858,7 +885,9 @@ int plvi_local_lines_filter_batch(int n_frames, const plvi_frustum_params* d_par
  * d_nstereo [n_frames] = left keypoints with a depth; *d_err |= 1 when a
  * right keypoint's row band leaves the image (the reference indexes
  * vRowIndices out of range), |= 2 when an SAD window leaves its level (the
- * reference's rowRange/colRange assert).  Asynchronous on `stream`. */
+ * reference's rowRange/colRange assert).  The counts are the handles' own
+ * (at most cap); the kernel clamps them to cap like every count of the count
+ * contract (plvi_hamming_knn2_batch).  Asynchronous on `stream`. */
 int plvi_stereo_match_batch(plvi_orb_extractor* left, plvi_orb_extractor* right, int n_frames, float mb, float mbf,
                             float* d_uright, float* d_depth, int* d_nstereo, int* d_err, void* stream);
 
@@ -884,6 +913,7 @@ int plvi_stereo_match(const plvi_keypoint* kpsL, const uint8_t* descL, int nL, c
  * no lines, as the reference returns before computing it), d_nstereo [n].
  * d_scratch: plvi_stereo_lines_scratch_bytes(n, capL, capR, idx_cap) bytes;
  * idx_cap bounds the grid entries of one frame (*d_err |= 4 if exceeded).
+ * d_nL / d_nR follow the count contract (plvi_hamming_knn2_batch).
  * Asynchronous on `stream`. */
 size_t plvi_stereo_lines_scratch_bytes(int n_frames, int capL, int capR, int idx_cap);
 int plvi_stereo_lines_batch(int n_frames, const plvi_keyline* d_klL, const uint8_t* d_descL, const int* d_nL, int capL,
@@ -953,6 +983,8 @@ typedef struct plvi_init_params {
  * plvi_assign_grid_batch over the same keypoints.  Output vnMatches12
  * [p][cap1] (first n1 entries) and nmatches [p].  cap1, cap2 <= 65535 and
  * ~24 B per F1 + ~19 B per F2 keypoint + 12 KB of LDS <= 160 KB.
+ * d_n1 / d_n2 follow the count contract (plvi_hamming_knn2_batch); rows of
+ * vbPrevMatched at or past n1 keep their values.
  * Replaces ORBmatcher.h:71 (SearchForInitialization). */
 int plvi_search_for_initialization_batch(int n_pairs, const plvi_init_params* p, const plvi_keypoint* d_kps1,
                                          const uint8_t* d_desc1, const int* d_n1, int cap1, float* d_prev_matched,
@@ -969,7 +1001,9 @@ int plvi_search_for_initialization_batch(int n_pairs, const plvi_init_params* p,
  * (nullable) {nn_mad, nn12_mad} as double [p][2].  d_scratch holds
  * 4 * n_pairs * cap1 ints.  The reference reads lmatches[0] and [i][1]:
  * with no query lines or fewer than 2 train lines it is undefined; here the
- * pair gets 0 matches.  Replaces LineMatcher.h:95 (SerachForInitialize). */
+ * pair gets 0 matches.  d_n1 / d_n2 follow the count contract
+ * (plvi_hamming_knn2_batch); pair rows at or past the pair count are not
+ * written.  Replaces LineMatcher.h:95 (SerachForInitialize). */
 int plvi_line_search_init_batch(const uint8_t* d_desc1, const int* d_n1, int cap1, const uint8_t* d_desc2,
                                 const int* d_n2, int cap2, int n_pairs, int* d_scratch, int* d_pairs, int* d_npairs,
                                 double* d_mad, void* stream);

@@ -52,11 +52,12 @@ __global__ __launch_bounds__(256) void search_by_bow_kernel(
     int* __restrict__ nmatches) {
     extern __shared__ __align__(16) int lds[];
     const int p = blockIdx.x;
-    int* s_mk = lds;                                      // [f_cap] matched KF index or -1
-    int2* s_pairs = reinterpret_cast<int2*>(lds + f_cap);  // [node_cap] shared (KF node, F node)
+    int* s_mk = lds;  // [f_cap] matched KF index or -1
+    // [node_cap] shared (KF node, F node), carved at the next 8-byte boundary (bow_smem)
+    int2* s_pairs = reinterpret_cast<int2*>(lds + ((f_cap + 1) & ~1));
     __shared__ int s_hist[kBowHisto], s_npairs, s_count, s_keep[3];
     const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int nF = f_n[p];
+    const int nF = min(f_n[p], f_cap);  // count contract (plvi_frontend.h)
     // F.Nleft (-1: one camera, every keypoint is "left")
     const int nLeft = (f_nleft && f_nleft[p] >= 0) ? f_nleft[p] : 0x7fffffff;
     const uint8_t* KD = kf_desc + (size_t)p * kf_cap * 32;
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(256) void search_by_bow_kernel(
     if (tid < kBowHisto) s_hist[tid] = 0;
     if (tid == 0) {
         // merge walk with the reference's lower_bound jumps (:289-448)
-        const int nK = kf_nnodes[p], nFn = f_nnodes[p];
+        const int nK = min(kf_nnodes[p], node_cap), nFn = min(f_nnodes[p], node_cap);
         int a = 0, b = 0, n = 0;
         while (a < nK && b < nFn) {
             const int ka = KN[a], fb = FN[b];
@@ -171,7 +172,11 @@ __global__ __launch_bounds__(256) void search_by_bow_kernel(
     if (tid == 0) nmatches[p] = s_count;
 }
 
-static size_t bow_smem(int f_cap, int node_cap) { return (size_t)f_cap * 4 + (size_t)node_cap * 8; }
+// s_mk rounded up to the int2 alignment of s_pairs; an odd f_cap makes 4*f_cap + 8*node_cap
+// at most 65532, so the header's 65536 rule still bounds the rounded size
+static size_t bow_smem(int f_cap, int node_cap) {
+    return (size_t)((f_cap + 1) & ~1) * 4 + (size_t)node_cap * 8;
+}
 
 }  // namespace plvi
 

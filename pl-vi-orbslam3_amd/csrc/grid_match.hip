@@ -40,7 +40,8 @@ __global__ __launch_bounds__(64) void line_match_grid_kernel(
     __shared__ int s_dist[kGridRightCap], s_m21[kGridRightCap], s_m12[kGridRightCap];
     __shared__ int s_ncand, s_overflow;
     const int p = blockIdx.x, lane = threadIdx.x;
-    const int n1 = n1s[p], n2 = n2s[p];
+    // count contract (plvi_frontend.h); the launcher bounds cap1 / cap2 by kGridRightCap
+    const int n1 = min(n1s[p], cap1), n2 = min(n2s[p], cap2);
     const int* L1 = lines1 + (size_t)p * cap1 * 4;
     const uint8_t* D1 = desc1 + (size_t)p * cap1 * 32;
     const int* CO = cell_off + (size_t)p * ((size_t)cols * rows + 1);

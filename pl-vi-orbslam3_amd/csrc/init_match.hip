@@ -236,6 +236,7 @@ __global__ __launch_bounds__(256) void line_init_select_kernel(const int* __rest
     __shared__ int h[4][260];
     __shared__ int s_med[2], s_dev[2], s_wsum[4];
     const int pr = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    // n2 is only compared with 2 (no row is indexed by it), so it needs no clamp to cap2
     const int n1 = min(n1_all[pr], cap1), n2 = n2_all[pr];
     if (n1 <= 0 || n2 < 2) {  // the reference reads lmatches[0] / [i][1]: undefined, no pairs here
         if (tid == 0) {

@@ -1413,7 +1413,7 @@ __global__ __launch_bounds__(64) void lbd_describe_kernel(const LineOctDev* __re
     __shared__ float bs[72];
     __shared__ float dv[72];
     const int li = blockIdx.x, f = blockIdx.y;
-    if (li >= counts[f]) return;
+    if (li >= counts[f]) return;  // li < fcap by the launch grid: the count needs no clamp
     const plvi_keyline kl = kls[(size_t)f * fcap + li];
     const LineOctDev& od = octs[kl.octave];
     const short2* pg = g_all + od.loff + (size_t)f * od.lplane;  // (dx, dy) interleaved

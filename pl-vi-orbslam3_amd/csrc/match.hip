@@ -32,7 +32,8 @@ __global__ __launch_bounds__(256) void hamming_knn2_kernel(const uint8_t* __rest
                                                            int* __restrict__ idx1, int* __restrict__ d1o) {
     __shared__ uint4 tr[kKnnChunk * 2];
     const int pair = blockIdx.y;
-    const int nQ = nq[pair], nT = nt[pair];
+    // count contract (plvi_frontend.h): counts read as clamped to their capacity
+    const int nQ = min(nq[pair], nq_cap), nT = min(nt[pair], nt_cap);
     const int qi = blockIdx.x * kKnnQ + threadIdx.x;
     if (blockIdx.x * kKnnQ >= nQ) return;
     const bool active = qi < nQ;
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(256) void line_match_finish_kernel(const int* __res
                                                                 int* __restrict__ m12, int* __restrict__ nmatch) {
     __shared__ int s_cnt;
     const int p = blockIdx.x;
-    const int a = n1[p], b = n2[p];
+    const int a = min(n1[p], cap1), b = min(n2[p], cap2);
     if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
     int local = 0;

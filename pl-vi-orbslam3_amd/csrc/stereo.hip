@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kStThreads) void stereo_orb_kernel(
     __shared__ int s_tmp[kStThreads / 64], s_njob, s_nacc, s_fail, s_hist[256], s_sel[2];
     __shared__ int s_part[kStThreads / 64][121], s_dist[kStThreads / 64][11];
     const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int nL = nLs[f], nR = nRs[f];
+    const int nL = min(nLs[f], capL), nR = min(nRs[f], capR);  // count contract (plvi_frontend.h)
     const int nRows = lv.h[0];
     int* s_row = lds_s;                                        // nRows + 1 (counts -> offsets)
     int* s_cur = s_row + (nRows + 1);                          // nRows fill cursors
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(kStThreads) void stereo_line_grid_kernel(
     double* __restrict__ dirs2, int* __restrict__ cell_off, int* __restrict__ cell_idx, int* __restrict__ err) {
     __shared__ int s_cnt[kLGridCells + 1], s_cur[kLGridCells], s_tmp[kStThreads / 64];
     const int f = blockIdx.x, t = threadIdx.x;
-    const int nL = nLs[f], nR = nRs[f];
+    const int nL = min(nLs[f], capL), nR = min(nRs[f], capR);  // count contract (plvi_frontend.h)
     const plvi_keyline* L = klL + (size_t)f * capL;
     const plvi_keyline* R = klR + (size_t)f * capR;
     int* l1 = lines1 + (size_t)f * capL * 4;
@@ -433,7 +433,7 @@ __global__ __launch_bounds__(kStThreads) void stereo_line_disparity_kernel(
     const int* __restrict__ m12, float* __restrict__ disp, float* __restrict__ dep, double* __restrict__ le,
     int* __restrict__ nstereo) {
     const int f = blockIdx.y, i1 = blockIdx.x * kStThreads + threadIdx.x;
-    const int nL = nLs[f], nR = nRs[f];
+    const int nL = min(nLs[f], capL), nR = min(nRs[f], capR);  // count contract (plvi_frontend.h)
     const size_t o = (size_t)f * capL + i1;
     int ok = 0;
     if (i1 < nL) {

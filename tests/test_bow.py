@@ -143,40 +143,21 @@ def test_descriptor_distance_batch_both_quirks():
 
 @pytest.mark.gpu
 def test_search_by_bow_batch_device():
-    """plvi_search_by_bow_batch: several (KF, F) pairs in one launch, fixed capacities."""
-    import ctypes
-    import plvi
-    lib = plvi.load()
+    """plvi_search_by_bow_batch: several (KF, F) pairs in one launch, fixed capacities; poisoned padding and
+    canary-filled outputs (tests/batch_pack.py)."""
+    import batch_pack as bp
     cases = [util.bow_case(40 + i, n_kf=300 + 50 * i, n_f=400 + 30 * i, n_nodes=60) for i in range(3)]
     P, kcap, fcap, ncap = len(cases), 500, 500, 64
-    kd = np.zeros((P, kcap, 32), np.uint8); ka = np.zeros((P, kcap), np.float32); kl = np.zeros((P, kcap), np.uint8)
-    fd = np.zeros((P, fcap, 32), np.uint8); fa = np.zeros((P, fcap), np.float32); fnk = np.zeros(P, np.int32)
-    kn = np.zeros((P, ncap), np.int32); ko = np.zeros((P, ncap + 1), np.int32); kc = np.zeros(P, np.int32)
-    ki = np.zeros((P, kcap), np.int32)
-    fn = np.zeros((P, ncap), np.int32); fo = np.zeros((P, ncap + 1), np.int32); fc = np.zeros(P, np.int32)
-    fi = np.zeros((P, fcap), np.int32)
-    refs = []
-    for p, c in enumerate(cases):
-        kdesc, kang, klive, kfv, fdesc, fang, ffv = c
-        kd[p, :len(kdesc)] = kdesc; ka[p, :len(kang)] = kang; kl[p, :len(klive)] = klive
-        fd[p, :len(fdesc)] = fdesc; fa[p, :len(fang)] = fang; fnk[p] = len(fdesc)
-        a, b, cidx = plvi.feature_vector_csr(kfv)
-        kn[p, :len(a)] = a; ko[p, :len(b)] = b; kc[p] = len(a); ki[p, :len(cidx)] = cidx
-        a, b, cidx = plvi.feature_vector_csr(ffv)
-        fn[p, :len(a)] = a; fo[p, :len(b)] = b; fc[p] = len(a); fi[p, :len(cidx)] = cidx
-        refs.append(oracle_lib.search_by_bow(*c, 0.75, True))
-    bufs = []
-    def dev(a):
-        b = plvi.DeviceBuffer(max(a.nbytes, 4)); b.upload(np.ascontiguousarray(a)); bufs.append(b)
-        return ctypes.c_void_p(b.ptr)
-    out = plvi.DeviceBuffer(P * fcap * 4); cnt = plvi.DeviceBuffer(P * 4)
-    rc = lib.plvi_search_by_bow_batch(P, 0.75, 1, kcap, fcap, ncap, dev(kd), dev(ka), dev(kl), dev(kn), dev(ko),
-                                      dev(kc), dev(ki), dev(fd), dev(fa), dev(fnk), dev(fn), dev(fo), dev(fc),
-                                      dev(fi), ctypes.c_void_p(out.ptr), ctypes.c_void_p(cnt.ptr), None)
+    refs = [oracle_lib.search_by_bow(*c, 0.75, True) for c in cases]
+    pk, dev = bp.pack_bow(cases, kcap, fcap, ncap), bp.Device()
+    out, get_m = dev.canary(P + bp.SLACK, fcap)
+    cnt, get_n = dev.canary(P + bp.SLACK)
+    rc = dev.lib.plvi_search_by_bow_batch(P, 0.75, 1, kcap, fcap, ncap, dev.up(pk["kd"]), dev.up(pk["ka"]),
+                                          dev.up(pk["kl"]), dev.up(pk["kn"]), dev.up(pk["ko"]),
+                                          dev.up(bp.counts_array(pk["kc"])), dev.up(pk["ki"]), dev.up(pk["fd"]),
+                                          dev.up(pk["fa"]), dev.up(bp.counts_array(pk["f_n"])), dev.up(pk["fn"]),
+                                          dev.up(pk["fo"]), dev.up(bp.counts_array(pk["fc"])), dev.up(pk["fi"]),
+                                          out, cnt, None)
     assert rc == 0
-    lib.plvi_device_synchronize()
-    m = out.download(np.zeros((P, fcap), np.int32))
-    n = cnt.download(np.zeros(P, np.int32))
-    for p, (n_ref, m_ref) in enumerate(refs):
-        assert n[p] == n_ref
-        np.testing.assert_array_equal(m[p, :len(m_ref)], m_ref)
+    bp.check_rows(get_m(), [m for _, m in refs], "search_by_bow match_kf")
+    bp.check_counts(get_n(), [n for n, _ in refs], "search_by_bow")

@@ -224,54 +224,50 @@ def test_oracle_line_search_init_degenerate():
 def test_search_for_initialization_batch_vs_oracle():
     """Several (F1, F2) pairs in one launch through the C-ABI batch entry
     point (device tables, grid by plvi_assign_grid_batch), two iterations of
-    vbPrevMatched as Tracking carries it; each pair equals the oracle."""
+    vbPrevMatched as Tracking carries it; each pair equals the oracle.
+    Padding rows hold poison, outputs a canary (tests/batch_pack.py)."""
+    import batch_pack as bp
     import plvi
-    cases = [(3, 2), (11, 6), (21, 1), (30, 12)]
-    pairs = [_orb_pair(s, g) for s, g in cases]
-    P = len(pairs)
-    cap1 = max(len(p[0]) for p in pairs)
-    cap2 = max(len(p[2]) for p in pairs)
-    K1 = np.zeros((P, cap1), plvi.KEYPOINT_DTYPE)
-    K2 = np.zeros((P, cap2), plvi.KEYPOINT_DTYPE)
-    D1 = np.zeros((P, cap1, 32), np.uint8)
-    D2 = np.zeros((P, cap2, 32), np.uint8)
-    PV = np.zeros((P, cap1, 2), np.float32)
-    N = np.zeros(2 * P, np.int32)
-    for i, (k1, d1, k2, d2) in enumerate(pairs):
+
+    def kp(k):
+        out = np.zeros(len(k), plvi.KEYPOINT_DTYPE)
         for f in ("x", "y", "size", "angle", "response", "octave", "class_id"):
-            K1[i, :len(k1)][f] = k1[f]
-            K2[i, :len(k2)][f] = k2[f]
-        D1[i, :len(k1)] = d1
-        D2[i, :len(k2)] = d2
-        PV[i, :len(k1), 0], PV[i, :len(k1), 1] = k1["x"], k1["y"]
-        N[i], N[P + i] = len(k1), len(k2)
-    bufs = {k: plvi.DeviceBuffer(a.nbytes) for k, a in (("k1", K1), ("k2", K2), ("d1", D1), ("d2", D2), ("pv", PV),
-                                                         ("n", N))}
-    for k, a in (("k1", K1), ("k2", K2), ("d1", D1), ("d2", D2), ("pv", PV), ("n", N)):
-        bufs[k].upload(a)
-    co = plvi.DeviceBuffer(4 * 3073 * P)
-    ci = plvi.DeviceBuffer(4 * cap2 * P)
-    m = plvi.DeviceBuffer(4 * cap1 * P)
-    nm = plvi.DeviceBuffer(4 * P)
-    plvi.assign_grid_batch(bufs["k2"].ptr, bufs["n"].ptr + 4 * P, cap2, P, plvi.GridParams(*[float(g) for g in GRID]),
-                           co.ptr, ci.ptr)
+            out[f] = k[f]
+        return out
+    cases = []
+    for s, g in [(3, 2), (11, 6), (21, 1), (30, 12)]:
+        k1, d1, k2, d2 = _orb_pair(s, g)
+        cases.append({"k1": kp(k1), "d1": d1, "prev": np.stack([k1["x"], k1["y"]], 1).astype(np.float32),
+                      "k2": kp(k2), "d2": d2})
+    P = len(cases)
+    cap1 = max(len(c["k1"]) for c in cases) + 9
+    cap2 = max(len(c["k2"]) for c in cases) + 5
+    b = {**bp.pack_keyed(cases, cap1, bp.INIT_K1), **bp.pack_keyed(cases, cap2, bp.INIT_K2)}
+    dev = bp.Device()
+    d_k2, d_n2 = dev.up(b["k2"]), dev.up(bp.counts_array([len(c["k2"]) for c in cases]))
+    co, ci = bp.assign_grid(dev, d_k2, d_n2, cap2, P, (GRID[0], None, GRID[1], None, GRID[2], GRID[3]),
+                            [c["k2"] for c in cases])
+    d_k1, d_d1, d_d2 = dev.up(b["k1"]), dev.up(b["d1"]), dev.up(b["d2"])
+    d_n1 = dev.up(bp.counts_array([len(c["k1"]) for c in cases]))
+    d_pv, get_pv = dev.table(b["prev"])
     prm = plvi.InitParams(*[float(g) for g in GRID], 100, 0.9, 1)
-    ref_prev = [np.stack([p[0]["x"], p[0]["y"]], 1) for p in pairs]
+    ref_prev = [c["prev"] for c in cases]
     for it, win in enumerate((100, 40)):
         prm.window = win
-        plvi.search_for_initialization_batch(P, prm, bufs["k1"].ptr, bufs["d1"].ptr, bufs["n"].ptr, cap1,
-                                             bufs["pv"].ptr, bufs["k2"].ptr, bufs["d2"].ptr, bufs["n"].ptr + 4 * P,
-                                             cap2, co.ptr, ci.ptr, m.ptr, nm.ptr)
-        plvi.load().plvi_device_synchronize()
-        gm = m.download(np.zeros((P, cap1), np.int32))
-        gn = nm.download(np.zeros(P, np.int32))
-        gpv = bufs["pv"].download(np.zeros((P, cap1, 2), np.float32))
-        for i, (k1, d1, k2, d2) in enumerate(pairs):
-            en, em, epv = ol.search_for_initialization(k1, d1, ref_prev[i], k2, d2, GRID, window=win)
-            assert gn[i] == en and (it > 0 or en > 20), f"pair {i} iter {it}: {gn[i]} vs {en}"
-            np.testing.assert_array_equal(gm[i, :len(k1)], em)
-            np.testing.assert_array_equal(gpv[i, :len(k1)], epv)
-            ref_prev[i] = epv
+        m, get_m = dev.canary(P + bp.SLACK, cap1)
+        nm, get_n = dev.canary(P + bp.SLACK)
+        plvi.search_for_initialization_batch(P, prm, d_k1.value, d_d1.value, d_n1.value, cap1, d_pv.value, d_k2.value,
+                                             d_d2.value, d_n2.value, cap2, co.value, ci.value, m.value, nm.value)
+        refs = [ol.search_for_initialization(c["k1"], c["d1"], ref_prev[i], c["k2"], c["d2"], GRID, window=win)
+                for i, c in enumerate(cases)]
+        assert it > 0 or all(en > 20 for en, _, _ in refs)
+        bp.check_rows(get_m(), [em for _, em, _ in refs], f"vnMatches12 iter {it}")
+        bp.check_counts(get_n(), [en for en, _, _ in refs], f"nmatches iter {it}")
+        gpv = get_pv()
+        for i, (_, _, epv) in enumerate(refs):
+            np.testing.assert_array_equal(gpv[i, :len(epv)], epv)
+            np.testing.assert_array_equal(gpv[i, len(epv):], b["prev"][i, len(epv):])
+        ref_prev = [epv for _, _, epv in refs]
 
 
 @pytest.mark.gpu
@@ -301,7 +297,9 @@ def test_search_for_initialization_host_edge_cases():
 @pytest.mark.gpu
 def test_line_search_init_batch_vs_oracle():
     """LineMatches and the MAD values of several pairs in one launch, plus
-    the degenerate pairs (no query lines, one train line, all-equal rows)."""
+    the degenerate pairs (no query lines, one train line, all-equal rows).
+    Padding rows hold poison, outputs a canary (tests/batch_pack.py)."""
+    import batch_pack as bp
     import plvi
     descs = []
     for seed, gap in ((5, 1), (9, 4), (14, 10)):
@@ -311,33 +309,21 @@ def test_line_search_init_batch_vs_oracle():
     t2 = np.stack([np.zeros(32, np.uint8), np.full(32, 1, np.uint8)])
     descs += [(z[:0], t2), (z, t2[:1]), (z, t2)]
     P = len(descs)
-    cap1 = max(max(len(a) for a, _ in descs), 1)
-    cap2 = max(len(b) for _, b in descs)
-    D1 = np.zeros((P, cap1, 32), np.uint8)
-    D2 = np.zeros((P, cap2, 32), np.uint8)
-    N = np.zeros(2 * P, np.int32)
+    cap1 = max(len(a) for a, _ in descs) + 3
+    cap2 = max(len(b) for _, b in descs) + 7
+    pk, dev = bp.pack_knn(descs, cap1, cap2), bp.Device()
+    scr = dev.up(np.zeros(4 * (P + bp.SLACK) * cap1, np.int32))
+    pr, get_p = dev.canary(P + bp.SLACK, cap1, 2)
+    cnt, get_n = dev.canary(P + bp.SLACK)
+    mad, get_mad = dev.canary(P + bp.SLACK, 4)
+    plvi.line_search_init_batch(dev.up(pk["q"]).value, dev.up(bp.counts_array(pk["nq"])).value, cap1,
+                                dev.up(pk["t"]).value, dev.up(bp.counts_array(pk["nt"])).value, cap2, P, scr.value,
+                                pr.value, cnt.value, mad.value)
+    refs = [ol.line_search_init(a, b) for a, b in descs]
+    bp.check_rows(get_p(), [ep for ep, _ in refs], "LineMatches")
+    bp.check_counts(get_n(), [len(ep) for ep, _ in refs], "LineMatches")
+    gm = get_mad()
     for i, (a, b) in enumerate(descs):
-        D1[i, :len(a)] = a
-        D2[i, :len(b)] = b
-        N[i], N[P + i] = len(a), len(b)
-    b1, b2, bn = plvi.DeviceBuffer(D1.nbytes), plvi.DeviceBuffer(D2.nbytes), plvi.DeviceBuffer(N.nbytes)
-    b1.upload(D1)
-    b2.upload(D2)
-    bn.upload(N)
-    scr = plvi.DeviceBuffer(16 * P * cap1)
-    pr = plvi.DeviceBuffer(8 * P * cap1)
-    cnt = plvi.DeviceBuffer(4 * P)
-    mad = plvi.DeviceBuffer(16 * P)
-    plvi.line_search_init_batch(b1.ptr, bn.ptr, cap1, b2.ptr, bn.ptr + 4 * P, cap2, P, scr.ptr, pr.ptr, cnt.ptr,
-                                mad.ptr)
-    plvi.load().plvi_device_synchronize()
-    gp = pr.download(np.zeros((P, cap1, 2), np.int32))
-    gc = cnt.download(np.zeros(P, np.int32))
-    gm = mad.download(np.zeros((P, 2), np.float64))
-    for i, (a, b) in enumerate(descs):
-        ep, emad = ol.line_search_init(a, b)
-        assert gc[i] == len(ep), f"pair {i}"
-        np.testing.assert_array_equal(gp[i, :gc[i]], ep)
         if len(a) and len(b) >= 2:
-            assert tuple(gm[i]) == emad
-    assert gc[0] > 5
+            assert tuple(gm[i].view(np.float64)) == refs[i][1]
+    assert len(refs[0][0]) > 5

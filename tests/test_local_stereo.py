@@ -216,54 +216,35 @@ def test_local_stereo_degenerate():
 @pytest.mark.gpu
 def test_local_stereo_batch_device():
     """Several two-camera frames in one launch through plvi_search_local_stereo_batch (device tables, both
-    grids built on the device), each compared with the oracle."""
+    grids built on the device), each compared with the oracle; poisoned padding rows and canary-filled
+    outputs (tests/batch_pack.py)."""
     import ctypes
-    import plvi
-    lib = plvi.load()
+    import batch_pack as bp
     cases = [util.local_stereo_case(70 + i, n_left=500 + 60 * i, n_right=450 + 50 * i, n_mp=700 + 80 * i)
              for i in range(3)]
-    P, cl, cr, mc = len(cases), 700, 600, 900
-    kl = np.zeros((P, cl), plvi.KEYPOINT_DTYPE); kr = np.zeros((P, cr), plvi.KEYPOINT_DTYPE)
-    dl = np.zeros((P, cl, 32), np.uint8); dr = np.zeros((P, cr, 32), np.uint8)
-    bl = np.zeros((P, cl), np.uint8); br = np.zeros((P, cr), np.uint8)
-    l2r = np.full((P, cl), -1, np.int32); r2l = np.full((P, cr), -1, np.int32)
-    nl = np.zeros(P, np.int32); nr = np.zeros(P, np.int32); nm = np.zeros(P, np.int32)
-    fl = np.zeros((P, mc), np.uint8); pr = np.zeros((P, mc, 4), np.float32); lv = np.zeros((P, mc), np.int32)
-    prr = np.zeros((P, mc, 4), np.float32); lvr = np.zeros((P, mc), np.int32); md = np.zeros((P, mc, 32), np.uint8)
-    for p, c in enumerate(cases):
-        a, b, m = len(c["kps"]), len(c["kps_r"]), len(c["mp_flags"])
-        kl[p, :a] = c["kps"]; dl[p, :a] = c["desc"]; bl[p, :a] = c["blocked"]; l2r[p, :a] = c["l2r"]; nl[p] = a
-        kr[p, :b] = c["kps_r"]; dr[p, :b] = c["desc_r"]; br[p, :b] = c["blocked_r"]; r2l[p, :b] = c["r2l"]
-        nr[p] = b
-        fl[p, :m] = c["mp_flags"]; pr[p, :m] = c["mp_proj"]; lv[p, :m] = c["mp_level"]
-        prr[p, :m] = c["mp_proj_r"]; lvr[p, :m] = c["mp_level_r"]; md[p, :m] = c["mp_desc"]; nm[p] = m
-    bufs = []
-
-    def dev(x):
-        b = plvi.DeviceBuffer(max(x.nbytes, 4)); b.upload(np.ascontiguousarray(x)); bufs.append(b)
-        return b.ptr
-    g = cases[0]["grid"]
-    gp = plvi.GridParams(g[0], g[2], g[4], g[5])
-    dkl, dnl, dkr, dnr = dev(kl), dev(nl), dev(kr), dev(nr)
-    col = plvi.DeviceBuffer(P * 3073 * 4); cil = plvi.DeviceBuffer(P * cl * 4)
-    cor = plvi.DeviceBuffer(P * 3073 * 4); cir = plvi.DeviceBuffer(P * cr * 4)
-    plvi.assign_grid_batch(dkl, dnl, cl, P, gp, col.ptr, cil.ptr)
-    plvi.assign_grid_batch(dkr, dnr, cr, P, gp, cor.ptr, cir.ptr)
+    cl, cr, mc = 700, 600, 900
+    P = len(cases)
+    b = {**bp.pack_keyed(cases, cl, bp.LOCAL2_LEFT), **bp.pack_keyed(cases, cr, bp.LOCAL2_RIGHT),
+         **bp.pack_keyed(cases, mc, bp.LOCAL2_MP)}
+    dev = bp.Device()
+    dkl, dkr = dev.up(b["kps"]), dev.up(b["kps_r"])
+    dnl = dev.up(bp.counts_array([len(c["kps"]) for c in cases]))
+    dnr = dev.up(bp.counts_array([len(c["kps_r"]) for c in cases]))
+    dnm = dev.up(bp.counts_array([len(c["mp_flags"]) for c in cases]))
+    col, cil = bp.assign_grid(dev, dkl, dnl, cl, P, cases[0]["grid"], [c["kps"] for c in cases])
+    cor, cir = bp.assign_grid(dev, dkr, dnr, cr, P, cases[0]["grid"], [c["kps_r"] for c in cases])
+    ml, get_l = dev.canary(P + bp.SLACK, cl)
+    mr, get_r = dev.canary(P + bp.SLACK, cr)
+    nmt, get_n = dev.canary(P + bp.SLACK)
     prm = util.local_params(cases[0], 1.0)
     prm.nnratio = 0.8
-    ml = plvi.DeviceBuffer(P * cl * 4); mr = plvi.DeviceBuffer(P * cr * 4); nmt = plvi.DeviceBuffer(P * 4)
-    V = ctypes.c_void_p
-    rc = lib.plvi_search_local_stereo_batch(P, ctypes.byref(prm), V(dkl), V(dev(dl)), V(dnl), cl, V(dev(bl)),
-                                            V(dev(l2r)), V(col.ptr), V(cil.ptr), V(dkr), V(dev(dr)), V(dnr), cr,
-                                            V(dev(br)), V(dev(r2l)), V(cor.ptr), V(cir.ptr), V(dev(fl)), V(dev(pr)),
-                                            V(dev(lv)), V(dev(prr)), V(dev(lvr)), V(dev(md)), V(dev(nm)), mc,
-                                            V(ml.ptr), V(mr.ptr), V(nmt.ptr), None)
+    rc = dev.lib.plvi_search_local_stereo_batch(
+        P, ctypes.byref(prm), dkl, dev.up(b["desc"]), dnl, cl, dev.up(b["blocked"]), dev.up(b["l2r"]), col, cil, dkr,
+        dev.up(b["desc_r"]), dnr, cr, dev.up(b["blocked_r"]), dev.up(b["r2l"]), cor, cir, dev.up(b["mp_flags"]),
+        dev.up(b["mp_proj"]), dev.up(b["mp_level"]), dev.up(b["mp_proj_r"]), dev.up(b["mp_level_r"]),
+        dev.up(b["mp_desc"]), dnm, mc, ml, mr, nmt, None)
+    refs = [oracle_lib.search_local_stereo(c, 1.0) for c in cases]
     assert rc == 0
-    lib.plvi_device_synchronize()
-    ML = ml.download(np.zeros((P, cl), np.int32)); MR = mr.download(np.zeros((P, cr), np.int32))
-    N = nmt.download(np.zeros(P, np.int32))
-    for p, c in enumerate(cases):
-        ne, mle, mre = oracle_lib.search_local_stereo(c, 1.0)
-        assert N[p] == ne
-        np.testing.assert_array_equal(ML[p, :len(mle)], mle)
-        np.testing.assert_array_equal(MR[p, :len(mre)], mre)
+    bp.check_rows(get_l(), [r[1] for r in refs], "match")
+    bp.check_rows(get_r(), [r[2] for r in refs], "match_r")
+    bp.check_counts(get_n(), [r[0] for r in refs], "nmatches")

@@ -107,50 +107,28 @@ def test_search_by_projection_matches_oracle(seed, th, fwd, bwd, ori, ur):
 
 @pytest.mark.gpu
 def test_assign_grid_and_projection_batch_device():
+    """Poisoned padding rows, canary-filled outputs and grid tables (tests/batch_pack.py)."""
     import ctypes
-    import plvi
-    lib = plvi.load()
+    import batch_pack as bp
     cases = [util.projection_case(40 + i, n_cur=700 + 90 * i, n_last=600 + 50 * i) for i in range(3)]
     P, cc, lc = len(cases), 1000, 800
-    kp = np.zeros((P, cc), plvi.KEYPOINT_DTYPE); cd = np.zeros((P, cc, 32), np.uint8)
-    cb = np.zeros((P, cc), np.uint8); cn = np.zeros(P, np.int32)
-    x3 = np.zeros((P, lc, 3), np.float32); lo = np.zeros((P, lc), np.int32); la = np.zeros((P, lc), np.float32)
-    md = np.zeros((P, lc, 32), np.uint8); lf = np.zeros((P, lc), np.uint8); ln = np.zeros(P, np.int32)
-    for p, c in enumerate(cases):
-        n, m = len(c["cur_kps"]), len(c["flags"])
-        kp[p, :n] = c["cur_kps"]; cd[p, :n] = c["cur_desc"]; cb[p, :n] = c["cur_blocked"]; cn[p] = n
-        x3[p, :m] = c["x3dc"]; lo[p, :m] = c["last_octave"]; la[p, :m] = c["last_angle"]
-        md[p, :m] = c["mp_desc"]; lf[p, :m] = c["flags"]; ln[p] = m
-    bufs = []
-
-    def dev(a):
-        b = plvi.DeviceBuffer(max(a.nbytes, 4)); b.upload(np.ascontiguousarray(a)); bufs.append(b)
-        return b.ptr
-    off = plvi.DeviceBuffer(P * 3073 * 4); idx = plvi.DeviceBuffer(P * cc * 4)
-    g = cases[0]["grid"]
-    gp = plvi.GridParams(g[0], g[2], g[4], g[5])
-    dk, dn = dev(kp), dev(cn)
-    plvi.assign_grid_batch(dk, dn, cc, P, gp, off.ptr, idx.ptr)
-    lib.plvi_device_synchronize()
-    offs = off.download(np.zeros((P, 3073), np.int32)); idxs = idx.download(np.zeros((P, cc), np.int32))
-    for p, c in enumerate(cases):
-        eo, ei = oracle_lib.assign_grid(c["cur_kps"]["x"], c["cur_kps"]["y"], c["grid"])
-        np.testing.assert_array_equal(offs[p], eo)
-        np.testing.assert_array_equal(idxs[p, :len(ei)], ei)
+    b = {**bp.pack_keyed(cases, cc, bp.CUR), **bp.pack_keyed(cases, lc, bp.PROJ_LAST)}
+    dev = bp.Device()
+    dk = dev.up(b["cur_kps"])
+    dn = dev.up(bp.counts_array([len(c["cur_kps"]) for c in cases]))
+    off, idx = bp.assign_grid(dev, dk, dn, cc, P, cases[0]["grid"], [c["cur_kps"] for c in cases])
     prm = util.proj_params(cases[0], 15.0)
     prm.check_orientation = 1
-    out = plvi.DeviceBuffer(P * cc * 4); nm = plvi.DeviceBuffer(P * 4)
-    V = ctypes.c_void_p
-    rc = lib.plvi_search_by_projection_batch(P, ctypes.byref(prm), V(dk), V(dev(cd)), V(dn), cc, V(dev(cb)), None,
-                                             V(off.ptr), V(idx.ptr), V(dev(x3)), V(dev(lo)), V(dev(la)), V(dev(md)),
-                                             V(dev(lf)), V(dev(ln)), lc, V(out.ptr), V(nm.ptr), None)
+    out, get_m = dev.canary(P + bp.SLACK, cc)
+    nm, get_n = dev.canary(P + bp.SLACK)
+    rc = dev.lib.plvi_search_by_projection_batch(
+        P, ctypes.byref(prm), dk, dev.up(b["cur_desc"]), dn, cc, dev.up(b["cur_blocked"]), None, off, idx,
+        dev.up(b["x3dc"]), dev.up(b["last_octave"]), dev.up(b["last_angle"]), dev.up(b["mp_desc"]),
+        dev.up(b["flags"]), dev.up(bp.counts_array([len(c["flags"]) for c in cases])), lc, out, nm, None)
     assert rc == 0
-    lib.plvi_device_synchronize()
-    M = out.download(np.zeros((P, cc), np.int32)); N = nm.download(np.zeros(P, np.int32))
-    for p, c in enumerate(cases):
-        n_ref, m_ref = oracle_lib.search_by_projection(c, 15.0)
-        assert N[p] == n_ref
-        np.testing.assert_array_equal(M[p, :len(m_ref)], m_ref)
+    refs = [oracle_lib.search_by_projection(c, 15.0) for c in cases]
+    bp.check_rows(get_m(), [m for _, m in refs], "search_by_projection match")
+    bp.check_counts(get_n(), [n for n, _ in refs], "search_by_projection")
 
 
 # ------------------------------------------------- local-map search (ORBmatcher.cc:44-145)

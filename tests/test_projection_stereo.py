@@ -154,53 +154,36 @@ def test_stereo_lds_check_counts_static_shared():
 
 @pytest.mark.gpu
 def test_stereo_projection_batch_device():
-    """Several (CurrentFrame, LastFrame) pairs in one plvi_search_by_projection_stereo_batch launch."""
+    """Several (CurrentFrame, LastFrame) pairs in one plvi_search_by_projection_stereo_batch launch; poisoned
+    padding rows and canary-filled outputs (tests/batch_pack.py)."""
     import ctypes
-    import plvi
-    lib = plvi.load()
+    import batch_pack as bp
     cases = [util.projection_stereo_case(80 + i, n_left=600 + 50 * i, n_right=550 + 40 * i, n_last=500 + 60 * i)
              for i in range(3)]
-    P, cl, cr, lc = len(cases), 800, 700, 700
-    kl = np.zeros((P, cl), plvi.KEYPOINT_DTYPE); kr = np.zeros((P, cr), plvi.KEYPOINT_DTYPE)
-    dl = np.zeros((P, cl, 32), np.uint8); dr = np.zeros((P, cr, 32), np.uint8)
-    bl = np.zeros((P, cl), np.uint8); br = np.zeros((P, cr), np.uint8)
-    nl = np.zeros(P, np.int32); nr = np.zeros(P, np.int32); nlast = np.zeros(P, np.int32)
-    x3 = np.zeros((P, lc, 3), np.float32); x3r = np.zeros((P, lc, 3), np.float32)
-    oc = np.zeros((P, lc), np.int32); an = np.zeros((P, lc), np.float32)
-    md = np.zeros((P, lc, 32), np.uint8); lf = np.zeros((P, lc), np.uint8)
-    for p, c in enumerate(cases):
-        a, b, m = len(c["kps"]), len(c["kps_r"]), len(c["flags"])
-        kl[p, :a] = c["kps"]; dl[p, :a] = c["desc"]; bl[p, :a] = c["blocked"]; nl[p] = a
-        kr[p, :b] = c["kps_r"]; dr[p, :b] = c["desc_r"]; br[p, :b] = c["blocked_r"]; nr[p] = b
-        x3[p, :m] = c["x3dc"]; x3r[p, :m] = c["x3dr"]; oc[p, :m] = c["last_octave"]; an[p, :m] = c["last_angle"]
-        md[p, :m] = c["mp_desc"]; lf[p, :m] = c["flags"]; nlast[p] = m
-    bufs = []
-
-    def dev(x):
-        b = plvi.DeviceBuffer(max(x.nbytes, 4)); b.upload(np.ascontiguousarray(x)); bufs.append(b)
-        return b.ptr
-    g = cases[0]["grid"]
-    gp = plvi.GridParams(g[0], g[2], g[4], g[5])
-    dkl, dnl, dkr, dnr = dev(kl), dev(nl), dev(kr), dev(nr)
-    col = plvi.DeviceBuffer(P * 3073 * 4); cil = plvi.DeviceBuffer(P * cl * 4)
-    cor = plvi.DeviceBuffer(P * 3073 * 4); cir = plvi.DeviceBuffer(P * cr * 4)
-    plvi.assign_grid_batch(dkl, dnl, cl, P, gp, col.ptr, cil.ptr)
-    plvi.assign_grid_batch(dkr, dnr, cr, P, gp, cor.ptr, cir.ptr)
+    cl, cr, mc = 800, 700, 700
+    P = len(cases)
+    b = {**bp.pack_keyed(cases, cl, bp.LEFT), **bp.pack_keyed(cases, cr, bp.RIGHT),
+         **bp.pack_keyed(cases, mc, bp.PROJ2_LAST)}
+    dev = bp.Device()
+    dkl, dkr = dev.up(b["kps"]), dev.up(b["kps_r"])
+    dnl = dev.up(bp.counts_array([len(c["kps"]) for c in cases]))
+    dnr = dev.up(bp.counts_array([len(c["kps_r"]) for c in cases]))
+    dnm = dev.up(bp.counts_array([len(c["flags"]) for c in cases]))
+    col, cil = bp.assign_grid(dev, dkl, dnl, cl, P, cases[0]["grid"], [c["kps"] for c in cases])
+    cor, cir = bp.assign_grid(dev, dkr, dnr, cr, P, cases[0]["grid"], [c["kps_r"] for c in cases])
+    ml, get_l = dev.canary(P + bp.SLACK, cl)
+    mr, get_r = dev.canary(P + bp.SLACK, cr)
+    nmt, get_n = dev.canary(P + bp.SLACK)
     prm = util.proj_params(cases[0], 7.0)
     prm.check_orientation = 1
     kb = np.ascontiguousarray(cases[0]["kb8"], np.float32)
-    ml = plvi.DeviceBuffer(P * cl * 4); mr = plvi.DeviceBuffer(P * cr * 4); nmt = plvi.DeviceBuffer(P * 4)
-    V = ctypes.c_void_p
-    rc = lib.plvi_search_by_projection_stereo_batch(
-        P, ctypes.byref(prm), kb.ctypes.data_as(V), V(dkl), V(dev(dl)), V(dnl), cl, V(dev(bl)), V(col.ptr),
-        V(cil.ptr), V(dkr), V(dev(dr)), V(dnr), cr, V(dev(br)), V(cor.ptr), V(cir.ptr), V(dev(x3)), V(dev(x3r)),
-        V(dev(oc)), V(dev(an)), V(dev(md)), V(dev(lf)), V(dev(nlast)), lc, V(ml.ptr), V(mr.ptr), V(nmt.ptr), None)
+    rc = dev.lib.plvi_search_by_projection_stereo_batch(
+        P, ctypes.byref(prm), kb.ctypes.data_as(ctypes.c_void_p), dkl, dev.up(b["desc"]), dnl, cl,
+        dev.up(b["blocked"]), col, cil, dkr, dev.up(b["desc_r"]), dnr, cr, dev.up(b["blocked_r"]), cor, cir,
+        dev.up(b["x3dc"]), dev.up(b["x3dr"]), dev.up(b["last_octave"]), dev.up(b["last_angle"]),
+        dev.up(b["mp_desc"]), dev.up(b["flags"]), dnm, mc, ml, mr, nmt, None)
+    refs = [oracle_lib.search_by_projection_stereo(c, 7.0) for c in cases]
     assert rc == 0
-    lib.plvi_device_synchronize()
-    ML = ml.download(np.zeros((P, cl), np.int32)); MR = mr.download(np.zeros((P, cr), np.int32))
-    N = nmt.download(np.zeros(P, np.int32))
-    for p, c in enumerate(cases):
-        ne, mle, mre = oracle_lib.search_by_projection_stereo(c, 7.0)
-        assert N[p] == ne
-        np.testing.assert_array_equal(ML[p, :len(mle)], mle)
-        np.testing.assert_array_equal(MR[p, :len(mre)], mre)
+    bp.check_rows(get_l(), [r[1] for r in refs], "match")
+    bp.check_rows(get_r(), [r[2] for r in refs], "match_r")
+    bp.check_counts(get_n(), [r[0] for r in refs], "nmatches")

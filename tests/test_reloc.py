@@ -174,42 +174,26 @@ def test_search_reloc_degenerate():
 @pytest.mark.gpu
 def test_search_reloc_batch_device():
     """Several candidate KeyFrames against one current frame in one launch (the relocalization loop's
-    candidates), grid built on the device."""
+    candidates), grid built on the device; poisoned padding rows and canary-filled outputs
+    (tests/batch_pack.py)."""
     import ctypes
-    import plvi
-    lib = plvi.load()
+    import batch_pack as bp
     cases = [util.reloc_case(60 + i, n_cur=700 + 90 * i, n_kf=500 + 70 * i) for i in range(4)]
     P, cc, kc = len(cases), 1000, 800
-    kp = np.zeros((P, cc), plvi.KEYPOINT_DTYPE); cd = np.zeros((P, cc, 32), np.uint8)
-    cb = np.zeros((P, cc), np.uint8); cn = np.zeros(P, np.int32)
-    fl = np.zeros((P, kc), np.uint8); x3 = np.zeros((P, kc, 3), np.float32); ds = np.zeros((P, kc, 3), np.float32)
-    lv = np.zeros((P, kc), np.int32); an = np.zeros((P, kc), np.float32); md = np.zeros((P, kc, 32), np.uint8)
-    kn = np.zeros(P, np.int32)
-    for p, c in enumerate(cases):
-        n, m = len(c["cur_kps"]), len(c["kf_flags"])
-        kp[p, :n] = c["cur_kps"]; cd[p, :n] = c["cur_desc"]; cb[p, :n] = c["cur_blocked"]; cn[p] = n
-        fl[p, :m] = c["kf_flags"]; x3[p, :m] = c["x3dc"]; ds[p, :m] = c["dist"]; lv[p, :m] = c["level"]
-        an[p, :m] = c["kf_angle"]; md[p, :m] = c["mp_desc"]; kn[p] = m
-    bufs = []
-
-    def dev(a):
-        b = plvi.DeviceBuffer(max(a.nbytes, 4)); b.upload(np.ascontiguousarray(a)); bufs.append(b)
-        return b.ptr
-    off = plvi.DeviceBuffer(P * 3073 * 4); idx = plvi.DeviceBuffer(P * cc * 4)
-    g = cases[0]["grid"]
-    dk, dn = dev(kp), dev(cn)
-    plvi.assign_grid_batch(dk, dn, cc, P, plvi.GridParams(g[0], g[2], g[4], g[5]), off.ptr, idx.ptr)
+    b = {**bp.pack_keyed(cases, cc, bp.CUR), **bp.pack_keyed(cases, kc, bp.RELOC_KF)}
+    dev = bp.Device()
+    dk = dev.up(b["cur_kps"])
+    dn = dev.up(bp.counts_array([len(c["cur_kps"]) for c in cases]))
+    off, idx = bp.assign_grid(dev, dk, dn, cc, P, cases[0]["grid"], [c["cur_kps"] for c in cases])
     prm = util.reloc_params(cases[0], 10.0, 100)
     prm.check_orientation = 1
-    out = plvi.DeviceBuffer(P * cc * 4); nm = plvi.DeviceBuffer(P * 4)
-    V = ctypes.c_void_p
-    rc = lib.plvi_search_reloc_batch(P, ctypes.byref(prm), V(dk), V(dev(cd)), V(dn), cc, V(dev(cb)), V(off.ptr),
-                                     V(idx.ptr), V(dev(fl)), V(dev(x3)), V(dev(ds)), V(dev(lv)), V(dev(an)),
-                                     V(dev(md)), V(dev(kn)), kc, V(out.ptr), V(nm.ptr), None)
+    out, get_m = dev.canary(P + bp.SLACK, cc)
+    nm, get_n = dev.canary(P + bp.SLACK)
+    rc = dev.lib.plvi_search_reloc_batch(
+        P, ctypes.byref(prm), dk, dev.up(b["cur_desc"]), dn, cc, dev.up(b["cur_blocked"]), off, idx,
+        dev.up(b["kf_flags"]), dev.up(b["x3dc"]), dev.up(b["dist"]), dev.up(b["level"]), dev.up(b["kf_angle"]),
+        dev.up(b["mp_desc"]), dev.up(bp.counts_array([len(c["kf_flags"]) for c in cases])), kc, out, nm, None)
     assert rc == 0
-    lib.plvi_device_synchronize()
-    M = out.download(np.zeros((P, cc), np.int32)); N = nm.download(np.zeros(P, np.int32))
-    for p, c in enumerate(cases):
-        n_ref, m_ref = oracle_lib.search_reloc(c, 10.0, 100)
-        assert N[p] == n_ref
-        np.testing.assert_array_equal(M[p, :len(m_ref)], m_ref)
+    refs = [oracle_lib.search_reloc(c, 10.0, 100) for c in cases]
+    bp.check_rows(get_m(), [m for _, m in refs], "search_reloc match")
+    bp.check_counts(get_n(), [n for n, _ in refs], "search_reloc")
