@@ -12,6 +12,7 @@
 #include "orb_device.h"
 #include "plvi_common.h"
 #include "plvi_math.h"
+#include "orb_xtab.h"
 
 namespace plvi {
 
@@ -22,6 +23,24 @@ __device__ __forceinline__ int reflect1(int p, int len) {
     return max(p, 0);
 }
 
+__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {  // any alignment (gfx950 unaligned access)
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+__device__ __forceinline__ void st_u32(uint8_t* p, uint32_t v) {
+    __builtin_memcpy(p, &v, 4);
+}
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u16x2 as_u16x2(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
+__device__ __forceinline__ uint32_t as_u32(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
+__device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c) {  // a.lo*b.lo + a.hi*b.hi + c
+    return __builtin_amdgcn_udot2(as_u16x2(a), as_u16x2(b), c, false);
+}
 
 // ---------------------------------------------------------------------------
 // K1a: ComputePyramid (ORBextractor.cc:1152-1177): levels 1..L-1, chained
@@ -34,7 +53,10 @@ __device__ __forceinline__ int reflect1(int p, int len) {
 //     yields the (at most one: scale > 1) next row of the level above it,
 //     cascading through the levels; each level keeps its last two rows in
 //     LDS, and every level row is written to HBM once -- no intermediate
-//     HBM round trip.
+//     HBM round trip.  A lane makes four consecutive output pixels at a
+//     time (pyr_quad below): one 16-byte read of their column entries, three
+//     aligned dwords of each source row, one dword store to HBM and one to
+//     the level's LDS row.
 // Waves hand rows over through per-frame LDS counters (rows loaded / rows
 // consumed) and s_sleep polling, never a workgroup barrier: a resizer issues
 // only stores and LDS traffic, so nothing in its loop waits for memory.
@@ -48,12 +70,9 @@ __device__ __forceinline__ int reflect1(int p, int len) {
 #ifndef PLVI_PYR_FRAMES
 #define PLVI_PYR_FRAMES 4
 #endif
-constexpr int kPyrAhead = 2, kPyrDw = 4, kPyrRing = 4, kPyrUnroll = 4, kPyrFrames = PLVI_PYR_FRAMES;
+// kPyrUnroll: quads per lane and pass of the resizer (64 * 4 * kPyrUnroll columns), all reads issued first
+constexpr int kPyrAhead = 2, kPyrDw = 4, kPyrRing = 4, kPyrUnroll = 2, kPyrFrames = PLVI_PYR_FRAMES;
 
-// packed column entry: sx (10 bits) | a0 (12 bits) << 10 | (a0 + a1 - 2047) (2 bits) << 22 | clampR << 24
-__host__ __device__ inline uint32_t pyr_xtab_pack(int sx, int a0, int a1, bool clampR) {
-    return (uint32_t)sx | ((uint32_t)a0 << 10) | ((uint32_t)(a0 + a1 - 2047) << 22) | ((uint32_t)clampR << 24);
-}
 // A level that is exactly half of its source in both axes takes cv::resize's
 // INTER_AREA fast path (resize.cpp: is_area_fast, iscale 2).  Its vector body
 // is (s + 2) >> 2 of the 2 x 2 sum s -- what the bilinear formula gives at
@@ -62,8 +81,135 @@ __host__ __device__ inline uint32_t pyr_xtab_pack(int sx, int a0, int a1, bool c
 // host marks those columns (append_xtab) and launches the *_area pyramid
 // kernels (end of this file) for such a level; the plain kernels never test
 // the bit.
-constexpr uint32_t kPyrXtabAreaTail = 1u << 25;
 __device__ __forceinline__ int pyr_area_tail(unsigned s) { return (int)((s + 1 + ((s >> 2) & 1)) >> 2); }
+// (kPyrXtabAreaTail, kPyrXtabWide and the entry packing: orb_xtab.h)
+typedef uint32_t pyr_u32x4 __attribute__((ext_vector_type(4)));
+typedef pyr_u32x4 __attribute__((address_space(3))) lds_pyr_u32x4;
+
+// The vertical pass and the rounding of one pixel from its two horizontal
+// sums: the 8U specialisation (default) or the generic fixed-point cast (A.1
+// switch); s = the 2 x 2 sum of the taps, for the area tail.
+template <bool kArea, bool kGeneric>
+__device__ __forceinline__ uint32_t pyr_vert(uint32_t e, unsigned h0, unsigned h1, unsigned s, unsigned b0,
+                                             unsigned b1) {
+    int v;
+    if (!kGeneric)
+        v = (int)(((__umul24(b0, h0 >> 4) >> 16) + (__umul24(b1, h1 >> 4) >> 16) + 2) >> 2);
+    else
+        v = min((int)((b0 * h0 + b1 * h1 + (1u << 21)) >> 22), 255);
+    if (kArea && (e & kPyrXtabAreaTail)) v = pyr_area_tail(s);
+    return (uint32_t)v & 255u;
+}
+// Four output pixels, each from its own four byte-wide taps: the per-pixel
+// path of a kPyrXtabWide level.  S0 / S1: the two source rows, global or LDS.
+template <bool kArea, bool kGeneric, class Row>
+__device__ __forceinline__ uint32_t pyr_quad_pixels(const uint32_t (&e)[4], Row S0, Row S1, unsigned b0, unsigned b1) {
+    uint32_t out = 0;
+#pragma nounroll
+    for (int u = 0; u < 4; ++u) {
+        const int sx = e[u] & 1023, sx1 = (e[u] >> 24) & 1 ? sx : sx + 1;
+        const unsigned p00 = S0[sx], p01 = S0[sx1], p10 = S1[sx], p11 = S1[sx1];
+        const unsigned a0 = (e[u] >> 10) & 4095, a1 = 2047u - a0 + ((e[u] >> 22) & 3);
+        const unsigned h0 = __umul24(p00, a0) + __umul24(p01, a1);
+        const unsigned h1 = __umul24(p10, a0) + __umul24(p11, a1);
+        out |= pyr_vert<kArea, kGeneric>(e[u], h0, h1, p00 + p01 + p10 + p11, b0, b1) << (8 * u);
+    }
+    return out;
+}
+// Four consecutive output pixels (entries e[0..3]) as one dword, shared by the
+// two pyramid builders.  lo / hi: the 8 bytes of source row 0 / 1 that start at
+// column sxb, sxb <= every sx of the quad and sx + 1 - sxb <= 7 for every
+// column that is not clampR.  A pixel's two taps are picked out of the window
+// as a pair of 16-bit fields (v_perm_b32: selector 0x0c is a zero byte) and
+// meet the pair (a0, a1) in one v_dot2_u32_u16: exact integers, the same sums.
+// Both selectors come from one multiply-add: sx * 0x10001 + (0x0c010c00 -
+// sxb * 0x10001) is (sx - sxb) | 0x0c00 in the low half and (sx + 1 - sxb) |
+// 0x0c00 in the high one.  A clampR column may have sx + 1 - sxb = 8, which
+// selects a sign byte (0x00 or 0xff) instead of a tap; its a1 = 0 drops it.
+template <bool kArea, bool kGeneric>
+__device__ __forceinline__ uint32_t pyr_quad(const uint32_t (&e)[4], unsigned sxb, uint32_t lo0, uint32_t hi0,
+                                             uint32_t lo1, uint32_t hi1, unsigned b0, unsigned b1) {
+    uint32_t out = 0;
+    const uint32_t selb = 0x0c010c00u - sxb * 0x10001u;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const uint32_t sel = __umul24(e[u] & 1023u, 0x10001u) + selb;
+        const uint32_t s0 = __builtin_amdgcn_perm(hi0, lo0, sel), s1 = __builtin_amdgcn_perm(hi1, lo1, sel);
+        const unsigned a0 = (e[u] >> 10) & 4095, a1 = 2047u - a0 + ((e[u] >> 22) & 3);
+        const uint32_t a = a0 | (a1 << 16);
+        const uint32_t t = s0 + s1;  // per 16-bit field <= 510
+        out |= pyr_vert<kArea, kGeneric>(e[u], udot2(s0, a, 0u), udot2(s1, a, 0u), (t & 0xffffu) + (t >> 16), b0, b1)
+               << (8 * u);
+    }
+    return out;
+}
+// A quad's store to a row packed at pitch w in HBM.  The bytes after column
+// w - 1 are the next row, the next frame's plane, the next level's region or
+// the end of the allocation, and another wave may write them at any time: only
+// a whole quad is one dword store (any alignment: gfx950 unaligned access),
+// the row's last, partial quad goes bytewise.
+__device__ __forceinline__ void pyr_store_quad(uint8_t* D, int x, int w, uint32_t pk) {
+    if (x + 3 < w) {
+        st_u32(D + x, pk);
+    } else {
+        D[x] = (uint8_t)pk;
+        if (x + 1 < w) D[x + 1] = (uint8_t)(pk >> 8);
+        if (x + 2 < w) D[x + 2] = (uint8_t)(pk >> 16);
+    }
+}
+// One output row of the streaming builder's resizer wave: kPyrUnroll quads per
+// lane and pass, all LDS reads issued before the first use.  A quad's taps lie
+// in the 8 bytes from its first sx on: three aligned dwords per source row
+// (indices held inside the row -- sdl is its last dword -- since a dword past
+// it holds no tap), shifted to that byte.  R: the level's own LDS row (pitch
+// (w + 3) & ~3, so the quad always fits) or null for the last level.
+template <bool kArea, bool kGeneric>
+__device__ __forceinline__ void pyr_row_quads(const lds_u32* T, const lds_u8* S0, const lds_u8* S1, int sdl, uint8_t* D,
+                                              lds_u8* R, int w, int lane, unsigned b0, unsigned b1) {
+    const lds_u32* S0w = (const lds_u32*)S0;
+    const lds_u32* S1w = (const lds_u32*)S1;
+    for (int x0 = 0; x0 < w; x0 += 256 * kPyrUnroll) {
+        uint32_t e[kPyrUnroll][4], d0[kPyrUnroll][3], d1[kPyrUnroll][3];
+#pragma unroll
+        for (int u = 0; u < kPyrUnroll; ++u) {
+            const int x = x0 + 256 * u + 4 * lane;
+            const pyr_u32x4 q = x < w ? *(const lds_pyr_u32x4*)(T + x) : pyr_u32x4{0u, 0u, 0u, 0u};
+            e[u][0] = q.x, e[u][1] = q.y, e[u][2] = q.z, e[u][3] = q.w;
+        }
+#pragma unroll
+        for (int u = 0; u < kPyrUnroll; ++u) {
+            const int i0 = (int)(e[u][0] & 1023u) >> 2;
+            const int i1 = min(i0 + 1, sdl), i2 = min(i0 + 2, sdl);
+            d0[u][0] = S0w[i0], d0[u][1] = S0w[i1], d0[u][2] = S0w[i2];
+            d1[u][0] = S1w[i0], d1[u][1] = S1w[i1], d1[u][2] = S1w[i2];
+        }
+#pragma unroll
+        for (int u = 0; u < kPyrUnroll; ++u) {
+            const int x = x0 + 256 * u + 4 * lane;
+            if (x >= w) break;
+            const unsigned sx0 = e[u][0] & 1023u, o = sx0 & 3u;
+            const uint32_t pk = pyr_quad<kArea, kGeneric>(e[u], sx0, __builtin_amdgcn_alignbyte(d0[u][1], d0[u][0], o),
+                                                          __builtin_amdgcn_alignbyte(d0[u][2], d0[u][1], o),
+                                                          __builtin_amdgcn_alignbyte(d1[u][1], d1[u][0], o),
+                                                          __builtin_amdgcn_alignbyte(d1[u][2], d1[u][1], o), b0, b1);
+            pyr_store_quad(D, x, w, pk);
+            if (R) *(lds_u32*)(R + x) = pk;
+        }
+    }
+}
+// The same row of a kPyrXtabWide level, pixel by pixel.
+template <bool kArea>
+__device__ __forceinline__ void pyr_row_pixels(const lds_u32* T, const lds_u8* S0, const lds_u8* S1, uint8_t* D,
+                                               lds_u8* R, int w, int lane, unsigned b0, unsigned b1, int generic) {
+    for (int x = 4 * lane; x < w; x += 256) {
+        const pyr_u32x4 q = *(const lds_pyr_u32x4*)(T + x);
+        const uint32_t e[4] = {q.x, q.y, q.z, q.w};
+        const uint32_t pk = generic ? pyr_quad_pixels<kArea, true>(e, S0, S1, b0, b1)
+                                    : pyr_quad_pixels<kArea, false>(e, S0, S1, b0, b1);
+        pyr_store_quad(D, x, w, pk);
+        if (R) *(lds_u32*)(R + x) = pk;
+    }
+}
 
 // Loader -> resizer hand-off of the pyramid kernel's LDS row ring, inside the
 // HIP memory model: the producing wave makes all its lanes' row writes
@@ -148,25 +294,7 @@ __device__ __forceinline__ int lane_from_right(int v) {  // lane i <- lane i+1 (
 __device__ __forceinline__ int orb_mbcnt(unsigned long long m) {  // set bits of m below this lane
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {  // any alignment (gfx950 unaligned access)
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-__device__ __forceinline__ void st_u32(uint8_t* p, uint32_t v) {
-    __builtin_memcpy(p, &v, 4);
-}
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
 __device__ __forceinline__ int byte_of(uint32_t v, int j) { return (int)((v >> (8 * j)) & 255u); }
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u16x2 as_u16x2(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
-__device__ __forceinline__ uint32_t as_u32(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c) {  // a.lo*b.lo + a.hi*b.hi + c
-    return __builtin_amdgcn_udot2(as_u16x2(a), as_u16x2(b), c, false);
-}
 
 __device__ __forceinline__ int fast_S_ring(const uint8_t (*rg)[kRingW], int y, int c) {
 #define RG(dy, dx) ((int)rg[(y + (dy)) & (kRingRows - 1)][c + (dx)])

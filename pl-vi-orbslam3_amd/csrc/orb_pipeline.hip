@@ -14,39 +14,9 @@
 #include "orb_device.h"
 #include "plvi_common.h"
 #include "orb_kernels.hpp"
+#include "orb_xtab.h"
 
 namespace plvi {
-
-static inline int cv_round_h(float v) { return (int)lrintf(v); }
-static inline int cv_round_h(double v) { return (int)lrint(v); }
-static inline int cv_floor_h(float v) { int i = (int)v; return i - (i > v); }
-static inline int cv_ceil_h(float v) { int i = (int)v; return i + (i < v); }
-
-// cv::resize INTER_LINEAR 8U column coefficients (imgproc/src/resize.cpp,
-// OpenCV 4.2: scale_x = 1/inv_scale_x, fx = (float)((dx+0.5)*scale_x-0.5),
-// sx = cvFloor(fx), border clamps, cvRound(... * INTER_RESIZE_COEF_SCALE)),
-// packed for orb_pyramid_kernel; dx >= xmax columns use S[sx] * 2048 only.
-// `area` (the level is exactly half of its source in both axes, so cv::resize
-// takes the INTER_AREA fast path): columns of ResizeAreaFastVec_SIMD_8u's
-// scalar tail, dx >= (sw / 2 / 8) * 8, carry kPyrXtabAreaTail; every other
-// column of such a level has sx = 2 dx, a0 = a1 = 1024, the same result.
-static int append_xtab(std::vector<uint32_t>& tab, int sw, int dw, bool area) {
-    const double scale_x = 1. / ((double)dw / sw);
-    const int tail0 = area ? (sw / 2 / 8) * 8 : dw;
-    for (int dx = 0; dx < dw; ++dx) {
-        float fx = (float)((dx + 0.5) * scale_x - 0.5);
-        int sx = cv_floor_h(fx);
-        fx -= sx;
-        if (sx < 0) { fx = 0; sx = 0; }
-        const bool clampR = sx + 1 >= sw;
-        if (clampR && sx >= sw - 1) { fx = 0; sx = sw - 1; }
-        const int a0 = cv_round_h((1.f - fx) * 2048), a1 = cv_round_h(fx * 2048);
-        if (sx > 1023 || a0 + a1 < 2047 || a0 + a1 > 2049) return PLVI_E_BADARG;
-        if (area && (sx != 2 * dx || a0 != 1024 || a1 != 1024 || clampR)) return PLVI_E_BADARG;
-        tab.push_back(pyr_xtab_pack(sx, a0, a1, clampR) | (dx >= tail0 ? kPyrXtabAreaTail : 0u));
-    }
-    return PLVI_OK;
-}
 
 // Split [0, n) into the fewest pieces whose interior cuts are taken from
 // `cand` (ascending) and that all satisfy fits(a, b), as even as possible:
@@ -110,8 +80,11 @@ struct OrbPipeline {
     size_t octSmem = 0;   // orb_octree_kernel dynamic LDS
     // batches of at most this many frames build the pyramid level by level
     // (orb_resize_level_kernel, one launch per level) instead of streaming it
-    // (PLVI_PYR_LEVELWISE overrides)
-    int pyrLevelwiseMax = 1024;
+    // (PLVI_PYR_LEVELWISE overrides).  With four pixels per thread the level
+    // launches are the faster builder at every batch measured, 1 to 3072 frames
+    // (2.36 against 3.88 ms alone at 3072), at 1.6 times the
+    // streaming kernel's memory traffic; larger batches are unmeasured and stream.
+    int pyrLevelwiseMax = 3072;
     int lastFrames = 0;
     // Level 0 of the pyramid (mvImagePyramid[0]) is the input frame itself.
     // When the batch's rows are packed (row stride = width) it stays a view of
@@ -388,7 +361,11 @@ struct OrbPipeline {
         xtabN = (int)xtab.size();
         pyrFrameLds = (int)((pyrSmem + 15) & ~size_t(15));
         pyrSmem = 4 * (size_t)xtabN + (size_t)kPyrFrames * pyrFrameLds;
-        if (W > 4 * 64 * kPyrDw || pyrSmem > 64 * 1024) return PLVI_E_BADARG;  // orb_pyramid_kernel limits
+        // orb_pyramid_kernel limits: the loader's row registers, and 64 KB of LDS
+        // for the dynamic part above plus the kernel's own static arrays
+        hipFuncAttributes pyrAttr{};
+        PLVI_CHECK(hipFuncGetAttributes(&pyrAttr, (const void*)(pyrHasArea ? orb_pyramid_area_kernel : orb_pyramid_kernel)));
+        if (W > 4 * 64 * kPyrDw || pyrSmem + pyrAttr.sharedSizeBytes > 64 * 1024) return PLVI_E_BADARG;
         if (xtab.empty()) xtab.push_back(0);
         if (d_xtab.alloc(4 * xtab.size())) return PLVI_E_HIP;
         PLVI_CHECK(hipMemcpy(d_xtab.p, xtab.data(), 4 * xtab.size(), hipMemcpyHostToDevice));
@@ -444,11 +421,15 @@ struct OrbPipeline {
                     const OrbLevelDev& d = lv[l];
                     const uint8_t* src = l == 1 ? d_frames : P + s.off;
                     const size_t sfr = l == 1 ? frame_stride : (size_t)s.plane, srow = l == 1 ? row_stride : (size_t)s.w;
-                    const int items = ((d.w + 3) >> 2) * d.h;
+                    const int qpr = (d.w + 3) >> 2, items = qpr * d.h;
+                    // the kernel's row of item i is (i * qinv) >> 32 = i / qpr: qinv * qpr - 2^32 < qpr, and
+                    // items * qpr < 2^32 (w <= 2080, h <= 1056 by the region limits above)
+                    const uint32_t qinv = (uint32_t)(((1ull << 32) + qpr - 1) / qpr);
+                    if (qpr < 2 || (unsigned long long)items * qpr >= (1ull << 32)) return PLVI_E_BADARG;
                     auto* resizeK = areaLevel[l] ? orb_resize_level_area_kernel : orb_resize_level_kernel;
                     hipLaunchKernelGGL(resizeK, dim3((items + 255) / 256, nf), dim3(256), 0, st, src, sfr,
                                        srow, s.w, s.h, P + d.off, (size_t)d.plane, d.w, d.h, d.rsy,
-                                       (const uint32_t*)d_xtab.as<uint32_t>() + d.xtab, resizeGeneric);
+                                       (const uint32_t*)d_xtab.as<uint32_t>() + d.xtab, resizeGeneric, qinv);
                 }
             } else {
                 auto* pyrK = pyrHasArea ? orb_pyramid_area_kernel : orb_pyramid_kernel;

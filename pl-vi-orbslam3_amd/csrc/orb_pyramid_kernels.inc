@@ -2,17 +2,20 @@
 // orb_kernels.hpp: PLVI_PYR_AREA 0 defines orb_pyramid_kernel /
 // orb_resize_level_kernel where they always stood, PLVI_PYR_AREA 1 the
 // *_area kernels of exact-half levels (kPyrXtabAreaTail) after the last
-// kernel of the file.  Plain textual inclusion, so the default kernels are
-// compiled from the same text in the same place as before the area path
-// existed: same instructions, same position in the code object.
+// kernel of the file.  Plain textual inclusion, so both variants come from
+// one text; the pixel arithmetic itself (pyr_quad, pyr_row_quads,
+// pyr_store_quad) is shared by the two builders and lives in orb_kernels.hpp.
 __global__ __launch_bounds__(64 * (kPyrFrames + 1)) __attribute__((amdgpu_waves_per_eu(PLVI_PYR_WPE))) void PLVI_PYR_KERNEL(
     const OrbLevelDev* __restrict__ lvs, int L, const uint8_t* __restrict__ frames, size_t f_frame, size_t f_row,
     int nf, uint8_t* __restrict__ pyr, const uint32_t* __restrict__ xtab, int xtab_n, int frame_lds, int generic) {
     PLVI_ORB_PRIO_SET();
     extern __shared__ __align__(16) uint8_t lds_pyr_g[];
     __shared__ int s_w[kOrbMaxLevels], s_h[kOrbMaxLevels], s_roff[kOrbMaxLevels], s_xoff[kOrbMaxLevels];
+    __shared__ int s_wide[kOrbMaxLevels];  // the level's quads do not fit the 8-byte tap window (kPyrXtabWide)
     __shared__ double s_sy[kOrbMaxLevels];
     __shared__ int s_cnt[2 * kPyrFrames];  // per frame: rows loaded, rows consumed
+    __shared__ uint8_t* s_dbase[kPyrFrames][kOrbMaxLevels];  // per resizer wave: its frame's level planes
+    __shared__ int s_prod[kPyrFrames][kOrbMaxLevels];        // and the rows it has produced per level
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform: scalar role / frame
     const int f0 = blockIdx.x * kPyrFrames;
     const int nfw = min(kPyrFrames, nf - f0);  // frames of this workgroup
@@ -22,6 +25,7 @@ __global__ __launch_bounds__(64 * (kPyrFrames + 1)) __attribute__((amdgpu_waves_
         s_h[threadIdx.x] = lvs[threadIdx.x].h;
         s_sy[threadIdx.x] = lvs[threadIdx.x].rsy;
         s_xoff[threadIdx.x] = lvs[threadIdx.x].xtab;
+        s_wide[threadIdx.x] = threadIdx.x > 0 && (xtab[lvs[threadIdx.x].xtab] & kPyrXtabWide);
     }
     if (threadIdx.x == 0) {
         int o = kPyrRing * ((lvs[0].w + 3) & ~3);  // level-0 ring first
@@ -96,14 +100,14 @@ __global__ __launch_bounds__(64 * (kPyrFrames + 1)) __attribute__((amdgpu_waves_
     lds_u8* lds_pyr = fbase + (size_t)k * frame_lds;
     lds_i32* s_loaded = (lds_i32*)&s_cnt[2 * k];
     lds_i32* s_consumed = (lds_i32*)&s_cnt[2 * k + 1];
-    // this frame's level planes (no global parameter loads inside the row loop)
-    uint8_t* dbase[kOrbMaxLevels];
-#pragma unroll
-    for (int l = 0; l < kOrbMaxLevels; ++l)
-        dbase[l] = l < L ? pyr + lvs[l].off + (size_t)f * lvs[l].plane : nullptr;
-    int prod[kOrbMaxLevels];
-#pragma unroll
-    for (int l = 0; l < kOrbMaxLevels; ++l) prod[l] = 0;
+    // this frame's level planes and rows produced per level: in LDS, written and
+    // read by this wave alone (registers indexed by the level cost a 16-way
+    // select per visit; no global parameter loads inside the row loop)
+    if (lane < kOrbMaxLevels) {
+        s_dbase[k][lane] = lane < L ? pyr + lvs[lane].off + (size_t)f * lvs[lane].plane : nullptr;
+        s_prod[k][lane] = 0;
+    }
+    wave_sync();
     for (int r = 0; r < H0; ++r) {
         while (lds_load_acquire(s_loaded) <= r) __builtin_amdgcn_s_sleep(1);
         int avail = r + 1;  // rows of the source level available
@@ -113,7 +117,7 @@ __global__ __launch_bounds__(64 * (kPyrFrames + 1)) __attribute__((amdgpu_waves_
             const int sring = l == 1 ? kPyrRing : 2;
             const double scy = s_sy[l];
             const lds_u32* T = ltab + s_xoff[l];
-            int y = prod[l];
+            int y = __builtin_amdgcn_readfirstlane(s_prod[k][l]);
             const int y_start = y;
             while (y < h) {
                 float fy = (float)((y + 0.5) * scy - 0.5);
@@ -127,53 +131,22 @@ __global__ __launch_bounds__(64 * (kPyrFrames + 1)) __attribute__((amdgpu_waves_
                                b1 = (unsigned)__builtin_rintf(fy * 2048);
                 const lds_u8* S0 = lds_pyr + s_roff[l - 1] + (r0 % sring) * spitch;
                 const lds_u8* S1 = lds_pyr + s_roff[l - 1] + (r1 % sring) * spitch;
-                uint8_t* D = dbase[l] + (size_t)y * w;
+                uint8_t* D = s_dbase[k][l] + (size_t)y * w;
                 lds_u8* R = l < L - 1 ? lds_pyr + s_roff[l] + (y & 1) * pitch : nullptr;
-                for (int x0 = 0; x0 < w; x0 += 64 * kPyrUnroll) {
-                    // kPyrUnroll columns per lane: all LDS reads issued before the first use
-                    uint32_t e[kPyrUnroll];
-                    unsigned p00[kPyrUnroll], p01[kPyrUnroll], p10[kPyrUnroll], p11[kPyrUnroll];
-#pragma unroll
-                    for (int u = 0; u < kPyrUnroll; ++u) {
-                        const int x = x0 + 64 * u + lane;
-                        e[u] = x < w ? T[x] : 0u;
-                    }
-#pragma unroll
-                    for (int u = 0; u < kPyrUnroll; ++u) {
-                        const int sx = e[u] & 1023;
-                        const int sx1 = (e[u] >> 24) & 1 ? sx : sx + 1;
-                        p00[u] = S0[sx];
-                        p01[u] = S0[sx1];
-                        p10[u] = S1[sx];
-                        p11[u] = S1[sx1];
-                    }
-#pragma unroll
-                    for (int u = 0; u < kPyrUnroll; ++u) {
-                        const int x = x0 + 64 * u + lane;
-                        if (x >= w) break;
-                        const bool cr = (e[u] >> 24) & 1;
-                        // right-border column: H = S[sx] * 2048 (a0 = 2048, a1 = 0)
-                        const unsigned a0 = cr ? 2048u : (e[u] >> 10) & 4095;
-                        const unsigned a1 = cr ? 0u : 2047u - ((e[u] >> 10) & 4095) + ((e[u] >> 22) & 3);
-                        const unsigned h0 = __umul24(p00[u], a0) + __umul24(p01[u], a1);
-                        const unsigned h1 = __umul24(p10[u], a0) + __umul24(p11[u], a1);
-                        // 8U specialisation (default) or the generic fixed-point cast (A.1 switch)
-                        int v;
-                        if (!generic)
-                            v = (int)(((__umul24(b0, h0 >> 4) >> 16) + (__umul24(b1, h1 >> 4) >> 16) + 2) >> 2);
-                        else
-                            v = min((int)((b0 * h0 + b1 * h1 + (1u << 21)) >> 22), 255);
-                        if (PLVI_PYR_AREA && (e[u] & kPyrXtabAreaTail)) v = pyr_area_tail(p00[u] + p01[u] + p10[u] + p11[u]);
-                        D[x] = (uint8_t)v;
-                        if (R) R[x] = (uint8_t)v;
-                    }
-                }
+                // four consecutive pixels per lane (pyr_row_quads, orb_kernels.hpp); the
+                // row's last quad never stores past column w - 1 in HBM (pyr_store_quad)
+                if (s_wide[l])
+                    pyr_row_pixels<PLVI_PYR_AREA>(T, S0, S1, D, R, w, lane, b0, b1, generic);
+                else if (generic)
+                    pyr_row_quads<PLVI_PYR_AREA, true>(T, S0, S1, (spitch >> 2) - 1, D, R, w, lane, b0, b1);
+                else
+                    pyr_row_quads<PLVI_PYR_AREA, false>(T, S0, S1, (spitch >> 2) - 1, D, R, w, lane, b0, b1);
                 ++y;
                 // one wave: its LDS row writes precede the next level's reads in
                 // program order (compiler ordering point only)
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             }
-            prod[l] = y;
+            if (lane == 0) s_prod[k][l] = y;
             if (y == y_start) break;  // nothing new at level l: deeper levels have no new source rows
             avail = y;
         }
@@ -185,21 +158,23 @@ __global__ __launch_bounds__(64 * (kPyrFrames + 1)) __attribute__((amdgpu_waves_
 // K1a', small batches: one launch per level (level l from level l-1 in HBM /
 // L2), thread = 4 consecutive output pixels of one row, the whole chip on
 // every level.  The streaming kernel above runs one resizer wave per frame
-// through all 7 chained levels: at one frame that is a 2.6 ms serial chain
-// for 1.6 MB (DESIGN.md §4).  Same arithmetic, same packed column table,
-// same 8U / generic switch.  Level 1 reads the caller's frames (level 0's
+// through all 7 chained levels: at one frame that is a 2.3 ms serial chain
+// for 1.6 MB (DESIGN.md §4).  Same quad routine (pyr_quad), same packed
+// column table, same 8U / generic switch.  Level 1 reads the caller's frames (level 0's
 // plane is written later by orb_blur_fast_kernel).
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void PLVI_RESIZE_KERNEL(const uint8_t* __restrict__ src, size_t s_frame,
                                                                size_t s_row, int sw, int sh, uint8_t* __restrict__ dst,
                                                                size_t d_frame, int w, int h, double scy,
-                                                               const uint32_t* __restrict__ T, int generic) {
+                                                               const uint32_t* __restrict__ T, int generic,
+                                                               uint32_t qinv) {
     PLVI_ORB_PRIO_SET();
     const int qpr = (w + 3) >> 2;  // quads per row
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= qpr * h) return;
     const int f = blockIdx.y;
-    const int y = i / qpr, x0 = (i - y * qpr) * 4;
+    // i / qpr by the host's qinv = ceil(2^32 / qpr): exact while i * (qinv * qpr - 2^32) < 2^32 (pyr_qinv)
+    const int y = (int)__umulhi((uint32_t)i, qinv), x0 = (i - y * qpr) * 4;
     float fy = (float)((y + 0.5) * scy - 0.5);
     int sy = (int)fy;
     sy -= (sy > fy);
@@ -209,33 +184,21 @@ __global__ __launch_bounds__(256) void PLVI_RESIZE_KERNEL(const uint8_t* __restr
     const uint8_t* S0 = src + (size_t)f * s_frame + (size_t)r0 * s_row;
     const uint8_t* S1 = src + (size_t)f * s_frame + (size_t)r1 * s_row;
     uint8_t* D = dst + (size_t)f * d_frame + (size_t)y * w;
-    uint32_t e[4];
-    unsigned p00[4], p01[4], p10[4], p11[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) e[u] = x0 + u < w ? T[x0 + u] : T[x0];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int sx = e[u] & 1023;
-        const int sx1 = (e[u] >> 24) & 1 ? sx : sx + 1;
-        p00[u] = S0[sx];
-        p01[u] = S0[sx1];
-        p10[u] = S1[sx];
-        p11[u] = S1[sx1];
+    // the level's entries are padded to whole quads and start 16-byte aligned
+    const pyr_u32x4 q = *reinterpret_cast<const pyr_u32x4*>(T + x0);
+    const uint32_t e[4] = {q.x, q.y, q.z, q.w};
+    uint32_t pk;
+    if (e[0] & kPyrXtabWide) {
+        pk = generic ? pyr_quad_pixels<PLVI_PYR_AREA, true>(e, S0, S1, b0, b1)
+                     : pyr_quad_pixels<PLVI_PYR_AREA, false>(e, S0, S1, b0, b1);
+    } else {
+        // the quad's taps lie in the 8 bytes from its first sx on; the window is
+        // held inside the source row (sw >= 8: append_xtab), which keeps every tap
+        const int sxb = min((int)(e[0] & 1023u), sw - 8);
+        const uint32_t lo0 = ld_u32(S0 + sxb), hi0 = ld_u32(S0 + sxb + 4), lo1 = ld_u32(S1 + sxb),
+                       hi1 = ld_u32(S1 + sxb + 4);
+        pk = generic ? pyr_quad<PLVI_PYR_AREA, true>(e, (unsigned)sxb, lo0, hi0, lo1, hi1, b0, b1)
+                     : pyr_quad<PLVI_PYR_AREA, false>(e, (unsigned)sxb, lo0, hi0, lo1, hi1, b0, b1);
     }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        if (x0 + u >= w) break;
-        const bool cr = (e[u] >> 24) & 1;
-        const unsigned a0 = cr ? 2048u : (e[u] >> 10) & 4095;
-        const unsigned a1 = cr ? 0u : 2047u - ((e[u] >> 10) & 4095) + ((e[u] >> 22) & 3);
-        const unsigned h0 = __umul24(p00[u], a0) + __umul24(p01[u], a1);
-        const unsigned h1 = __umul24(p10[u], a0) + __umul24(p11[u], a1);
-        int v;
-        if (!generic)
-            v = (int)(((__umul24(b0, h0 >> 4) >> 16) + (__umul24(b1, h1 >> 4) >> 16) + 2) >> 2);
-        else
-            v = min((int)((b0 * h0 + b1 * h1 + (1u << 21)) >> 22), 255);
-        if (PLVI_PYR_AREA && (e[u] & kPyrXtabAreaTail)) v = pyr_area_tail(p00[u] + p01[u] + p10[u] + p11[u]);
-        D[x0 + u] = (uint8_t)v;
-    }
+    pyr_store_quad(D, x0, w, pk);  // the row's last quad never stores past column w - 1
 }
