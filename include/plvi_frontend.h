@@ -265,13 +265,21 @@ int plvi_lines_debug_planes(plvi_line_extractor* h, int frame, int octave, float
 /* Diagnostic: LBD Sobel plane of the last batch for one (frame, octave),
  * interleaved int16 (dx, dy) per pixel, copied to host; dxdy may be NULL. */
 int plvi_lines_debug_sobel(plvi_line_extractor* h, int frame, int octave, short* dxdy, int* w, int* hgt);
+/* Diagnostic: region2rect's segments of the last batch for one (frame,
+ * octave): one (x1, y1, x2, y2) float quadruple per region kept by region
+ * growing, in region order, before any length filter (what
+ * LineSegmentDetectorImpl::detect returns), copied to host.  *n = the count;
+ * PLVI_E_CAPACITY when it exceeds cap (nothing copied); out may be NULL. */
+int plvi_lines_debug_raw_lines(plvi_line_extractor* h, int frame, int octave, float* out, int cap, int* n);
 int plvi_lines_profile_read(plvi_line_extractor* h, float* stage_ms, int* runs);
 /* Per-launch timing of lsd_prep_kernel (bench.py's LSD-pass roofline), one
  * launch per octave: as plvi_orb_kernel_timing / _read. */
 int plvi_lines_kernel_timing(plvi_line_extractor* h, int enable);
 int plvi_lines_kernel_timing_read(plvi_line_extractor* h, float* total_ms, int* launches);
 /* The same timing per kernel kind: 0 = lsd_prep_kernel, 1 = lbd_sobel0_kernel
- * (octave-0 5x5 blur + Sobel), 2 = lbd_sobel1_kernel (pyrDown + Sobel). */
+ * (octave-0 5x5 blur + Sobel), 2 = lbd_sobel1_kernel (pyrDown + Sobel),
+ * 3 = lsd_rect_lanes_kernel (region2rect; one launch for all octaves, or one
+ * per stream where octave 0 grows beside the others). */
 int plvi_lines_kernel_timing_read_kind(plvi_line_extractor* h, int kind, float* total_ms, int* launches);
 
 /* ------------------------------------------------------------------ Hamming

@@ -806,22 +806,153 @@ __global__ __launch_bounds__(64 * kGrowWaves, PLVI_GROW_WPE) void lsd_grow_kerne
 // lsd.cpp:697-744, :755-771): the identical sequence of double operations per
 // region -- including the nine multiply-adds lsd.cpp.o fuses (x / y sums,
 // Ixx / Iyy / Ixy, the eigenvalue root, l, the endpoints) -- with no LDS
-// round trip and no idle lanes behind a serial lane 0.  Points and
-// weights are fetched kRectU at a time so each lane keeps several loads in
-// flight; regions of one wave are consecutive indices of one (frame, octave).
+// round trip and no idle lanes behind a serial lane 0.  Regions of one wave
+// are consecutive indices of one (frame, octave).
+//
+// Weights: a workgroup first stages the modgrad value of every point of its
+// 256 regions -- one contiguous range of the task's point list, since region
+// growing appends regions back to back -- into a weights array indexed like
+// the point list: lanes = consecutive points of one region's patch, so a load
+// touches a few sectors and every weight is gathered once.  The two weighted
+// passes then stream W[start + i] beside the points.  PLVI_RECT_STAGE=0
+// builds the earlier kernel, whose lanes gather from the modgrad plane in
+// both passes (one sector per lane and load).
 // ---------------------------------------------------------------------------
+#ifndef PLVI_RECT_STAGE
+#define PLVI_RECT_STAGE 1
+#endif
 #ifndef PLVI_RECT_LANE_BLOCKS
 #define PLVI_RECT_LANE_BLOCKS 2
 #endif
-constexpr int kRectLaneBlocks = PLVI_RECT_LANE_BLOCKS;  // 4-wave workgroups per (octave, frame), 256 regions each
-// points fetched per group: 4 above kRectSmallNf frames (throughput, 64
-// VGPRs); 16 for small batches, where the longest region's three serial
-// passes are the launch (104 VGPRs; batch 64 7.97 -> 7.91 ms,
-// profiles/r05/latency_ab.txt)
-constexpr int kRectU = 4;
-constexpr int kRectUSmall = 16;
+#ifndef PLVI_RECT_LANE_BLOCKS_LARGE
+#define PLVI_RECT_LANE_BLOCKS_LARGE (PLVI_RECT_STAGE ? 1 : 2)
+#endif
+#ifndef PLVI_RECT_U
+#define PLVI_RECT_U (PLVI_RECT_STAGE ? 8 : 4)
+#endif
+#ifndef PLVI_RECT_U_SMALL
+#define PLVI_RECT_U_SMALL 16
+#endif
+constexpr bool kRectStage = PLVI_RECT_STAGE != 0;
+// 4-wave workgroups per (octave, frame), each taking 256 regions at a time
+// (8 up to 16 frames, lines_pipeline.hip).  From kRectLargeNf frames on one
+// workgroup takes the whole task: with the weights staged, two were 2.76 and
+// one 2.37 ms at 3072 frames, 0.98 and 0.85 ms at 1024; at 256 frames two are
+// faster, 0.34 against 0.38 ms (profiles/r08/rect_probe_variants.txt)
+constexpr int kRectLaneBlocks = PLVI_RECT_LANE_BLOCKS;
+constexpr int kRectLaneBlocksLarge = PLVI_RECT_LANE_BLOCKS_LARGE;
+constexpr int kRectLargeNf = 1024;
+// points fetched per group above kRectSmallNf frames (throughput): 8 with
+// the weights staged -- a lane then takes a whole 64-byte sector of its
+// weights per group (3.27 ms at 4, 2.75 at 8, 2.85 at 16; 3072 frames, two
+// workgroups per task) -- and 4 for the gather kernel, capped at 64 VGPRs;
+// 16 for small batches, where the longest region's three serial passes are
+// the launch (batch 64 7.97 -> 7.91 ms, profiles/r05/latency_ab.txt)
+constexpr int kRectU = PLVI_RECT_U;
+constexpr int kRectUSmall = PLVI_RECT_U_SMALL;
 constexpr int kRectSmallNf = 64;
+constexpr int kRectStageU = 4;  // points per lane in flight while staging
 
+// One region: q its points, wq its staged weights (STAGED) or M the modgrad
+// plane of row pitch sw.
+template <int U, bool STAGED>
+__device__ inline LsdLine rect_region(const unsigned* __restrict__ q, const double* wq, const double* __restrict__ M,
+                                      int sw, int rn, double angle, double prec, double scale_lsd) {
+    // centroid (lsd.cpp:697-705)
+    double xs = 0.0, ys = 0.0, sum = 0.0;
+    int i = 0;
+    for (; i + U <= rn; i += U) {
+        unsigned v[U];
+        double w[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = q[i + u];
+#pragma unroll
+        for (int u = 0; u < U; ++u) w[u] = STAGED ? wq[i + u] : M[(size_t)(v[u] >> 16) * sw + (v[u] & 0xffffu)];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            xs = rfma((double)(int)(v[u] & 0xffffu), w[u], xs);
+            ys = rfma((double)(int)(v[u] >> 16), w[u], ys);
+            sum += w[u];
+        }
+    }
+    for (; i < rn; ++i) {
+        const unsigned v = q[i];
+        const double w = STAGED ? wq[i] : M[(size_t)(v >> 16) * sw + (v & 0xffffu)];
+        xs = rfma((double)(int)(v & 0xffffu), w, xs);
+        ys = rfma((double)(int)(v >> 16), w, ys);
+        sum += w;
+    }
+    xs /= sum;
+    ys /= sum;
+    // inertia (get_theta, lsd.cpp:755-763)
+    double Ixx = 0.0, Iyy = 0.0, Ixy = 0.0;
+    i = 0;
+    for (; i + U <= rn; i += U) {
+        unsigned v[U];
+        double w[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = q[i + u];
+#pragma unroll
+        for (int u = 0; u < U; ++u) w[u] = STAGED ? wq[i + u] : M[(size_t)(v[u] >> 16) * sw + (v[u] & 0xffffu)];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const double dx = (double)(int)(v[u] & 0xffffu) - xs, dy = (double)(int)(v[u] >> 16) - ys;
+            Ixx = rfma(dy * dy, w[u], Ixx);
+            Iyy = rfma(dx * dx, w[u], Iyy);
+            Ixy = rfma(-(dx * dy), w[u], Ixy);
+        }
+    }
+    for (; i < rn; ++i) {
+        const unsigned v = q[i];
+        const double w = STAGED ? wq[i] : M[(size_t)(v >> 16) * sw + (v & 0xffffu)];
+        const double dx = (double)(int)(v & 0xffffu) - xs, dy = (double)(int)(v >> 16) - ys;
+        Ixx = rfma(dy * dy, w, Ixx);
+        Iyy = rfma(dx * dx, w, Iyy);
+        Ixy = rfma(-(dx * dy), w, Ixy);
+    }
+    const double lambda = 0.5 * (Ixx + Iyy - __builtin_sqrt(rfma(Ixx - Iyy, Ixx - Iyy, 4.0 * Ixy * Ixy)));
+    double theta = (__builtin_fabs(Ixx) > __builtin_fabs(Iyy))
+                       ? (double)plvi_fast_atan2((float)(lambda - Ixx), (float)Ixy)
+                       : (double)plvi_fast_atan2((float)Ixy, (float)(lambda - Iyy));
+    theta *= kD2R;
+    if (angle_diff(theta, angle) > prec) theta += kPi;
+    // dx = cos(theta), dy = sin(theta) (lsd.cpp:710-711): the reference
+    // object calls glibc's sincos; its doubles feed l and the endpoints
+    double dxv, dyv;
+    plvi_sincos_glibc(theta, &dyv, &dxv);
+    // l extents (lsd.cpp:722-735): order-free max(0, .) / min(0, .)
+    double lmax = 0, lmin = 0;
+    i = 0;
+    for (; i + U <= rn; i += U) {
+        unsigned v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = q[i + u];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const double l = rfma((double)(int)(v[u] & 0xffffu) - xs, dxv, ((double)(int)(v[u] >> 16) - ys) * dyv);
+            lmax = l > lmax ? l : lmax;
+            lmin = l < lmin ? l : lmin;
+        }
+    }
+    for (; i < rn; ++i) {
+        const unsigned v = q[i];
+        const double l = rfma((double)(int)(v & 0xffffu) - xs, dxv, ((double)(int)(v >> 16) - ys) * dyv);
+        lmax = l > lmax ? l : lmax;
+        lmin = l < lmin ? l : lmin;
+    }
+    double x1 = rfma(lmin, dxv, xs), y1 = rfma(lmin, dyv, ys);
+    double x2 = rfma(lmax, dxv, xs), y2 = rfma(lmax, dyv, ys);
+    x1 += 0.5; y1 += 0.5; x2 += 0.5; y2 += 0.5;
+    if (scale_lsd != 1) {
+        x1 /= scale_lsd; y1 /= scale_lsd; x2 /= scale_lsd; y2 /= scale_lsd;
+    }
+    return LsdLine{(float)x1, (float)y1, (float)x2, (float)y2};
+}
+
+// wbuf: the weights array, wbuf_task doubles from one task to the next, the
+// first wcap of them usable.  A 256-region group whose point range ends
+// beyond wcap (more than half the plane in regions) gathers from the plane
+// as the earlier kernel did: the same operations on the same values.
 template <int U>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(U <= 4 ? 8 : 1))) void lsd_rect_lanes_kernel(const LineOctDev* __restrict__ octs,
                                                              const double* __restrict__ modgrad,
@@ -829,7 +960,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(U <= 4 ? 8 
                                                              const unsigned* __restrict__ regpts,
                                                              size_t regpts_frame, const int* __restrict__ nlines,
                                                              double prec, double scale_lsd,
-                                                             LsdLine* __restrict__ lines, int oBase, int nOct) {
+                                                             LsdLine* __restrict__ lines, int oBase, int nOct,
+                                                             double* wbuf, size_t wbuf_task, int wcap) {
     // octaves oBase .. oBase + gridDim.z - 1 of nOct; grid (blocks, frames,
     // octaves): every frame's octave 0 (the most regions) is dispatched
     // before the octave-1 blocks, which fill the tail
@@ -840,100 +972,43 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(U <= 4 ? 8 
     const int sw = od.sw;
     const double* M = modgrad + od.soff + (size_t)f * od.splane;
     const unsigned* P = regpts + (size_t)task * regpts_frame;
-    for (int k = blockIdx.x * 256 + threadIdx.x; k - (int)(threadIdx.x & 63) < n; k += gridDim.x * 256) {
+    const LsdRegion* R = regs + (size_t)task * kLsdRawCap;
+    if (!kRectStage) {
+        for (int k = blockIdx.x * 256 + threadIdx.x; k - (int)(threadIdx.x & 63) < n; k += gridDim.x * 256) {
+            if (k >= n) continue;
+            const LsdRegion r = R[k];
+            lines[(size_t)task * kLsdRawCap + k] =
+                rect_region<U, false>(P + r.start, nullptr, M, sw, r.n, r.angle, prec, scale_lsd);
+        }
+        return;
+    }
+    double* Wt = wbuf + (size_t)task * wbuf_task;
+    // kb is uniform over the workgroup: every thread reaches each barrier
+    for (int kb = blockIdx.x * 256; kb < n; kb += gridDim.x * 256) {
+        const int kl = min(kb + 256, n) - 1;
+        const int p0 = R[kb].start, p1 = R[kl].start + R[kl].n;
+        const bool staged = p1 <= wcap;
+        if (staged) {
+            for (int j = p0 + (int)threadIdx.x; j < p1; j += 256 * kRectStageU) {
+                unsigned v[kRectStageU];
+                double w[kRectStageU];
+#pragma unroll
+                for (int u = 0; u < kRectStageU; ++u) v[u] = j + u * 256 < p1 ? P[j + u * 256] : 0u;
+#pragma unroll
+                for (int u = 0; u < kRectStageU; ++u) w[u] = M[(size_t)(v[u] >> 16) * sw + (v[u] & 0xffffu)];
+#pragma unroll
+                for (int u = 0; u < kRectStageU; ++u)
+                    if (j + u * 256 < p1) Wt[j + u * 256] = w[u];
+            }
+        }
+        // the lanes below read what other waves of this workgroup staged
+        __syncthreads();
+        const int k = kb + (int)threadIdx.x;
         if (k >= n) continue;
-        const LsdRegion r = regs[(size_t)task * kLsdRawCap + k];
-        const unsigned* q = P + r.start;
-        const int rn = r.n;
-        // centroid (lsd.cpp:697-705)
-        double xs = 0.0, ys = 0.0, sum = 0.0;
-        int i = 0;
-        for (; i + U <= rn; i += U) {
-            unsigned v[U];
-            double w[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) v[u] = q[i + u];
-#pragma unroll
-            for (int u = 0; u < U; ++u) w[u] = M[(size_t)(v[u] >> 16) * sw + (v[u] & 0xffffu)];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                xs = rfma((double)(int)(v[u] & 0xffffu), w[u], xs);
-                ys = rfma((double)(int)(v[u] >> 16), w[u], ys);
-                sum += w[u];
-            }
-        }
-        for (; i < rn; ++i) {
-            const unsigned v = q[i];
-            const double w = M[(size_t)(v >> 16) * sw + (v & 0xffffu)];
-            xs = rfma((double)(int)(v & 0xffffu), w, xs);
-            ys = rfma((double)(int)(v >> 16), w, ys);
-            sum += w;
-        }
-        xs /= sum;
-        ys /= sum;
-        // inertia (get_theta, lsd.cpp:755-763)
-        double Ixx = 0.0, Iyy = 0.0, Ixy = 0.0;
-        i = 0;
-        for (; i + U <= rn; i += U) {
-            unsigned v[U];
-            double w[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) v[u] = q[i + u];
-#pragma unroll
-            for (int u = 0; u < U; ++u) w[u] = M[(size_t)(v[u] >> 16) * sw + (v[u] & 0xffffu)];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const double dx = (double)(int)(v[u] & 0xffffu) - xs, dy = (double)(int)(v[u] >> 16) - ys;
-                Ixx = rfma(dy * dy, w[u], Ixx);
-                Iyy = rfma(dx * dx, w[u], Iyy);
-                Ixy = rfma(-(dx * dy), w[u], Ixy);
-            }
-        }
-        for (; i < rn; ++i) {
-            const unsigned v = q[i];
-            const double w = M[(size_t)(v >> 16) * sw + (v & 0xffffu)];
-            const double dx = (double)(int)(v & 0xffffu) - xs, dy = (double)(int)(v >> 16) - ys;
-            Ixx = rfma(dy * dy, w, Ixx);
-            Iyy = rfma(dx * dx, w, Iyy);
-            Ixy = rfma(-(dx * dy), w, Ixy);
-        }
-        const double lambda = 0.5 * (Ixx + Iyy - __builtin_sqrt(rfma(Ixx - Iyy, Ixx - Iyy, 4.0 * Ixy * Ixy)));
-        double theta = (__builtin_fabs(Ixx) > __builtin_fabs(Iyy))
-                           ? (double)plvi_fast_atan2((float)(lambda - Ixx), (float)Ixy)
-                           : (double)plvi_fast_atan2((float)Ixy, (float)(lambda - Iyy));
-        theta *= kD2R;
-        if (angle_diff(theta, r.angle) > prec) theta += kPi;
-        // dx = cos(theta), dy = sin(theta) (lsd.cpp:710-711): the reference
-        // object calls glibc's sincos; its doubles feed l and the endpoints
-        double dxv, dyv;
-        plvi_sincos_glibc(theta, &dyv, &dxv);
-        // l extents (lsd.cpp:722-735): order-free max(0, .) / min(0, .)
-        double lmax = 0, lmin = 0;
-        i = 0;
-        for (; i + U <= rn; i += U) {
-            unsigned v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) v[u] = q[i + u];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const double l = rfma((double)(int)(v[u] & 0xffffu) - xs, dxv, ((double)(int)(v[u] >> 16) - ys) * dyv);
-                lmax = l > lmax ? l : lmax;
-                lmin = l < lmin ? l : lmin;
-            }
-        }
-        for (; i < rn; ++i) {
-            const unsigned v = q[i];
-            const double l = rfma((double)(int)(v & 0xffffu) - xs, dxv, ((double)(int)(v >> 16) - ys) * dyv);
-            lmax = l > lmax ? l : lmax;
-            lmin = l < lmin ? l : lmin;
-        }
-        double x1 = rfma(lmin, dxv, xs), y1 = rfma(lmin, dyv, ys);
-        double x2 = rfma(lmax, dxv, xs), y2 = rfma(lmax, dyv, ys);
-        x1 += 0.5; y1 += 0.5; x2 += 0.5; y2 += 0.5;
-        if (scale_lsd != 1) {
-            x1 /= scale_lsd; y1 /= scale_lsd; x2 /= scale_lsd; y2 /= scale_lsd;
-        }
-        lines[(size_t)task * kLsdRawCap + k] = LsdLine{(float)x1, (float)y1, (float)x2, (float)y2};
+        const LsdRegion r = R[k];
+        lines[(size_t)task * kLsdRawCap + k] =
+            staged ? rect_region<U, true>(P + r.start, Wt + r.start, M, sw, r.n, r.angle, prec, scale_lsd)
+                   : rect_region<U, false>(P + r.start, nullptr, M, sw, r.n, r.angle, prec, scale_lsd);
     }
 }
 

@@ -101,9 +101,10 @@ struct LinePipeline {
     bool ktime = false;
     int kn = 0;
     std::vector<hipEvent_t> kev;
-    // and around every LBD Gaussian + Sobel launch: [0] lbd_sobel0_kernel, [1] lbd_sobel1_kernel
-    std::vector<hipEvent_t> kevS[2];
-    int knS[2] = {0, 0};
+    // and around every LBD Gaussian + Sobel launch ([0] lbd_sobel0_kernel, [1]
+    // lbd_sobel1_kernel) and every region2rect launch ([2] lsd_rect_lanes_kernel)
+    std::vector<hipEvent_t> kevS[3];
+    int knS[3] = {0, 0, 0};
     int ktiming(int on) {
         if (on && kev.empty()) {
             kev.resize(2 * kKRing);
@@ -114,7 +115,7 @@ struct LinePipeline {
             }
         }
         ktime = on != 0;
-        if (on) kn = knS[0] = knS[1] = 0;
+        if (on) kn = knS[0] = knS[1] = knS[2] = 0;
         return PLVI_OK;
     }
     void ktimeS(int k, int edge, hipStream_t st) {  // edge 0 = before, 1 = after launch k
@@ -124,7 +125,7 @@ struct LinePipeline {
     }
     int ktiming_read_kind(int kind, float* total_ms, int* launches) {
         if (kind == 0) return ktiming_read(total_ms, launches);
-        if (kind < 1 || kind > 2) return PLVI_E_BADARG;
+        if (kind < 1 || kind > 3) return PLVI_E_BADARG;
         const int k = kind - 1;
         float tot = 0.f;
         for (int i = 0; i < knS[k]; ++i) {
@@ -152,6 +153,8 @@ struct LinePipeline {
 
     ~LinePipeline() {
         for (auto e : kev) (void)hipEventDestroy(e);
+        for (auto& v : kevS)
+            for (auto e : v) (void)hipEventDestroy(e);
         for (auto e : evs) (void)hipEventDestroy(e);
         for (auto e : {evFork, evPrep, evSobel, evOrb, evCrit, evBlur, evGate, evGrow2, evPair, evSobelGo})
             if (e) (void)hipEventDestroy(e);
@@ -376,7 +379,9 @@ struct LinePipeline {
             lOff += (size_t)d.lplane * Bcap;
         }
         lbdPlaneTotal = lOff;
-        qspillFrame = maxSplane;
+        // even: a task's queue-spill slot doubles as its region2rect weights
+        // array (doubles) once the task has grown
+        qspillFrame = (maxSplane + 1) & ~size_t(1);
         for (auto& d : oct) gbitsFrame = std::max(gbitsFrame, (size_t)d.sh * (size_t)((d.sw + 31) / 32));
         if (d_oct.alloc(sizeof(LineOctDev) * nOct) || d_tabs.alloc(tabs.size())) return PLVI_E_HIP;
         PLVI_CHECK(hipMemcpy(d_oct.p, oct.data(), sizeof(LineOctDev) * nOct, hipMemcpyHostToDevice));
@@ -601,12 +606,17 @@ struct LinePipeline {
     // region2rect (lane = region) of octaves [oBase, oBase + oCount); small
     // batches spread a frame's regions over more workgroups (latency)
     void launch_rect(int nf, int oBase, int oCount, hipStream_t st) {
-        const int bx = nf <= 16 ? 8 : kRectLaneBlocks;
+        const int bx = nf <= 16 ? 8 : nf < kRectLargeNf ? kRectLaneBlocks : kRectLaneBlocksLarge;
         auto rectK = nf <= kRectSmallNf ? lsd_rect_lanes_kernel<kRectUSmall> : lsd_rect_lanes_kernel<kRectU>;
+        // weights array: the task's own queue-spill slot, dead once the task
+        // has grown (another octave's growth beside this launch has its own)
+        ktimeS(2, 0, st);
         hipLaunchKernelGGL(rectK, dim3(bx, nf, oCount), dim3(256), 0, st, d_oct.as<LineOctDev>(),
                            (const double*)modg.as<double>(), (const LsdRegion*)regs.as<LsdRegion>(),
                            (const unsigned*)regpts.as<unsigned>(), qspillFrame, (const int*)nlines.as<int>(), prec,
-                           SCALE, rawLines.as<LsdLine>(), oBase, nOct);
+                           SCALE, rawLines.as<LsdLine>(), oBase, nOct, qspill.as<double>(), qspillFrame / 2,
+                           (int)(qspillFrame / 2));
+        ktimeS(2, 1, st);
     }
     // grown: region growing already launched; rect0: only octave 0's
     // region2rect is left (the other octaves' ran behind their growth on
@@ -1080,6 +1090,26 @@ extern "C" int plvi_lines_debug_planes(plvi_line_extractor* h, int frame, int oc
     if (deg) PLVI_CHECK(hipMemcpy(deg, P.pix.as<float>() + o, n * sizeof(float), hipMemcpyDeviceToHost));
     if (modgrad) PLVI_CHECK(hipMemcpy(modgrad, P.modg.as<double>() + o, n * sizeof(double), hipMemcpyDeviceToHost));
     if (cs) PLVI_CHECK(hipMemcpy(cs, P.seedcs.as<float2>() + o, n * sizeof(float2), hipMemcpyDeviceToHost));
+    return PLVI_OK;
+}
+
+// Diagnostic: region2rect's segments of the last batch for one (frame,
+// octave), one per region kept by region growing and nothing filtered
+// (LineSegmentDetectorImpl::detect's lines, x1 y1 x2 y2), copied to host memory.
+extern "C" int plvi_lines_debug_raw_lines(plvi_line_extractor* h, int frame, int octave, float* out, int cap, int* n) {
+    if (!h || octave < 0 || octave >= h->p().nOct || frame < 0 || frame >= h->p().Bcap || cap < 0) return PLVI_E_BADARG;
+    LinePipeline& P = h->p();
+    PLVI_CHECK(hipSetDevice(P.device));
+    PLVI_CHECK(hipDeviceSynchronize());
+    const size_t task = (size_t)frame * P.nOct + octave;
+    int cnt = 0;
+    PLVI_CHECK(hipMemcpy(&cnt, P.nlines.as<int>() + task, sizeof(int), hipMemcpyDeviceToHost));
+    cnt = std::min(cnt, plvi::kLsdRawCap);
+    if (n) *n = cnt;
+    if (cnt > cap) return PLVI_E_CAPACITY;
+    if (out && cnt > 0)
+        PLVI_CHECK(hipMemcpy(out, P.rawLines.as<plvi::LsdLine>() + task * plvi::kLsdRawCap,
+                             sizeof(plvi::LsdLine) * cnt, hipMemcpyDeviceToHost));
     return PLVI_OK;
 }
 

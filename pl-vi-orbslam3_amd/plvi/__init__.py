@@ -290,6 +290,7 @@ def _declare(lib):
         "plvi_lines_debug_mw_stats": ([V, V], I),
         "plvi_lines_debug_planes": ([V, I, I, V, V, V, P, P], I),
         "plvi_lines_debug_sobel": ([V, I, I, V, P, P], I),
+        "plvi_lines_debug_raw_lines": ([V, I, I, V, I, P], I),
         "plvi_descriptor_distance_batch": ([V, V, I, I, V, V], I),
         "plvi_search_by_bow": ([F, I, V, V, V, I, V, V, I, V, V, V, I, V, V, I, V, V], I),
         "plvi_search_by_bow_stereo": ([F, I, V, V, V, I, V, V, I, V, V, V, I, V, V, I, V, I, V], I),
@@ -707,7 +708,7 @@ class Lineextractor:
 
     def kernel_timing_read(self, kind=0):
         """(total ms, launches) since kernel_timing(True): kind 0 = lsd_prep_kernel, 1 = lbd_sobel0_kernel,
-        2 = lbd_sobel1_kernel."""
+        2 = lbd_sobel1_kernel, 3 = lsd_rect_lanes_kernel (region2rect)."""
         tot = ctypes.c_float()
         n = ctypes.c_int()
         _check(self._lib.plvi_lines_kernel_timing_read_kind(self._h, int(kind), ctypes.byref(tot), ctypes.byref(n)),
@@ -734,6 +735,16 @@ class Lineextractor:
         _check(self._lib.plvi_lines_debug_planes(self._h, frame, level, _ptr(deg), _ptr(mg), _ptr(cs), None, None),
                "plvi_lines_debug_planes")
         return deg, mg, cs
+
+    def debug_raw_lines(self, level, frame=0):
+        """n x 4 float32 (x1, y1, x2, y2): region2rect's segments of the last batch, one per region (diagnostic)."""
+        n = ctypes.c_int()
+        _check(self._lib.plvi_lines_debug_raw_lines(self._h, frame, level, None, 1 << 30, ctypes.byref(n)),
+               "plvi_lines_debug_raw_lines")
+        out = np.zeros((max(n.value, 1), 4), np.float32)
+        _check(self._lib.plvi_lines_debug_raw_lines(self._h, frame, level, _ptr(out), n.value, ctypes.byref(n)),
+               "plvi_lines_debug_raw_lines")
+        return out[:n.value].copy()
 
     def debug_sobel(self, level, frame=0):
         """(dx, dy) int16 LBD Sobel planes of the last batch (diagnostic)."""
