@@ -97,7 +97,7 @@ double overlap_stereo(double spl_obs, double epl_obs, double spl_proj, double ep
             overlap = overlap / length;
         else
             overlap = 0.f;
-        if (overlap > 1.f) overlap = 1.f;
+        if (overlap > 1.f) overlap = 1.f;  // never taken: every arm's overlap is a part of [spn, eln] = length
     }
     return overlap;
 }
@@ -139,6 +139,8 @@ extern "C" int oracle_stereo_match(const plvi_keypoint* kpsL, const uint8_t* des
         const int maxr = std::ceil(ref_fmaf(2.0f, scale[kp.octave], kpY));
         const int minr = std::floor(ref_fmaf(-2.0f, scale[kp.octave], kpY));
         if (minr < 0 || maxr >= nRows) return -1;  // vRowIndices[yi] out of range (UB in the reference)
+        // (a band holds at most ceil(4*scale) + 2 rows: the kernel's bucket capacity, its `total > rowCap`
+        // test, is never exceeded)
         for (int yi = minr; yi <= maxr; yi++) vRowIndices[yi].push_back(iR);
     }
     const float minZ = mb;
@@ -215,6 +217,8 @@ extern "C" int oracle_stereo_match(const plvi_keypoint* kpsL, const uint8_t* des
             const float dist2 = vDists[L + bestincR];
             const float dist3 = vDists[L + bestincR + 1];
             const float deltaR = (dist1 - dist3) / (2.0f * ref_fmaf(-2.0f, dist2, dist1 + dist3));
+            // never taken: dist2 is a strict first minimum (dist2 < dist1, dist2 <= dist3), so deltaR =
+            // (a - b) / (2 (a + b)) with a = dist1 - dist2 > 0, b = dist3 - dist2 >= 0 lies in [-0.5, 0.5]
             if (deltaR < -1 || deltaR > 1) continue;
             float bestuR = scale[kpL.octave] * ((float)scaleduR0 + (float)bestincR + deltaR);
             float disparity = (uL - bestuR);

@@ -133,6 +133,7 @@ __global__ __launch_bounds__(kStThreads) void stereo_orb_kernel(
     }
     __syncthreads();
     const int total = block_scan_excl(s_row, nRows + 1, s_tmp);
+    // never taken: a band holds at most ceil(4*scale) + 2 rows and rowCap allows ceil(4*scale_top) + 3 each
     if (total > prm.rowCap) s_fail = 1;
     __syncthreads();
     if (s_fail) {
@@ -155,7 +156,8 @@ __global__ __launch_bounds__(kStThreads) void stereo_orb_kernel(
     for (int iL = t; iL < nL; iL += kStThreads) {
         const plvi_keypoint kp = KL[iL];
         const int row = (int)kp.y;  // vRowIndices[vL] (size_t conversion)
-        if (row >= nRows) { atomicOr(err, 1); continue; }
+        // unsigned: y <= -1 is out of range like y >= nRows (the oracle's (size_t)vL >= nRows)
+        if ((unsigned)row >= (unsigned)nRows) { atomicOr(err, 1); continue; }
         const int c0 = s_row[row], c1 = s_row[row + 1];
         if (c0 == c1) continue;
         const float minU = kp.x - maxD, maxU = kp.x - minD;
@@ -247,6 +249,9 @@ __global__ __launch_bounds__(kStThreads) void stereo_orb_kernel(
                         const float dist2 = (float)s_dist[wv][L + bestincR];
                         const float dist3 = (float)s_dist[wv][L + bestincR + 1];
                         const float deltaR = (dist1 - dist3) / (2.0f * rfmaf(-2.0f, dist2, dist1 + dist3));
+                        // always true: dist2 is a strict first minimum (dist2 < dist1, dist2 <= dist3), so
+                        // deltaR = (a - b) / (2 (a + b)) with a = dist1 - dist2 > 0, b = dist3 - dist2 >= 0
+                        // lies in [-0.5, 0.5]
                         if (!(deltaR < -1 || deltaR > 1)) {
                             float bestuR = prm.scale[oct] * ((float)scaleduR0 + (float)bestincR + deltaR);
                             float disparity = kp.x - bestuR;
@@ -422,7 +427,7 @@ __device__ double overlap_stereo(double spl_obs, double epl_obs, double spl_proj
         else overlap = dmin(eln, epn) - dmax(sln, spn);
         if (length > (double)0.01f) overlap = overlap / length;
         else overlap = 0.f;
-        if (overlap > 1.f) overlap = 1.f;
+        if (overlap > 1.f) overlap = 1.f;  // never taken: every arm's overlap is a part of [spn, eln] = length
     }
     return overlap;
 }

@@ -10,8 +10,6 @@ restatements of the cited lines on extractor output of synthetic rectified
 pairs (plvi.synth.stereo_pair: two planted disparities), and the HIP path
 (host and batched entry points) is compared with the oracle exactly:
 mvuRight, mvDepth, matchGrid table, mvDisparity_l, mvDepth_l, mvle_l."""
-import math
-
 import numpy as np
 import pytest
 
@@ -32,82 +30,7 @@ def _orb_side(img):
     return kps, desc, oracle_lib.orb_pyramid(img)
 
 
-def _dist(a, b):
-    return int(np.unpackbits(np.bitwise_xor(a, b)).sum())
-
-
-def _py_stereo(kL, dL, kR, dR, pyrL, pyrR, scale, inv, mb, mbf):
-    """Literal restatement of Frame::ComputeStereoMatches (float32 arithmetic)."""
-    N = len(kL)
-    ur = np.full(N, -1, np.float32)
-    dp = np.full(N, -1, np.float32)
-    nRows = pyrL[0].shape[0]
-    rows = [[] for _ in range(nRows)]
-    for iR in range(len(kR)):
-        y = f32(kR["y"][iR])
-        sc = f32(scale[kR["octave"][iR]])  # kpY +/- 2*scale, fused in Frame.cc.o
-        maxr, minr = int(math.ceil(util.fmaf(2.0, sc, y))), int(math.floor(util.fmaf(-2.0, sc, y)))
-        for yi in range(minr, maxr + 1):
-            rows[yi].append(iR)
-    minD, maxD = f32(0), f32(mbf / mb)
-    vdist = []
-    for iL in range(N):
-        lev, vL, uL = int(kL["octave"][iL]), f32(kL["y"][iL]), f32(kL["x"][iL])
-        cand = rows[int(vL)]
-        if not cand:
-            continue
-        minU, maxU = f32(uL - maxD), f32(uL - minD)
-        if maxU < 0:
-            continue
-        best, bestR = 100, 0
-        for iR in cand:
-            if kR["octave"][iR] < lev - 1 or kR["octave"][iR] > lev + 1:
-                continue
-            uR = f32(kR["x"][iR])
-            if minU <= uR <= maxU:
-                d = _dist(dL[iL], dR[iR])
-                if d < best:
-                    best, bestR = d, iR
-        if best >= 75:
-            continue
-        sf = inv[lev]
-        rnd = lambda v: f32(math.floor(v + 0.5) if v >= 0 else -math.floor(-v + 0.5))  # noqa: E731
-        suL, svL, suR0 = rnd(f32(uL * sf)), rnd(f32(vL * sf)), rnd(f32(f32(kR["x"][bestR]) * sf))
-        w, L = 5, 5
-        IL = pyrL[lev][int(svL) - w:int(svL) + w + 1, int(suL) - w:int(suL) + w + 1].astype(np.int32)
-        IL = IL - IL[w, w]
-        if suR0 < 0 or suR0 + L + w + 1 >= pyrR[lev].shape[1]:
-            continue
-        dists = []
-        for inc in range(-L, L + 1):
-            c = int(suR0 + inc - w)
-            IR = pyrR[lev][int(svL) - w:int(svL) + w + 1, c:c + 2 * w + 1].astype(np.int32)
-            IR = IR - IR[w, w]
-            dists.append(f32(np.abs(IL - IR).sum()))
-        bi = int(np.argmin(dists))  # first minimum = strict-< scan
-        binc = bi - L
-        if binc in (-L, L):
-            continue
-        d1, d2, d3 = dists[bi - 1], dists[bi], dists[bi + 1]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            delta = f32(f32(d1 - d3) / f32(f32(2.0) * util.fmaf(-2.0, d2, f32(d1 + d3))))
-        if delta < -1 or delta > 1:
-            continue
-        bu = f32(scale[lev] * f32(f32(suR0 + f32(binc)) + delta))
-        disp = f32(uL - bu)
-        if disp >= minD and disp < maxD:
-            if disp <= 0:
-                disp, bu = f32(0.01), f32(float(uL) - 0.01)
-            dp[iL], ur[iL] = f32(mbf / disp), bu
-            vdist.append((int(d2), iL))
-    if vdist:
-        vdist.sort()
-        th = f32(f32(f32(1.5) * f32(1.4)) * f32(vdist[len(vdist) // 2][0]))
-        for d, i in reversed(vdist):
-            if f32(d) < th:
-                break
-            ur[i] = dp[i] = -1
-    return ur, dp
+_py_stereo = util.py_stereo  # the literal restatements live in tests/util.py (shared with test_stereo_branches)
 
 
 @pytest.fixture(scope="module")
@@ -144,69 +67,7 @@ def test_oracle_stereo_empty_sides(pair0):
 
 
 # ------------------------------------------------------------------ lines
-def _py_overlap(spl, epl, spp, epp):
-    ov = 1.0
-    if abs(epl - spl) > float(f32(0.1)):
-        sln, eln, spn, epn = min(spl, epl), max(spl, epl), min(spp, epp), max(spp, epp)
-        length = eln - spn
-        if epn < sln or spn > eln:
-            ov = 0.0
-        elif epn > eln and spn < sln:
-            ov = eln - sln
-        else:
-            ov = min(eln, epn) - max(sln, spn)
-        ov = ov / length if length > float(f32(0.01)) else 0.0
-        ov = min(ov, 1.0) if ov > 1.0 else ov
-    return ov
-
-
-def _py_stereo_lines(klL, dL, klR, dR, W, H, mbf):
-    """Restatement of ComputeStereoMatches_Lines around oracle_lib.match_grid."""
-    iw, ih = 64 / W, 48 / H
-    n1, n2 = len(klL), len(klR)
-    g = lambda k, f: k[f].astype(np.float64)  # noqa: E731
-    sx, sy, ex, ey = g(klL, "startPointX"), g(klL, "startPointY"), g(klL, "endPointX"), g(klL, "endPointY")
-    lines1 = np.stack([(sx * iw).astype(np.int64), (sy * ih).astype(np.int64), (ex * iw).astype(np.int64),
-                       (ey * ih).astype(np.int64)], 1).astype(np.int32)
-    grid = [[[] for _ in range(48)] for _ in range(64)]
-    dirs = np.zeros((n2, 2))
-    for i in range(n2):
-        k = klR[i]
-        vx = float(f32(k["endPointX"] - k["startPointX"])) * iw
-        vy = float(f32(k["endPointY"] - k["startPointY"])) * ih
-        m = math.sqrt(util.fma(vx, vx, vy * vy))
-        dirs[i] = (vx / m, vy / m)
-        for (x, y) in util.line_iterator(float(k["startPointX"]) * iw, float(k["startPointY"]) * ih,
-                                         float(k["endPointX"]) * iw, float(k["endPointY"]) * ih):
-            if 0 <= x < 64 and 0 <= y < 48:
-                grid[x][y].append(i)
-    _, m12 = oracle_lib.match_grid(lines1, dL, grid, dR, dirs)
-    disp = np.full((n1, 2), -1, np.float32)
-    dep = np.full((n1, 2), -1, np.float32)
-    for i1 in range(n1):
-        i2 = m12[i1]
-        if i2 < 0:
-            continue
-        spl0, spl1, epl0, epl1 = sx[i1], sy[i1], ex[i1], ey[i1]
-        r = klR[i2]
-        spr0, spr1 = float(r["startPointX"]), float(r["startPointY"])
-        epr0, epr1 = float(r["endPointX"]), float(r["endPointY"])
-        ov = _py_overlap(spl1, epl1, spr1, epr1)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            spr0 = float(np.float64(util.fma(spr0, spl1 - epr1, epr0 * (spr1 - spl1))) / np.float64(spr1 - epr1))
-            spr1 = spl1
-            epr0 = float(np.float64(util.fma(spr0, epl1 - epr1, epr0 * (spr1 - epl1))) / np.float64(spr1 - epr1))
-            epr1 = epl1
-            ds, de = spl0 - spr0, epl0 - epr0
-            mn = de if de < ds else ds
-            mx = de if ds < de else ds
-            if np.float64(mn) / np.float64(mx) < float(f32(0.7)):
-                ds = de = -1.0
-        th = float(f32(0.1))
-        if ds >= 1 and de >= 1 and abs(spl1 - epl1) > th and abs(spr1 - epr1) > th and ov > float(f32(0.75)):
-            disp[i1] = (ds, de)
-            dep[i1] = (f32(mbf) / f32(ds), f32(mbf) / f32(de))
-    return m12, disp, dep
+_py_stereo_lines = util.py_stereo_lines
 
 
 @pytest.fixture(scope="module")

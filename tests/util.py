@@ -1,3 +1,4 @@
+import math
 import pathlib
 
 import numpy as np
@@ -571,6 +572,9 @@ def structured_frames(w=640, h=480):
 def fma(a, b, c):
     """a*b + c rounded once to double (float(Fraction) is correctly rounded)."""
     from fractions import Fraction
+    if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)):
+        with np.errstate(invalid="ignore"):
+            return float(np.float64(a) * np.float64(b) + np.float64(c))  # inf / NaN: as the unfused operations
     return float(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))
 
 
@@ -707,3 +711,397 @@ def frustum_line_case(seed, p, n=800):
             "in_flags": (rng.random(n) < 0.9).astype(np.uint8),
             "desc": rng.integers(0, 256, (n, 32), dtype=np.uint8),
             "proj": rng.uniform(-5, 800, (n, 4)).astype(np.float32), "angle": rng.uniform(-3, 3, n)}
+
+
+# ------------------------------------------------------------- rectified stereo
+# Literal pure-Python restatements of Frame::ComputeStereoMatches (src/Frame.cc:1228-1406) and
+# Frame::ComputeStereoMatches_Lines (:1408-1492, lineSegmentOverlapStereo :1494-1529,
+# filterLineSegmentDisparity :1531-1542).  tests/test_stereo.py pins the oracle against them on extractor
+# output; tests/test_stereo_branches.py on crafted pairs, where the traced variants also say which branch
+# every left keypoint / line took.
+_f32 = np.float32
+
+# outcome of a left keypoint (py_stereo_traced)
+(ST_NO_CANDIDATE, ST_MAXU_NEG, ST_NO_ORB_MATCH, ST_BORDER_SKIP, ST_EDGE_MINIMUM, ST_DELTA_RANGE, ST_DISPARITY_RANGE,
+ ST_CLAMPED, ST_ACCEPTED, ST_MEDIAN_REJECTED) = range(10)
+ST_NAMES = ("NO_CANDIDATE", "MAXU_NEG", "NO_ORB_MATCH", "BORDER_SKIP", "EDGE_MINIMUM", "DELTA_RANGE",
+            "DISPARITY_RANGE", "CLAMPED", "ACCEPTED", "MEDIAN_REJECTED")
+
+# outcome of a left line (py_stereo_lines_traced): the first test of the acceptance condition that fails, the
+# two horizontal tests first; and the arm of lineSegmentOverlapStereo it took
+(SL_UNMATCHED, SL_HORIZONTAL_LEFT, SL_HORIZONTAL_RIGHT, SL_RATIO_REJECT, SL_MIN_DISP_REJECT, SL_OVERLAP_REJECT,
+ SL_ACCEPTED) = range(7)
+SL_NAMES = ("UNMATCHED", "HORIZONTAL_LEFT", "HORIZONTAL_RIGHT", "RATIO_REJECT", "MIN_DISP_REJECT", "OVERLAP_REJECT",
+            "ACCEPTED")
+OV_NONE, OV_DISJOINT, OV_CONTAINED, OV_PARTIAL, OV_SHORT_LENGTH = range(5)
+OV_NAMES = ("NONE", "DISJOINT", "CONTAINED", "PARTIAL", "SHORT_LENGTH")
+
+_POP8 = np.array([bin(i).count("1") for i in range(256)], np.int32)
+
+
+def py_stereo_traced(kL, dL, kR, dR, pyrL, pyrR, scale, inv, mb, mbf):
+    """Literal restatement of Frame::ComputeStereoMatches (float32 arithmetic).  Returns (mvuRight, mvDepth,
+    codes, info): codes[iL] = the ST_* outcome of left keypoint iL (ST_CLAMPED / ST_ACCEPTED are kept matches,
+    ST_MEDIAN_REJECTED a match the median test removed); info = {"sad": the accepted SADs in iL order,
+    "sad_idx": their iL, "clamped": mask of the matches that took the disparity <= 0 clamp, "best": the chosen
+    right index per left keypoint (-1 none), "band": (minr, maxr) per right keypoint, "pre": the outcomes before
+    the median test}."""
+    N = len(kL)
+    ur = np.full(N, -1, np.float32)
+    dp = np.full(N, -1, np.float32)
+    codes = np.full(N, ST_NO_CANDIDATE, np.int32)
+    clamped = np.zeros(N, bool)
+    bestidx = np.full(N, -1, np.int32)
+    nRows = pyrL[0].shape[0]
+    rows = [[] for _ in range(nRows)]
+    band = np.zeros((len(kR), 2), np.int64)
+    for iR in range(len(kR)):
+        y = _f32(kR["y"][iR])
+        sc = _f32(scale[kR["octave"][iR]])  # kpY +/- 2*scale, fused in Frame.cc.o
+        maxr, minr = int(math.ceil(fmaf(2.0, sc, y))), int(math.floor(fmaf(-2.0, sc, y)))
+        band[iR] = (minr, maxr)
+        for yi in range(minr, maxr + 1):
+            rows[yi].append(iR)
+    minD, maxD = _f32(0), _f32(mbf / mb)
+    vdist = []
+    dL = np.asarray(dL, np.uint8).reshape(-1, 32)
+    dR = np.asarray(dR, np.uint8).reshape(-1, 32)
+    for iL in range(N):
+        lev, vL, uL = int(kL["octave"][iL]), _f32(kL["y"][iL]), _f32(kL["x"][iL])
+        cand = rows[int(vL)]
+        if not cand:
+            continue
+        minU, maxU = _f32(uL - maxD), _f32(uL - minD)
+        if maxU < 0:
+            codes[iL] = ST_MAXU_NEG
+            continue
+        best, bestR = 100, 0
+        dists_c = _POP8[dR[cand] ^ dL[iL]].sum(1)  # DescriptorDistance to every candidate
+        for c, iR in enumerate(cand):
+            if kR["octave"][iR] < lev - 1 or kR["octave"][iR] > lev + 1:
+                continue
+            uR = _f32(kR["x"][iR])
+            if minU <= uR <= maxU:
+                d = int(dists_c[c])
+                if d < best:
+                    best, bestR = d, iR
+        if best >= 75:
+            codes[iL] = ST_NO_ORB_MATCH
+            continue
+        bestidx[iL] = bestR
+        sf = inv[lev]
+        rnd = lambda v: _f32(math.floor(v + 0.5) if v >= 0 else -math.floor(-v + 0.5))  # noqa: E731
+        suL, svL, suR0 = rnd(_f32(uL * sf)), rnd(_f32(vL * sf)), rnd(_f32(_f32(kR["x"][bestR]) * sf))
+        w, L = 5, 5
+        IL = pyrL[lev][int(svL) - w:int(svL) + w + 1, int(suL) - w:int(suL) + w + 1].astype(np.int32)
+        IL = IL - IL[w, w]
+        if suR0 < 0 or suR0 + L + w + 1 >= pyrR[lev].shape[1]:
+            codes[iL] = ST_BORDER_SKIP
+            continue
+        dists = []
+        for inc in range(-L, L + 1):
+            c = int(suR0 + inc - w)
+            IR = pyrR[lev][int(svL) - w:int(svL) + w + 1, c:c + 2 * w + 1].astype(np.int32)
+            IR = IR - IR[w, w]
+            dists.append(_f32(np.abs(IL - IR).sum()))
+        bi = int(np.argmin(dists))  # first minimum = strict-< scan
+        binc = bi - L
+        if binc in (-L, L):
+            codes[iL] = ST_EDGE_MINIMUM
+            continue
+        d1, d2, d3 = dists[bi - 1], dists[bi], dists[bi + 1]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            delta = _f32(_f32(d1 - d3) / _f32(_f32(2.0) * fmaf(-2.0, d2, _f32(d1 + d3))))
+        if delta < -1 or delta > 1:
+            codes[iL] = ST_DELTA_RANGE
+            continue
+        bu = _f32(scale[lev] * _f32(_f32(suR0 + _f32(binc)) + delta))
+        disp = _f32(uL - bu)
+        if disp >= minD and disp < maxD:
+            codes[iL] = ST_ACCEPTED
+            if disp <= 0:
+                disp, bu = _f32(0.01), _f32(float(uL) - 0.01)
+                codes[iL] = ST_CLAMPED
+                clamped[iL] = True
+            dp[iL], ur[iL] = _f32(mbf / disp), bu
+            vdist.append((int(d2), iL))
+        else:
+            codes[iL] = ST_DISPARITY_RANGE
+    info = {"sad": np.array([d for d, _ in vdist], np.int64), "sad_idx": np.array([i for _, i in vdist], np.int64),
+            "clamped": clamped, "best": bestidx, "band": band, "pre": codes.copy()}
+    if vdist:
+        vdist.sort()
+        th = _f32(_f32(_f32(1.5) * _f32(1.4)) * _f32(vdist[len(vdist) // 2][0]))
+        for d, i in reversed(vdist):
+            if _f32(d) < th:
+                break
+            ur[i] = dp[i] = -1
+            codes[i] = ST_MEDIAN_REJECTED
+    return ur, dp, codes, info
+
+
+def py_stereo(kL, dL, kR, dR, pyrL, pyrR, scale, inv, mb, mbf):
+    """(mvuRight, mvDepth) of py_stereo_traced."""
+    return py_stereo_traced(kL, dL, kR, dR, pyrL, pyrR, scale, inv, mb, mbf)[:2]
+
+
+def py_overlap_traced(spl, epl, spp, epp):
+    """Frame::lineSegmentOverlapStereo -> (overlap, OV_* arm)."""
+    ov, arm = 1.0, OV_NONE
+    if abs(epl - spl) > float(_f32(0.1)):
+        sln, eln, spn, epn = min(spl, epl), max(spl, epl), min(spp, epp), max(spp, epp)
+        length = eln - spn
+        if epn < sln or spn > eln:
+            ov, arm = 0.0, OV_DISJOINT
+        elif epn > eln and spn < sln:
+            ov, arm = eln - sln, OV_CONTAINED
+        else:
+            ov, arm = min(eln, epn) - max(sln, spn), OV_PARTIAL
+        if length > float(_f32(0.01)):
+            ov = ov / length
+        else:
+            ov, arm = 0.0, OV_SHORT_LENGTH
+        ov = min(ov, 1.0) if ov > 1.0 else ov
+    return ov, arm
+
+
+def py_overlap(spl, epl, spp, epp):
+    return py_overlap_traced(spl, epl, spp, epp)[0]
+
+
+def py_stereo_lines_traced(klL, dL, klR, dR, W, H, mbf, klUn=None, range_hint=0):
+    """Restatement of ComputeStereoMatches_Lines around oracle_lib.match_grid.  Returns (matches_12,
+    mvDisparity_l, mvDepth_l, codes, info): codes[i1] = SL_* outcome; info = {"arm": OV_* per left line, "le":
+    mvle_l from klUn (None = the left lines), "grid_total": entries of the right lines' GridStructure,
+    "cells_outside": rasterised cells that fell outside it, "max_cell": the longest cell list, "quirk": mask of
+    the lines whose acceptance differs when ep_r is re-projected from the original sp_r instead of the
+    updated one (Frame.cc:1469-1470), "disp": the (disp_s, disp_e) doubles before the filter}."""
+    import oracle_lib
+    iw, ih = 64 / W, 48 / H
+    n1, n2 = len(klL), len(klR)
+    g = lambda k, f: k[f].astype(np.float64)  # noqa: E731
+    sx, sy, ex, ey = g(klL, "startPointX"), g(klL, "startPointY"), g(klL, "endPointX"), g(klL, "endPointY")
+    with np.errstate(invalid="ignore"):
+        lines1 = np.stack([np.trunc(sx * iw), np.trunc(sy * ih), np.trunc(ex * iw), np.trunc(ey * ih)],
+                          1).astype(np.int64).astype(np.int32)
+    grid = [[[] for _ in range(48)] for _ in range(64)]
+    dirs = np.zeros((n2, 2))
+    outside = 0
+    for i in range(n2):
+        k = klR[i]
+        vx = float(_f32(k["endPointX"] - k["startPointX"])) * iw
+        vy = float(_f32(k["endPointY"] - k["startPointY"])) * ih
+        with np.errstate(divide="ignore", invalid="ignore"):
+            m = np.float64(math.sqrt(fma(vx, vx, vy * vy)))
+            dirs[i] = (np.float64(vx) / m, np.float64(vy) / m)
+        for (x, y) in line_iterator(float(k["startPointX"]) * iw, float(k["startPointY"]) * ih,
+                                    float(k["endPointX"]) * iw, float(k["endPointY"]) * ih):
+            if 0 <= x < 64 and 0 <= y < 48:
+                grid[x][y].append(i)
+            else:
+                outside += 1
+    _, m12 = oracle_lib.match_grid(lines1, dL, grid, dR, dirs, range_hint=range_hint)
+    disp = np.full((n1, 2), -1, np.float32)
+    dep = np.full((n1, 2), -1, np.float32)
+    codes = np.full(n1, SL_UNMATCHED, np.int32)
+    arms = np.full(n1, OV_NONE, np.int32)
+    quirk = np.zeros(n1, bool)
+    raw = np.full((n1, 2), np.nan)
+    th = float(_f32(0.1))
+    for i1 in range(n1):
+        i2 = m12[i1]
+        if i2 < 0:
+            continue
+        spl0, spl1, epl0, epl1 = sx[i1], sy[i1], ex[i1], ey[i1]
+        r = klR[i2]
+        spr0, spr1 = float(r["startPointX"]), float(r["startPointY"])
+        epr0, epr1 = float(r["endPointX"]), float(r["endPointY"])
+        right_flat = not abs(spr1 - epr1) > th
+        ov, arms[i1] = py_overlap_traced(spl1, epl1, spr1, epr1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            plain = np.float64(fma(spr0, epl1 - epr1, epr0 * (spr1 - epl1))) / np.float64(spr1 - epr1)
+            spr0 = float(np.float64(fma(spr0, spl1 - epr1, epr0 * (spr1 - spl1))) / np.float64(spr1 - epr1))
+            spr1 = spl1
+            epr0 = float(np.float64(fma(spr0, epl1 - epr1, epr0 * (spr1 - epl1))) / np.float64(spr1 - epr1))
+            epr1 = epl1
+            ds, de = spl0 - spr0, epl0 - epr0
+            raw[i1] = (ds, de)
+            de_plain = epl0 - float(plain)
+
+            def filt(a, b):
+                mn = b if b < a else a
+                mx = b if a < b else a
+                return (-1.0, -1.0) if np.float64(mn) / np.float64(mx) < float(_f32(0.7)) else (a, b)
+            fs, fe = filt(ds, de)
+            ps, pe = filt(ds, de_plain)
+        geom = abs(spl1 - epl1) > th and abs(spr1 - epr1) > th and ov > float(_f32(0.75))
+        ok = fs >= 1 and fe >= 1 and geom
+        quirk[i1] = ok != (ps >= 1 and pe >= 1 and geom)
+        if not abs(spl1 - epl1) > th:
+            codes[i1] = SL_HORIZONTAL_LEFT
+        elif right_flat:
+            codes[i1] = SL_HORIZONTAL_RIGHT
+        elif (fs, fe) != (ds, de) and not (np.isnan(ds) or np.isnan(de)):
+            codes[i1] = SL_RATIO_REJECT
+        elif not (fs >= 1 and fe >= 1):
+            codes[i1] = SL_MIN_DISP_REJECT
+        elif not ov > float(_f32(0.75)):
+            codes[i1] = SL_OVERLAP_REJECT
+        else:
+            codes[i1] = SL_ACCEPTED
+        if ok:
+            disp[i1] = (fs, fe)
+            dep[i1] = (_f32(mbf) / _f32(fs), _f32(mbf) / _f32(fe))
+    le = np.zeros((n1, 3))
+    if n2 > 0:
+        un = klL if klUn is None else klUn
+        for i in range(n1):
+            a0, a1, b0, b1 = (float(un[f][i]) for f in ("startPointX", "startPointY", "endPointX", "endPointY"))
+            l0, l1, l2 = a1 - b1, b0 - a0, fma(a0, b1, -(a1 * b0))  # Eigen cross + norm, fused in Frame.cc.o
+            with np.errstate(divide="ignore", invalid="ignore"):
+                s = np.float64(math.sqrt(fma(l0, l0, l1 * l1)))
+                le[i] = (np.float64(l0) / s, np.float64(l1) / s, np.float64(l2) / s)
+    info = {"arm": arms, "le": le, "grid_total": sum(len(c) for col in grid for c in col), "cells_outside": outside,
+            "max_cell": max(len(c) for col in grid for c in col), "quirk": quirk, "disp": raw}
+    return m12, disp, dep, codes, info
+
+
+def py_stereo_lines(klL, dL, klR, dR, W, H, mbf):
+    """(matches_12, mvDisparity_l, mvDepth_l) of py_stereo_lines_traced."""
+    return py_stereo_lines_traced(klL, dL, klR, dR, W, H, mbf)[:3]
+
+
+def flip_bits(desc, k, rng):
+    """A copy of the 32-byte descriptor with exactly k of its 256 bits flipped."""
+    bits = np.unpackbits(np.asarray(desc, np.uint8))
+    bits[rng.choice(256, k, replace=False)] ^= 1
+    return np.packbits(bits)
+
+
+def stereo_lds_bytes(n_rows, cap_l, cap_r, nlevels, sf=1.2):
+    """Dynamic LDS of stereo_orb_kernel (Stereo): row offsets and cursors, right u / octave, four
+    per-left-keypoint tables and the row buckets of cap_r * (ceil(4 * scale_top) + 3) 16-bit entries."""
+    top = orb_scale_factors(nlevels, sf)[nlevels - 1]
+    row_cap = cap_r * (int(math.ceil(np.float32(2) * (np.float32(2.0) * top))) + 3)
+    return (2 * n_rows + 1) * 4 + 8 * cap_r + 16 * cap_l + (2 * row_cap + 15) // 16 * 16
+
+
+class StereoScene:
+    """A hand-made rectified ORB pair for Frame::ComputeStereoMatches: per level a random left plane and a
+    right plane holding the same content moved `shift` pixels to the left (right[y, x] = left[y, x + shift];
+    an int, or one int per row of the level) plus uniform noise of amplitude `noise` (an int, or one per row);
+    the planes are no resizes of each other, the matcher only reads them.  fold = P makes every row of both
+    planes a triangle-wave fold of a random base (img[:, x] = base[:, |((x + P) mod 2P) - P|]), so that every
+    column that is a multiple of P is a mirror axis.  Keypoints are placed by hand (add_*); a matching pair
+    shares a random descriptor, unrelated ones sit near distance 128."""
+
+    def __init__(self, seed, nlevels, w0=160, h0=96, shift=3, noise=3, sizes=None, fold=None):
+        from oracle_lib import KEYPOINT_DTYPE
+        self.dtype = KEYPOINT_DTYPE
+        self.rng = rng = np.random.default_rng(seed)
+        self.n = nlevels
+        self.scale = orb_scale_factors(nlevels)
+        self.inv = np.zeros(16, np.float32)
+        self.inv[:nlevels] = [np.float32(1.0) / s for s in self.scale[:nlevels]]
+        self.sizes = sizes or [(int(round(w0 / float(self.scale[lv]))), int(round(h0 / float(self.scale[lv]))))
+                               for lv in range(nlevels)]
+        self.pL, self.pR, self.shift = [], [], []
+        for lv, (w, h) in enumerate(self.sizes):
+            sh = shift[lv] if isinstance(shift, (list, tuple)) else shift
+            sh = np.broadcast_to(np.asarray(sh, np.int64), (h,))
+            nz = noise[lv] if isinstance(noise, (list, tuple)) else noise
+            nz = np.broadcast_to(np.asarray(nz, np.int64), (h,))
+            self.shift.append(sh)
+            if fold:
+                base = rng.integers(0, 256, (h, fold + 1), dtype=np.uint8)
+                tri = np.abs((np.arange(w) + fold) % (2 * fold) - fold)
+                nb = np.clip(base.astype(np.int64) + (rng.integers(-1, 2, base.shape) * nz[:, None]), 0, 255)
+                self.pL.append(np.ascontiguousarray(base[:, tri]))
+                self.pR.append(np.ascontiguousarray(nb.astype(np.uint8)[:, tri]))
+                continue
+            left = rng.integers(0, 256, (h, w), dtype=np.uint8)
+            right = rng.integers(0, 256, (h, w), dtype=np.uint8)
+            xs = np.arange(w)[None, :] + sh[:, None]
+            ok = (xs >= 0) & (xs < w)
+            moved = np.take_along_axis(left, np.clip(xs, 0, w - 1), 1)
+            right = np.where(ok, moved, right).astype(np.int64)
+            right = right + (rng.integers(-1, 2, (h, w)) * nz[:, None])
+            self.pL.append(left)
+            self.pR.append(np.clip(right, 0, 255).astype(np.uint8))
+        self.kl, self.dl, self.kr, self.dr = [], [], [], []
+
+    def desc(self):
+        return self.rng.integers(0, 256, 32, dtype=np.uint8)
+
+    def add_left(self, x, y, octave, desc):
+        self.kl.append((np.float32(x), np.float32(y), octave))
+        self.dl.append(np.asarray(desc, np.uint8))
+        return len(self.kl) - 1
+
+    def add_right(self, x, y, octave, desc):
+        self.kr.append((np.float32(x), np.float32(y), octave))
+        self.dr.append(np.asarray(desc, np.uint8))
+        return len(self.kr) - 1
+
+    def level_xy(self, xl, yl, octave):
+        """Image coordinates of the level pixel (xl, yl): round(x * mvInvScaleFactors) gives it back."""
+        s = self.scale[octave]
+        x, y = np.float32(np.float32(xl) * s), np.float32(np.float32(yl) * s)
+        back = (round(float(np.float32(x * self.inv[octave]))), round(float(np.float32(y * self.inv[octave]))))
+        assert back == (xl, yl)
+        return x, y
+
+    def add_pair(self, xl, yl, octave, e=0, flips=0):
+        """A left keypoint on level pixel (xl, yl) and its right keypoint listed e level pixels to the right
+        of where the content is (the SAD minimum then lies at incR = -e); the right descriptor differs in
+        `flips` bits."""
+        x, y = self.level_xy(xl, yl, octave)
+        xr, _ = self.level_xy(xl - int(self.shift[octave][yl]) + e, yl, octave)
+        d = self.desc()
+        return self.add_left(x, y, octave, d), self.add_right(xr, y, octave, flip_bits(d, flips, self.rng))
+
+    def tables(self):
+        def tab(k):
+            t = np.zeros(len(k), self.dtype)
+            for i, (x, y, o) in enumerate(k):
+                t["x"][i], t["y"][i], t["octave"][i] = x, y, o
+            t["size"], t["class_id"] = 31, -1
+            return t
+        return (tab(self.kl), np.array(self.dl, np.uint8).reshape(-1, 32), tab(self.kr),
+                np.array(self.dr, np.uint8).reshape(-1, 32), self.pL, self.pR, self.scale, self.inv)
+
+
+class StereoLineSet:
+    """Hand-built keylines for Frame::ComputeStereoMatches_Lines: only the end points and the LBD descriptors
+    are read.  A pair shares a random descriptor (distance 0, every other line near 128), so matchGrid pairs
+    them whenever the right line crosses the grid window of a left end point."""
+
+    def __init__(self, seed):
+        self.rng = np.random.default_rng(seed)
+        self.L, self.R, self.dl, self.dr, self.un = [], [], [], [], []
+
+    def left(self, line, desc=None, un=None):
+        self.L.append(line)
+        self.un.append(un if un is not None else (line[0] + 0.25, line[1], line[2], line[3]))
+        self.dl.append(self.rng.integers(0, 256, 32, dtype=np.uint8) if desc is None else desc)
+        return len(self.L) - 1
+
+    def right(self, line, desc=None):
+        self.R.append(line)
+        self.dr.append(self.rng.integers(0, 256, 32, dtype=np.uint8) if desc is None else desc)
+        return len(self.R) - 1
+
+    def pair(self, left, right, un=None):
+        d = self.rng.integers(0, 256, 32, dtype=np.uint8)
+        return self.left(left, d, un), self.right(right, d.copy())
+
+    def tables(self):
+        from oracle_lib import KEYLINE_DTYPE
+
+        def tab(lines):
+            t = np.zeros(len(lines), KEYLINE_DTYPE)
+            for i, ln in enumerate(lines):
+                (t["startPointX"][i], t["startPointY"][i], t["endPointX"][i], t["endPointY"][i]) = ln
+            return t
+        return (tab(self.L), np.array(self.dl, np.uint8).reshape(-1, 32), tab(self.R),
+                np.array(self.dr, np.uint8).reshape(-1, 32), tab(self.un))
