@@ -1029,6 +1029,100 @@ int plvi_stereo_frame_extract_batch(plvi_orb_extractor* orb_left, plvi_orb_extra
                                     const uint8_t* d_left, const uint8_t* d_right, int n_frames, size_t frame_stride,
                                     size_t row_stride, int lap0, int lap1, void* stream);
 
+/* ----------------------------------------------------------- triangulation
+ * The candidate searches of LocalMapping::CreateNewMapPoints /
+ * CreateNewMapLines, called once per covisible neighbour of every new
+ * keyframe (src/LocalMapping.cc:804, :1135). */
+
+/* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs,
+ * bOnlyStereo, bCoarse) (src/ORBmatcher.cc:965-1206), the single-camera
+ * branch: !pKF1->mpCamera2 && !pKF2->mpCamera2, NLeft == -1, Pinhole;
+ * keypoints are mvKeysUn.  The constants of one (KF1, KF2) pair:
+ *   F12   row-major 3x3.  Replaces the matrix Pinhole::epipolarConstrain
+ *         (src/CameraModels/Pinhole.cpp:137-140) rebuilds for every
+ *         candidate, K1.t().inv() * SkewSymmetricMatrix(t12) * R12 * K2.inv()
+ *         with R12 = R1w*R2w.t() and t12 = -R1w*R2w.t()*t2w + t1w
+ *         (ORBmatcher.cc:991-992): in this branch it is the same for every
+ *         candidate, and it is built with cv::Mat::inv and cv::gemm, whose
+ *         arithmetic is outside the reference tree.  (The F12 argument of
+ *         the reference function itself is never read.)
+ *   ep    the epipole in KF2, replaces pKF2->mpCamera->project(R2w*Cw + t2w)
+ *         with Cw = pKF1->GetCameraCenter() (ORBmatcher.cc:972-977).
+ *   sigma2 / scale_factors   pKF2->mvLevelSigma2 and pKF2->mvScaleFactors,
+ *         indexed by kp2.octave (an octave outside [0, n) reads the nearest
+ *         entry; n_* outside [1, 16] is clamped).
+ * Everything downstream of these inputs is bit-exact with the reference
+ * build: the epipolar line, num, den and dsqr in float with the reference
+ * object's fused multiply-adds, the double compare dsqr < 3.84*unc, den == 0
+ * rejecting, `|| bCoarse`, the epipole rejection (only when neither keypoint
+ * is stereo) in float, TH_LOW = 50, last-wins among equal distances, the
+ * rotation histogram and ComputeThreeMaxima; nmatches counts after the
+ * histogram filter.
+ * Out of scope: the KannalaBrandt8 / two-camera branch (:994-1003,
+ * :1099-1129; its epipolarConstrain is TriangulateMatches with an OpenCV SVD,
+ * VERDICT.md), the overload with vMatchedPoints (:1208), Fuse, SearchBySim3
+ * and SearchByBoW(KeyFrame*, KeyFrame*). */
+typedef struct plvi_triangulation_pair {
+  float F12[9];
+  float ep[2];
+  int n_sigma2;
+  float sigma2[16];
+  int n_scale_factors;
+  float scale_factors[16];
+  int only_stereo;       /* bOnlyStereo */
+  int coarse;            /* bCoarse */
+  int check_orientation; /* mbCheckOrientation */
+} plvi_triangulation_pair;
+
+/* Batched device variant, layout as plvi_search_by_bow_batch: pair p uses
+ * rows p*cap1 / p*cap2 of the keypoint tables (kps, desc, has_point, uright
+ * and the FeatureVector index list idx), p*node_cap (node ids, ascending)
+ * and p*(node_cap+1) (offsets) of the CSR arrays, and d_pairs[p].
+ * has_point[i] = GetMapPoint(i) != NULL (skipped on either side), uright =
+ * mvuRight (>= 0: stereo).  A keypoint is in at most one node.  Outputs
+ * matches12 [n_pairs][cap1] (vMatches12: KF2 index or -1) and nmatches
+ * [n_pairs]; vMatchedPairs is the in-order compaction of matches12.
+ * d_n1 / d_n2 follow the count contract (plvi_hamming_knn2_batch) against
+ * cap1 / cap2 and the node counts against node_cap; an offset outside
+ * [0, list length] is read as clamped and a list entry outside [0, n) is
+ * ignored.  rows [0, n1) of matches12 are fully written.
+ * The KF2 list is staged whole in LDS: 52*cap2 + 16*node_cap + 8 bytes, which
+ * with the kernel's static data must fit the 160 KB of a CU (cap2 up to
+ * ~3000); a larger table returns PLVI_E_CAPACITY and nothing is launched --
+ * no pair is truncated.  Asynchronous on `stream`.
+ * Replaces ORBmatcher.h:74 (SearchForTriangulation). */
+int plvi_search_for_triangulation_batch(int n_pairs, const plvi_triangulation_pair* d_pairs, int cap1, int cap2,
+                                        int node_cap, const plvi_keypoint* d_kps1, const uint8_t* d_desc1,
+                                        const int* d_n1, const int* d_node1, const int* d_off1, const int* d_nnodes1,
+                                        const int* d_idx1, const uint8_t* d_has_point1, const float* d_uright1,
+                                        const plvi_keypoint* d_kps2, const uint8_t* d_desc2, const int* d_n2,
+                                        const int* d_node2, const int* d_off2, const int* d_nnodes2,
+                                        const int* d_idx2, const uint8_t* d_has_point2, const float* d_uright2,
+                                        int* d_matches12, int* d_nmatches, void* stream);
+
+/* Single pair from host memory, synchronous (like plvi_search_by_bow):
+ * matches12 [n1]; returns nmatches (>= 0) or an error. */
+int plvi_search_for_triangulation(const plvi_triangulation_pair* pair, const plvi_keypoint* kps1,
+                                  const uint8_t* desc1, int n1, const int* node1, const int* off1, int nnodes1,
+                                  const int* idx1, const uint8_t* has_point1, const float* uright1,
+                                  const plvi_keypoint* kps2, const uint8_t* desc2, int n2, const int* node2,
+                                  const int* off2, int nnodes2, const int* idx2, const uint8_t* has_point2,
+                                  const float* uright2, int* matches12);
+
+/* LineMatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs)
+ * (src/LineMatcher.cpp:142-171): plvi_line_search_init_batch with the
+ * threshold 0.1 * nn12_mad (pKF1->lineDescriptorMAD) and without the pairs
+ * whose query line (d_has_line1 [p][cap1], pKF1->GetMapLine(qdx)) or train
+ * line (d_has_line2 [p][cap2], pKF2->GetMapLine(tdx)) already has a MapLine.
+ * The masks act after the MAD: a masked line still counts in nn12_mad.
+ * Same tables, scratch (4 * n_pairs * cap1 ints), outputs, count contract
+ * and 0 matches for n1 = 0 or n2 < 2 as plvi_line_search_init_batch.
+ * Replaces LineMatcher.h:97 (SearchForTriangulation). */
+int plvi_line_search_triangulation_batch(const uint8_t* d_desc1, const int* d_n1, int cap1, const uint8_t* d_desc2,
+                                         const int* d_n2, int cap2, int n_pairs, const uint8_t* d_has_line1,
+                                         const uint8_t* d_has_line2, int* d_scratch, int* d_pairs, int* d_npairs,
+                                         double* d_mad, void* stream);
+
 /* Device memory helpers for bindings that have no HIP runtime of their own
  * (ctypes, JNI): thin wrappers over hipMalloc/hipFree/hipMemcpy on the
  * current device.  kind: 1 = host->device, 2 = device->host, 3 = d->d. */

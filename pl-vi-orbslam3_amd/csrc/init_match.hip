@@ -225,14 +225,20 @@ __global__ __launch_bounds__(256) void search_init_kernel(
     if (tid == 0) nmatch_all[pr] = s_nm;
 }
 
-// lineDescriptorMAD + the selection of SerachForInitialize, one workgroup per
+// lineDescriptorMAD + the selection of SerachForInitialize (factor 0.5, no
+// masks) or of LineMatcher::SearchForTriangulation (LineMatcher.cpp:142-171:
+// factor 0.1, and a pair whose query or train line already has a MapLine is
+// dropped -- after the MAD, which counts every query), one workgroup per
 // pair, from the kNN-2 tables (i0, d0, i1, d1) [pair][cap1].
 __global__ __launch_bounds__(256) void line_init_select_kernel(const int* __restrict__ n1_all, int cap1,
                                                                const int* __restrict__ n2_all,
                                                                const int* __restrict__ i0_all,
                                                                const int* __restrict__ d0_all,
-                                                               const int* __restrict__ d1_all, int2* __restrict__ out,
-                                                               int* __restrict__ nout, double* __restrict__ mad) {
+                                                               const int* __restrict__ d1_all, double factor,
+                                                               const uint8_t* __restrict__ has1_all,
+                                                               const uint8_t* __restrict__ has2_all, int cap2,
+                                                               int2* __restrict__ out, int* __restrict__ nout,
+                                                               double* __restrict__ mad) {
     __shared__ int h[4][260];
     __shared__ int s_med[2], s_dev[2], s_wsum[4];
     const int pr = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -286,17 +292,21 @@ __global__ __launch_bounds__(256) void line_init_select_kernel(const int* __rest
     __syncthreads();
     const double nn_mad = 1.4826 * (double)(float)s_dev[0];
     const double nn12_mad = 1.4826 * (double)(float)s_dev[1];
-    const double th = nn12_mad * 0.5;
+    const double th = nn12_mad * factor;
     if (mad && tid == 0) {
         mad[2 * pr] = nn_mad;
         mad[2 * pr + 1] = nn12_mad;
     }
-    // LineMatches in query order: (double)(d1 - d0) > 0.5 * nn12_mad
+    // LineMatches in query order: (double)(d1 - d0) > factor * nn12_mad
     int2* O = out + (size_t)pr * cap1;
+    const uint8_t* H1 = has1_all ? has1_all + (size_t)pr * cap1 : nullptr;
+    const uint8_t* H2 = has2_all ? has2_all + (size_t)pr * cap2 : nullptr;
     int base = 0;
     for (int i0 = 0; i0 < n1; i0 += 256) {
         const int i = i0 + tid;
-        const bool keep = i < n1 && (double)((float)D1[i] - (float)D0[i]) > th;
+        bool keep = i < n1 && (double)((float)D1[i] - (float)D0[i]) > th;
+        // GetMapLine(qdx) || GetMapLine(tdx) (:161); the train index is a row of [0, min(n2, cap2))
+        if (keep && ((H1 && H1[i]) || (H2 && H2[I0[i]]))) keep = false;
         const unsigned long long b = __ballot(keep);
         if (lane == 0) s_wsum[wv] = __popcll(b);
         __syncthreads();
@@ -339,9 +349,10 @@ extern "C" int plvi_search_for_initialization_batch(int n_pairs, const plvi_init
     return PLVI_OK;
 }
 
-extern "C" int plvi_line_search_init_batch(const uint8_t* d_desc1, const int* d_n1, int cap1, const uint8_t* d_desc2,
-                                           const int* d_n2, int cap2, int n_pairs, int* d_scratch, int* d_pairs,
-                                           int* d_npairs, double* d_mad, void* stream) {
+static int line_search_select(const uint8_t* d_desc1, const int* d_n1, int cap1, const uint8_t* d_desc2,
+                              const int* d_n2, int cap2, int n_pairs, double factor, const uint8_t* d_has1,
+                              const uint8_t* d_has2, int* d_scratch, int* d_pairs, int* d_npairs, double* d_mad,
+                              void* stream) {
     if (n_pairs < 0 || cap1 < 1 || cap2 < 1) return PLVI_E_BADARG;
     if (n_pairs == 0) return PLVI_OK;
     if (!d_desc1 || !d_n1 || !d_desc2 || !d_n2 || !d_scratch || !d_pairs || !d_npairs) return PLVI_E_BADARG;
@@ -352,8 +363,25 @@ extern "C" int plvi_line_search_init_batch(const uint8_t* d_desc1, const int* d_
     int* d1 = d_scratch + 3 * plane;
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = launch_knn2(d_desc1, d_n1, cap1, d_desc2, d_n2, cap2, n_pairs, i0, d0, i1, d1, st)) return rc;
-    hipLaunchKernelGGL(line_init_select_kernel, dim3(n_pairs), dim3(256), 0, st, d_n1, cap1, d_n2, i0, d0, d1,
-                       reinterpret_cast<int2*>(d_pairs), d_npairs, d_mad);
+    hipLaunchKernelGGL(line_init_select_kernel, dim3(n_pairs), dim3(256), 0, st, d_n1, cap1, d_n2, i0, d0, d1, factor,
+                       d_has1, d_has2, cap2, reinterpret_cast<int2*>(d_pairs), d_npairs, d_mad);
     PLVI_CHECK(hipGetLastError());
     return PLVI_OK;
+}
+
+extern "C" int plvi_line_search_init_batch(const uint8_t* d_desc1, const int* d_n1, int cap1, const uint8_t* d_desc2,
+                                           const int* d_n2, int cap2, int n_pairs, int* d_scratch, int* d_pairs,
+                                           int* d_npairs, double* d_mad, void* stream) {
+    return line_search_select(d_desc1, d_n1, cap1, d_desc2, d_n2, cap2, n_pairs, 0.5, nullptr, nullptr, d_scratch,
+                              d_pairs, d_npairs, d_mad, stream);
+}
+
+extern "C" int plvi_line_search_triangulation_batch(const uint8_t* d_desc1, const int* d_n1, int cap1,
+                                                    const uint8_t* d_desc2, const int* d_n2, int cap2, int n_pairs,
+                                                    const uint8_t* d_has_line1, const uint8_t* d_has_line2,
+                                                    int* d_scratch, int* d_pairs, int* d_npairs, double* d_mad,
+                                                    void* stream) {
+    if (n_pairs > 0 && (!d_has_line1 || !d_has_line2)) return PLVI_E_BADARG;
+    return line_search_select(d_desc1, d_n1, cap1, d_desc2, d_n2, cap2, n_pairs, 0.1, d_has_line1, d_has_line2,
+                              d_scratch, d_pairs, d_npairs, d_mad, stream);
 }

@@ -5,7 +5,8 @@ Class and method names follow the reference interfaces they replace:
 
   ORBextractor  -> ORB_SLAM3::ORBextractor (include/ORBextractor.h:44-110)
   LineMatcher   -> ORB_SLAM3::LineMatcher  (include/LineMatcher.h:88-107)
-  ORBmatcher    -> ORB_SLAM3::ORBmatcher   (include/ORBmatcher.h:39-68): SearchByBoW, DescriptorDistance
+  ORBmatcher    -> ORB_SLAM3::ORBmatcher   (include/ORBmatcher.h:39-78): SearchByBoW, SearchForTriangulation,
+                   DescriptorDistance
   hamming_knn2  -> cv::BFMatcher(NORM_HAMMING).knnMatch(k=2) (LineMatcher.cpp:47-48)
   ORBVocabulary -> DBoW2::TemplatedVocabulary<FORB> (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h):
                    loadFromTextFile, transform(features, BowVector&, FeatureVector&, levelsup)
@@ -111,6 +112,30 @@ class InitParams(ctypes.Structure):
     _fields_ = [("min_x", ctypes.c_float), ("min_y", ctypes.c_float), ("inv_w", ctypes.c_float),
                 ("inv_h", ctypes.c_float), ("window", ctypes.c_int), ("nnratio", ctypes.c_float),
                 ("check_orientation", ctypes.c_int)]
+
+
+class TriangulationPair(ctypes.Structure):
+    """plvi_triangulation_pair (include/plvi_frontend.h): the constants of one (KF1, KF2) pair of
+    ORBmatcher::SearchForTriangulation."""
+    _fields_ = [("F12", ctypes.c_float * 9), ("ep", ctypes.c_float * 2), ("n_sigma2", ctypes.c_int),
+                ("sigma2", ctypes.c_float * 16), ("n_scale_factors", ctypes.c_int),
+                ("scale_factors", ctypes.c_float * 16), ("only_stereo", ctypes.c_int), ("coarse", ctypes.c_int),
+                ("check_orientation", ctypes.c_int)]
+
+    @classmethod
+    def make(cls, F12, ep, sigma2, scale_factors, only_stereo=False, coarse=False, check_orientation=True):
+        t = cls()
+        for i, v in enumerate(np.asarray(F12, np.float32).reshape(9)):
+            t.F12[i] = v
+        t.ep[0], t.ep[1] = float(ep[0]), float(ep[1])
+        t.n_sigma2, t.n_scale_factors = len(sigma2), len(scale_factors)
+        for i, v in enumerate(sigma2):
+            t.sigma2[i] = v
+        for i, v in enumerate(scale_factors):
+            t.scale_factors[i] = v
+        t.only_stereo, t.coarse, t.check_orientation = int(bool(only_stereo)), int(bool(coarse)), int(
+            bool(check_orientation))
+        return t
 
 
 class LocalParams(ctypes.Structure):
@@ -319,6 +344,10 @@ def _declare(lib):
         "plvi_stream_synchronize": ([V], I),
         "plvi_search_for_initialization_batch": ([I, V, V, V, V, I, V, V, V, V, I, V, V, V, V, V], I),
         "plvi_line_search_init_batch": ([V, V, I, V, V, I, I, V, V, V, V, V], I),
+        "plvi_line_search_triangulation_batch": ([V, V, I, V, V, I, I, V, V, V, V, V, V, V], I),
+        "plvi_search_for_triangulation_batch": ([I, V, I, I, I, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V,
+                                                 V, V, V], I),
+        "plvi_search_for_triangulation": ([V, V, V, I, V, V, I, V, V, V, V, V, I, V, V, I, V, V, V, V], I),
         "plvi_search_local_batch": ([I, V, V, V, V, I, V, V, V, V, V, V, V, V, V, I, V, V, V], I),
         "plvi_search_local": ([V, V, V, I, V, V, V, V, V, V, I, V], I),
         "plvi_search_by_projection_stereo_batch": ([I, V, V, V, V, V, I, V, V, V, V, V, V, I, V, V, V, V, V, V, V, V,
@@ -835,6 +864,35 @@ class LineMatcher:
         return n, out[:len(ca)]
 
     @staticmethod
+    def SearchForTriangulation(desc1, desc2, has_line1, has_line2):
+        """SearchForTriangulation(pKF1, pKF2, vMatchedPairs) (src/LineMatcher.cpp:142-171): has_line =
+        GetMapLine(i) != NULL per line.  Returns (nmatches, vMatchedPairs as an n x 2 int array (query, train),
+        (nn_mad, nn12_mad))."""
+        n1, n2 = len(desc1), len(desc2)
+        c1, c2 = max(n1, 1), max(n2, 1)
+        d1 = np.zeros((c1, 32), np.uint8)
+        d1[:n1] = desc1
+        d2 = np.zeros((c2, 32), np.uint8)
+        d2[:n2] = desc2
+        h1 = np.zeros(c1, np.uint8)
+        h1[:n1] = has_line1
+        h2 = np.zeros(c2, np.uint8)
+        h2[:n2] = has_line2
+        bufs = [DeviceBuffer(a.nbytes) for a in (d1, d2, h1, h2)]
+        for b, a in zip(bufs, (d1, d2, h1, h2)):
+            b.upload(a)
+        cnt = DeviceBuffer(16)
+        cnt.upload(np.array([n1, n2, 0, 0], np.int32))
+        scr = DeviceBuffer(16 * c1)
+        pr = DeviceBuffer(8 * c1)
+        mad = DeviceBuffer(16)
+        line_search_triangulation_batch(bufs[0].ptr, cnt.ptr, c1, bufs[1].ptr, cnt.ptr + 4, c2, 1, bufs[2].ptr,
+                                        bufs[3].ptr, scr.ptr, pr.ptr, cnt.ptr + 8, mad.ptr)
+        load().plvi_device_synchronize()
+        n = int(cnt.download(np.zeros(4, np.int32))[2])
+        return n, pr.download(np.zeros((c1, 2), np.int32))[:n], tuple(mad.download(np.zeros(2, np.float64)))
+
+    @staticmethod
     def matchGrid(lines1, desc1, grid, desc2, directions2, window=((7, 0), (2, 2)), range_hint=1):
         """LineMatcher::matchGrid (src/LineMatcher.cpp:191-272).  lines1: n1 x 4 ints (line_2d grid coords),
         grid: grid[x][y] lists of right-line indices, directions2: n2 x 2.  range_hint: 1 = libstdc++ <= GCC 10
@@ -891,6 +949,37 @@ class ORBmatcher:
                                                        len(fn), _ptr(fi), int(f_nleft), _ptr(out)),
                    "plvi_search_by_bow_stereo")
         return n, out[:len(fd)]
+
+    def SearchForTriangulation(self, kps1, desc1, featvec1, has_point1, uright1, kps2, desc2, featvec2, has_point2,
+                               uright2, F12, ep, sigma2, scale_factors, bOnlyStereo=False, bCoarse=False):
+        """SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse)
+        (src/ORBmatcher.cc:965-1206), single-camera Pinhole branch.  Keypoints are mvKeysUn in
+        KEYPOINT_DTYPE, has_point = GetMapPoint(i) != NULL, uright = mvuRight; F12 (3 x 3) and the epipole
+        ep replace what the reference derives from the poses (plvi_frontend.h), sigma2 / scale_factors
+        are pKF2's mvLevelSigma2 / mvScaleFactors.  Returns (nmatches, vMatchedPairs as an n x 2 int
+        array (idx1, idx2) in idx1 order)."""
+        n1, n2 = len(kps1), len(kps2)
+        k1 = np.ascontiguousarray(kps1, KEYPOINT_DTYPE)
+        k2 = np.ascontiguousarray(kps2, KEYPOINT_DTYPE)
+        d1 = np.ascontiguousarray(desc1, np.uint8)
+        d2 = np.ascontiguousarray(desc2, np.uint8)
+        h1 = np.ascontiguousarray(has_point1, np.uint8)
+        h2 = np.ascontiguousarray(has_point2, np.uint8)
+        u1 = np.ascontiguousarray(uright1, np.float32)
+        u2 = np.ascontiguousarray(uright2, np.float32)
+        _same_len(n1, desc1=d1, has_point1=h1, uright1=u1)
+        _same_len(n2, desc2=d2, has_point2=h2, uright2=u2)
+        a, ao, ai = feature_vector_csr(featvec1)
+        b, bo, bi = feature_vector_csr(featvec2)
+        pair = TriangulationPair.make(F12, ep, sigma2, scale_factors, bOnlyStereo, bCoarse, self.check_orientation)
+        out = np.full(max(n1, 1), -1, np.int32)
+        n = _check(self._lib.plvi_search_for_triangulation(
+            ctypes.byref(pair), _ptr(k1), _ptr(d1), n1, _ptr(a), _ptr(ao), len(a), _ptr(ai), _ptr(h1), _ptr(u1),
+            _ptr(k2), _ptr(d2), n2, _ptr(b), _ptr(bo), len(b), _ptr(bi), _ptr(h2), _ptr(u2), _ptr(out)),
+            "plvi_search_for_triangulation")
+        m = out[:n1]
+        i1 = np.flatnonzero(m >= 0)
+        return n, np.stack([i1, m[i1]], axis=1).astype(np.int32)
 
     def SearchByProjection(self, params, cur_kps, cur_desc, last_x3dc, last_octave, last_angle, mp_desc,
                            last_flags, cur_blocked=None, cur_uright=None):
@@ -1280,6 +1369,30 @@ def line_search_init_batch(d_desc1, d_n1, cap1, d_desc2, d_n2, cap2, n_pairs, d_
     _check(load().plvi_line_search_init_batch(V(d_desc1), V(d_n1), cap1, V(d_desc2), V(d_n2), cap2, n_pairs,
                                               V(d_scratch), V(d_pairs), V(d_npairs), V(d_mad), V(stream or 0)),
            "plvi_line_search_init_batch")
+
+
+def line_search_triangulation_batch(d_desc1, d_n1, cap1, d_desc2, d_n2, cap2, n_pairs, d_has_line1, d_has_line2,
+                                    d_scratch, d_pairs, d_npairs, d_mad=0, stream=None):
+    """LineMatcher::SearchForTriangulation (src/LineMatcher.cpp:142-171) over device pair tables."""
+    V = ctypes.c_void_p
+    _check(load().plvi_line_search_triangulation_batch(V(d_desc1), V(d_n1), cap1, V(d_desc2), V(d_n2), cap2, n_pairs,
+                                                       V(d_has_line1), V(d_has_line2), V(d_scratch), V(d_pairs),
+                                                       V(d_npairs), V(d_mad), V(stream or 0)),
+           "plvi_line_search_triangulation_batch")
+
+
+def search_for_triangulation_batch(n_pairs, d_pairs, cap1, cap2, node_cap, kf1, kf2, d_matches12, d_nmatches,
+                                   stream=None):
+    """ORBmatcher::SearchForTriangulation over device pair tables (plvi_search_for_triangulation_batch).
+    d_pairs: TriangulationPair [n_pairs]; kf1 / kf2: the nine device pointers of one side in header order
+    (kps, desc, n, node, off, nnodes, idx, has_point, uright)."""
+    V = ctypes.c_void_p
+    if len(kf1) != 9 or len(kf2) != 9:
+        raise ValueError("kf1 / kf2: nine device pointers each")
+    _check(load().plvi_search_for_triangulation_batch(n_pairs, V(d_pairs), cap1, cap2, node_cap,
+                                                      *[V(x) for x in kf1], *[V(x) for x in kf2], V(d_matches12),
+                                                      V(d_nmatches), V(stream or 0)),
+           "plvi_search_for_triangulation_batch")
 
 
 def line_search_init(desc1, desc2):
