@@ -398,6 +398,56 @@ int plvi_search_by_bow_stereo_batch(int n_pairs, float nnratio, int check_orient
                                     const int* d_f_nnodes, const int* d_f_idx, const int* d_f_nleft, int* d_match_kf,
                                     int* d_nmatches, void* stream);
 
+/* ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>&
+ * vpMatches12) (src/ORBmatcher.cc:823-963), the candidate search of
+ * LoopClosing::DetectCommonRegionsFromBoW (src/LoopClosing.cc:823, once per
+ * candidate and covisible: a batch of (current KF, KF_j) pairs), single-camera
+ * branch (NLeft == -1 on both sides).  Per side s = 1, 2:
+ *   desc   = pKFs->mDescriptors rows;  angle = pKFs->mvKeysUn[i].angle;
+ *   live[i] = GetMapPointMatches()[i] != NULL && !isBad(), evaluated by the
+ *             caller (replaces :862-866 and :882-888);
+ *   node / off / idx = pKFs->mFeatVec as CSR arrays sorted by node id, as in
+ *             plvi_search_by_bow.  A keypoint is in at most one node.
+ * The device does the rest: the lower_bound merge walk; per shared node the
+ * KF1 entries in list order, each against the node's KF2 entries that are
+ * live and not yet in vbMatched2 (which this function, unlike
+ * SearchForTriangulation, writes: :911); best / second with strict `<`
+ * (first wins); bestDist1 < TH_LOW = 50, strict here (the KF-Frame function
+ * has <=); (float)bestDist1 < nnratio * (float)bestDist2 (256 with a single
+ * candidate); the 30-bin rotation histogram of angle1[idx1] - angle2[idx2]
+ * and ComputeThreeMaxima.  Output matches12[idx1] = the KF2 keypoint index
+ * whose MapPoint the reference stores in vpMatches12[idx1]
+ * (vpMapPoints2[idx2] on the caller's side), or -1; nmatches is counted
+ * after the rotation filter.
+ *
+ * Batched device variant, layout as plvi_search_by_bow_batch: pair p uses
+ * rows p*cap1 / p*cap2 of the keypoint tables and of idx, p*node_cap (node
+ * ids, ascending) and p*(node_cap+1) (offsets) of the CSR arrays.  Outputs
+ * matches12 [n_pairs][cap1], nmatches [n_pairs]; rows [0, n1) of matches12
+ * are fully written.  d_n1 / d_n2 follow the count contract
+ * (plvi_hamming_knn2_batch) against cap1 / cap2 and the node counts against
+ * node_cap; an offset outside [0, list length] is read as clamped and a list
+ * entry outside [0, n) is ignored.
+ * LDS: 4*cap1 (cap1 rounded up to even) + 8*node_cap + cap2 bytes, which with
+ * the kernel's static data must fit the 160 KB of a CU; a larger table
+ * returns PLVI_E_CAPACITY and nothing is launched.  Asynchronous on `stream`.
+ * Replaces ORBmatcher.h:68 (SearchByBoW(KeyFrame*, KeyFrame*, ...)). */
+int plvi_search_by_bow_kf_batch(int n_pairs, float nnratio, int check_orientation, int cap1, int cap2, int node_cap,
+                                const uint8_t* d_desc1, const float* d_angle1, const uint8_t* d_live1,
+                                const int* d_n1, const int* d_node1, const int* d_off1, const int* d_nnodes1,
+                                const int* d_idx1, const uint8_t* d_desc2, const float* d_angle2,
+                                const uint8_t* d_live2, const int* d_n2, const int* d_node2, const int* d_off2,
+                                const int* d_nnodes2, const int* d_idx2, int* d_matches12, int* d_nmatches,
+                                void* stream);
+
+/* Single pair from host memory, synchronous: matches12 [n1]; returns
+ * nmatches (>= 0) or an error.  n1 == 0 or n2 == 0: matches12 all -1,
+ * returns 0, nothing is launched. */
+int plvi_search_by_bow_kf(float nnratio, int check_orientation, const uint8_t* desc1, const float* angle1,
+                          const uint8_t* live1, int n1, const int* node1, const int* off1, int nnodes1,
+                          const int* idx1, const uint8_t* desc2, const float* angle2, const uint8_t* live2, int n2,
+                          const int* node2, const int* off2, int nnodes2, const int* idx2, int* matches12);
+
 /* ------------------------------------------------------------- matchGrid
  * LineMatcher::matchGrid(lines1, desc1, grid, desc2, directions2, w,
  * matches_12) (src/LineMatcher.cpp:191-272) with GridStructure::get
@@ -695,6 +745,80 @@ int plvi_search_reloc_batch(int n_pairs, const plvi_reloc_params* p, const plvi_
 int plvi_search_reloc(const plvi_reloc_params* p, const plvi_keypoint* cur_kps, const uint8_t* cur_desc, int n_cur,
                       const uint8_t* cur_blocked, const uint8_t* kf_flags, const float* x3dc, const float* dist,
                       const int* level, const float* kf_angle, const uint8_t* mp_desc, int n_kf, int* match);
+
+/* ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, vpPoints,
+ * vpMatched, th, ratioHamming) (src/ORBmatcher.cc:473-586; LoopClosing.cc:954
+ * th 5 / ratio 1.0, :1207 th 3 / ratio 1.5) and the overload with
+ * vpPointsKFs / vpMatchedKF (:588-704; LoopClosing.cc:929 th 8 / ratio 1.5):
+ * the Sim3-guided searches of loop closing and map merging.  The MapPoint
+ * reads (they take the MapPoint mutexes) and every cv::Mat product stay with
+ * the caller: with sRcw = Scw(0:3, 0:3), scw = sqrt(sRcw.row(0).dot(sRcw.row(0))),
+ * Rcw = sRcw/scw, tcw = Scw(0:3, 3)/scw, Ow = -Rcw.t()*tcw (:483-487), per
+ * candidate MapPoint i, in vpPoints order,
+ *   flags bit0 = !pMP->isBad() && !spAlreadyFound.count(pMP) (:501; the set
+ *                is built from vpMatched on entry);
+ *   x3dc [3]   = Rcw*p3Dw + tcw (:508);
+ *   dist [3]   = { cv::norm(p3Dw - Ow) as float (:529), GetMinDistanceInvariance(),
+ *                  GetMaxDistanceInvariance() };
+ *   dot        = PO.dot(Pn) with PO = p3Dw - Ow, Pn = pMP->GetNormal() (:537;
+ *                cv::Mat::dot returns double, and the compare is in double);
+ *   level      = pMP->PredictScale(dist, pKF);  desc = pMP->GetDescriptor().
+ * The device does the rest, bit-exact with the reference build: z < 0.0
+ * skips; the projection -- 0: pKF->mpCamera->project, Pinhole,
+ * (fx*x)/z + cx (the :473 overload, no fused operation); 1: invz = 1/z,
+ * u = fma(x*invz, fx, cx) (the :588 overload; the reference object fuses
+ * both sums) --; KeyFrame::IsInImage (u >= min_x && u < max_x, likewise v);
+ * dist < min || dist > max skips; dot < 0.5 * (double)dist skips; a level
+ * outside [0, nlevels) gets no candidate; KeyFrame::GetFeaturesInArea(u, v,
+ * th * mvScaleFactors[level]) (KeyFrame.cc:1200-1244, the Frame's cell
+ * arithmetic without a level filter); candidates whose vpMatched[idx] is
+ * non-NULL -- on entry or assigned earlier in this call -- or whose octave is
+ * outside [level-1, level] are skipped; the first keypoint with the smallest
+ * distance wins; accepted when (float)bestDist <= 50.0f * ratio_hamming.
+ * The two overloads are not aliases: where x*invz*fx + cx rounds differently
+ * from (fx*x)/z + cx the window, and with it the result, can differ. */
+typedef struct plvi_sim3_proj_params {
+  float fx, fy, cx, cy;             /* pKF->fx, fy, cx, cy (Pinhole mvParameters) */
+  float min_x, max_x, min_y, max_y; /* pKF->mnMinX, mnMaxX, mnMinY, mnMaxY (ints in KeyFrame, compared as float) */
+  float inv_w, inv_h;               /* pKF->mfGridElementWidthInv / HeightInv */
+  int th;                           /* th (an int in the reference: radius = (float)th * mvScaleFactors[level]) */
+  float ratio_hamming;              /* ratioHamming; 50 * ratio_hamming < 256 is required (PLVI_E_BADARG):
+                                       beyond it a search without a candidate would index vpMatched[-1] */
+  int projection;                   /* 0: the :473 overload, 1: the :588 overload */
+  int nlevels;                      /* pKF->mnScaleLevels, in [1, 16] */
+  float scale_factors[16];          /* pKF->mvScaleFactors */
+} plvi_sim3_proj_params;
+
+/* Batched over n_pairs (KeyFrame, point list) pairs.  KeyFrame p:
+ * keypoints / descriptors [p][kp_cap] (mvKeysUn, mDescriptors, counts d_kp_n),
+ * the grid CSR from plvi_assign_grid_batch (the KeyFrame copies the Frame's
+ * 64 x 48 grid), matched[idx] = vpMatched[idx] != NULL on entry (d_matched
+ * NULL = none).  Points p: [p][pt_cap] flags, x3dc [3], dist [3], dot
+ * (double), level, desc [32] as above (counts d_pt_n).  Output match
+ * [p][kp_cap]: the point index i this call stored in vpMatched[idx], or -1
+ * (entry-matched rows stay -1); nmatches [p] = the return value.  The
+ * vpMatchedKF of the second overload is vpPointsKFs[match[idx]], a lookup on
+ * the caller's side.
+ * kp_cap <= 65535; pt_cap is bounded by LDS only: 17*kp_cap + 4*pt_cap +
+ * 12292 + 64 bytes, which with the kernel's static data must fit the 160 KB
+ * of a CU (8000 points against 2000 keypoints take 77 KB); a larger table
+ * returns PLVI_E_CAPACITY and nothing is launched -- no list is truncated.
+ * d_kp_n / d_pt_n follow the count contract (plvi_hamming_knn2_batch).
+ * Asynchronous on `stream`.  Replaces ORBmatcher.h:58 and :62. */
+int plvi_search_sim3_projection_batch(int n_pairs, const plvi_sim3_proj_params* p, const plvi_keypoint* d_kps,
+                                      const uint8_t* d_desc, const int* d_kp_n, int kp_cap, const uint8_t* d_matched,
+                                      const int* d_cell_off, const int* d_cell_idx, const uint8_t* d_flags,
+                                      const float* d_x3dc, const float* d_dist, const double* d_dot,
+                                      const int* d_level, const uint8_t* d_mp_desc, const int* d_pt_n, int pt_cap,
+                                      int* d_match, int* d_nmatches, void* stream);
+
+/* One pair from host memory, synchronous (grid built on the device, so
+ * n_kp <= 8192 as in plvi_assign_grid_batch).  match [n_kp]; returns
+ * nmatches (>= 0) or an error. */
+int plvi_search_sim3_projection(const plvi_sim3_proj_params* p, const plvi_keypoint* kps, const uint8_t* desc,
+                                int n_kp, const uint8_t* matched, const uint8_t* flags, const float* x3dc,
+                                const float* dist, const double* dot, const int* level, const uint8_t* mp_desc,
+                                int n_pt, int* match);
 
 /* ORBmatcher::SearchByProjection(Frame& F, const vector<MapPoint*>&
  * vpMapPoints, th, bFarPoints, thFarPoints) (src/ORBmatcher.cc:44-145,
@@ -1060,8 +1184,8 @@ int plvi_stereo_frame_extract_batch(plvi_orb_extractor* orb_left, plvi_orb_extra
  * histogram filter.
  * Out of scope: the KannalaBrandt8 / two-camera branch (:994-1003,
  * :1099-1129; its epipolarConstrain is TriangulateMatches with an OpenCV SVD,
- * VERDICT.md), the overload with vMatchedPoints (:1208), Fuse, SearchBySim3
- * and SearchByBoW(KeyFrame*, KeyFrame*). */
+ * VERDICT.md), the overload with vMatchedPoints (:1208), Fuse and
+ * SearchBySim3. */
 typedef struct plvi_triangulation_pair {
   float F12[9];
   float ep[2];

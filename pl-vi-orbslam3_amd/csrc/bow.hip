@@ -16,6 +16,9 @@
 // parallel (best / second with the reference's strict-< first-wins rule as
 // a wave reduction).  Matches and the 30-bin rotation histogram live in
 // LDS; ComputeThreeMaxima and the 10 % bin filter run at the end.
+//
+// ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vector<MapPoint*>&)
+// (:823-963) is search_by_bow_kf_kernel below, the same schedule.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +26,7 @@
 #include <vector>
 
 #include "grid_search.h"
+#include "host_stage.h"
 #include "plvi_common.h"
 
 namespace plvi {
@@ -178,6 +182,145 @@ static size_t bow_smem(int f_cap, int node_cap) {
     return (size_t)((f_cap + 1) & ~1) * 4 + (size_t)node_cap * 8;
 }
 
+// ---------------------------------------------------------------------------
+// ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>&
+// vpMatches12) (src/ORBmatcher.cc:823-963), the loop-closing candidate search
+// (LoopClosing.cc:823), single-camera branch (NLeft == -1 on both sides).
+// Same schedule as above with the roles renamed: the table indexed by the
+// result is KF1's (vpMatches12[idx1] = KF2 keypoint), the flags a match sets
+// are KF2's (vbMatched2, :911) and both sides have a live byte.  What differs
+// from the KF-Frame function, as the reference object shows: bestDist1 <
+// TH_LOW is strict (cmp $0x31 / jg) and there is no second camera.
+// LDS: matches12 [cap1] ints, the shared node pairs [node_cap] int2, one byte
+// per KF2 keypoint (!live2 on entry, then vbMatched2 or-ed in).
+__global__ __launch_bounds__(256) void search_by_bow_kf_kernel(
+    float nnratio, int check_orientation, int cap1, int cap2, int node_cap, const uint8_t* __restrict__ desc1_all,
+    const float* __restrict__ angle1_all, const uint8_t* __restrict__ live1_all, const int* __restrict__ n1_all,
+    const int* __restrict__ node1_all, const int* __restrict__ off1_all, const int* __restrict__ nnodes1_all,
+    const int* __restrict__ idx1_all, const uint8_t* __restrict__ desc2_all, const float* __restrict__ angle2_all,
+    const uint8_t* __restrict__ live2_all, const int* __restrict__ n2_all, const int* __restrict__ node2_all,
+    const int* __restrict__ off2_all, const int* __restrict__ nnodes2_all, const int* __restrict__ idx2_all,
+    int* __restrict__ matches12, int* __restrict__ nmatches) {
+    extern __shared__ __align__(16) int lds[];
+    const int p = blockIdx.x;
+    int* s_m12 = lds;                                                      // [cap1] KF2 index or -1
+    int2* s_pairs = reinterpret_cast<int2*>(lds + ((cap1 + 1) & ~1));     // [node_cap] shared (KF1 node, KF2 node)
+    unsigned char* s_skip2 = reinterpret_cast<unsigned char*>(s_pairs + node_cap);  // [cap2] !live2 | vbMatched2
+    __shared__ int s_hist[kBowHisto], s_npairs, s_count, s_keep[3];
+    const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    // count contract (plvi_frontend.h)
+    const int n1 = min(max(n1_all[p], 0), cap1), n2 = min(max(n2_all[p], 0), cap2);
+    const int nn1 = min(max(nnodes1_all[p], 0), node_cap), nn2 = min(max(nnodes2_all[p], 0), node_cap);
+    const uint8_t* D1 = desc1_all + (size_t)p * cap1 * 32;
+    const float* A1 = angle1_all + (size_t)p * cap1;
+    const uint8_t* L1 = live1_all + (size_t)p * cap1;
+    const int* N1 = node1_all + (size_t)p * node_cap;
+    const int* O1 = off1_all + (size_t)p * (node_cap + 1);
+    const int* I1 = idx1_all + (size_t)p * cap1;
+    const uint8_t* D2 = desc2_all + (size_t)p * cap2 * 32;
+    const float* A2 = angle2_all + (size_t)p * cap2;
+    const uint8_t* L2 = live2_all + (size_t)p * cap2;
+    const int* N2 = node2_all + (size_t)p * node_cap;
+    const int* O2 = off2_all + (size_t)p * (node_cap + 1);
+    const int* I2 = idx2_all + (size_t)p * cap2;
+    // list lengths: an offset outside [0, length] is read as clamped, like a count
+    const int len1 = nn1 ? min(max(O1[nn1], 0), cap1) : 0, len2 = nn2 ? min(max(O2[nn2], 0), cap2) : 0;
+    for (int i = tid; i < n1; i += 256) s_m12[i] = -1;
+    for (int i = tid; i < n2; i += 256) s_skip2[i] = L2[i] == 0;
+    if (tid < kBowHisto) s_hist[tid] = 0;
+    if (tid == 0) {
+        // merge walk with the reference's lower_bound jumps (:851-940)
+        int a = 0, b = 0, n = 0;
+        while (a < nn1 && b < nn2) {
+            const int ka = N1[a], kb = N2[b];
+            if (ka == kb) {
+                s_pairs[n++] = make_int2(a, b);
+                ++a;
+                ++b;
+            } else if (ka < kb) {
+                int lo = a, hi = nn1;
+                while (lo < hi) { const int mid = (lo + hi) >> 1; if (N1[mid] < kb) lo = mid + 1; else hi = mid; }
+                a = lo;
+            } else {
+                int lo = b, hi = nn2;
+                while (lo < hi) { const int mid = (lo + hi) >> 1; if (N2[mid] < ka) lo = mid + 1; else hi = mid; }
+                b = lo;
+            }
+        }
+        s_npairs = n;
+        s_count = 0;
+    }
+    __syncthreads();
+    const int npairs = s_npairs;
+    for (int q = wv; q < npairs; q += 4) {
+        const int2 pr = s_pairs[q];
+        const int k0 = min(max(O1[pr.x], 0), len1), k1 = min(max(O1[pr.x + 1], 0), len1);
+        const int f0 = min(max(O2[pr.y], 0), len2), nfn = min(max(O2[pr.y + 1], 0), len2) - f0;
+        for (int a = k0; a < k1; ++a) {
+            const int idx1 = __builtin_amdgcn_readfirstlane(I1[a]);
+            if (idx1 < 0 || idx1 >= n1 || !L1[idx1]) continue;  // not a keypoint / !pMP1 / isBad (:862-866)
+            const uint4* dk = reinterpret_cast<const uint4*>(D1 + (size_t)idx1 * 32);
+            const uint4 x0 = dk[0], x1 = dk[1];
+            BowBest bb{256, 0x7fffffff, 256};
+            for (int j = lane; j < nfn; j += 64) {
+                const int idx2 = I2[f0 + j];
+                if (idx2 < 0 || idx2 >= n2 || s_skip2[idx2]) continue;  // vbMatched2 || !pMP2 || isBad (:884-888)
+                const int d = hamming256(x0, x1, D2 + (size_t)idx2 * 32);
+                if (d < bb.b1) {
+                    bb.b2 = bb.b1;
+                    bb.b1 = d;
+                    bb.p1 = j;
+                } else if (d < bb.b2) {
+                    bb.b2 = d;
+                }
+            }
+            for (int s = 32; s > 0; s >>= 1) {
+                BowBest o;
+                o.b1 = __shfl_xor(bb.b1, s);
+                o.p1 = __shfl_xor(bb.p1, s);
+                o.b2 = __shfl_xor(bb.b2, s);
+                bb = bow_combine(bb, o);
+            }
+            if (lane == 0 && bb.b1 < kBowTHLow && (float)bb.b1 < nnratio * (float)bb.b2) {  // (:906-911)
+                const int bestIdx2 = I2[f0 + bb.p1];
+                s_m12[idx1] = bestIdx2;
+                s_skip2[bestIdx2] = 1;
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    __syncthreads();
+    // rotation histogram (:913-923) and ComputeThreeMaxima + filter (:942-960)
+    if (check_orientation) {
+        for (int i = tid; i < n1; i += 256) {
+            const int k = s_m12[i];
+            if (k < 0) continue;
+            atomicAdd(&s_hist[rot_bin(A1[i] - A2[k], kBowHisto)], 1);
+        }
+        __syncthreads();
+        if (tid == 0) three_maxima(s_hist, kBowHisto, s_keep);
+        __syncthreads();
+    }
+    int cnt = 0;
+    for (int i = tid; i < n1; i += 256) {
+        int k = s_m12[i];
+        if (k >= 0 && check_orientation) {
+            const int bin = rot_bin(A1[i] - A2[k], kBowHisto);
+            if (bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) k = -1;
+        }
+        matches12[(size_t)p * cap1 + i] = k;
+        cnt += k >= 0;
+    }
+    atomicAdd(&s_count, cnt);
+    __syncthreads();
+    if (tid == 0) nmatches[p] = s_count;
+}
+
+// matches12 rounded up to the int2 alignment of the node pairs
+static size_t bow_kf_smem(int cap1, int cap2, int node_cap) {
+    return (size_t)((cap1 + 1) & ~1) * 4 + (size_t)node_cap * 8 + (size_t)cap2;
+}
+
 }  // namespace plvi
 
 using namespace plvi;
@@ -282,4 +425,73 @@ extern "C" int plvi_search_by_bow(float nnratio, int check_orientation, const ui
     return plvi_search_by_bow_stereo(nnratio, check_orientation, kf_desc, kf_angle, kf_live, kf_n, kf_node, kf_off,
                                      kf_nnodes, kf_idx, f_desc, f_angle, f_n, f_node, f_off, f_nnodes, f_idx, -1,
                                      match_kf);
+}
+
+extern "C" int plvi_search_by_bow_kf_batch(int n_pairs, float nnratio, int check_orientation, int cap1, int cap2,
+                                           int node_cap, const uint8_t* d_desc1, const float* d_angle1,
+                                           const uint8_t* d_live1, const int* d_n1, const int* d_node1,
+                                           const int* d_off1, const int* d_nnodes1, const int* d_idx1,
+                                           const uint8_t* d_desc2, const float* d_angle2, const uint8_t* d_live2,
+                                           const int* d_n2, const int* d_node2, const int* d_off2,
+                                           const int* d_nnodes2, const int* d_idx2, int* d_matches12, int* d_nmatches,
+                                           void* stream) {
+    if (n_pairs < 0 || cap1 < 1 || cap2 < 1 || node_cap < 1) return PLVI_E_BADARG;
+    if (n_pairs == 0) return PLVI_OK;
+    if (!d_desc1 || !d_angle1 || !d_live1 || !d_n1 || !d_node1 || !d_off1 || !d_nnodes1 || !d_idx1 || !d_desc2 ||
+        !d_angle2 || !d_live2 || !d_n2 || !d_node2 || !d_off2 || !d_nnodes2 || !d_idx2 || !d_matches12 || !d_nmatches)
+        return PLVI_E_BADARG;
+    const size_t smem = bow_kf_smem(cap1, cap2, node_cap);
+    if (!lds_fits<search_by_bow_kf_kernel>(smem)) return PLVI_E_CAPACITY;
+    PLVI_CHECK(hipFuncSetAttribute((const void*)search_by_bow_kf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)smem));
+    hipLaunchKernelGGL(search_by_bow_kf_kernel, dim3(n_pairs), dim3(256), smem, (hipStream_t)stream, nnratio,
+                       check_orientation, cap1, cap2, node_cap, d_desc1, d_angle1, d_live1, d_n1, d_node1, d_off1,
+                       d_nnodes1, d_idx1, d_desc2, d_angle2, d_live2, d_n2, d_node2, d_off2, d_nnodes2, d_idx2,
+                       d_matches12, d_nmatches);
+    PLVI_CHECK(hipGetLastError());
+    return PLVI_OK;
+}
+
+// Single pair from host memory, synchronous.  Returns nmatches (>= 0) or an error.
+extern "C" int plvi_search_by_bow_kf(float nnratio, int check_orientation, const uint8_t* desc1, const float* angle1,
+                                     const uint8_t* live1, int n1, const int* node1, const int* off1, int nnodes1,
+                                     const int* idx1, const uint8_t* desc2, const float* angle2, const uint8_t* live2,
+                                     int n2, const int* node2, const int* off2, int nnodes2, const int* idx2,
+                                     int* matches12) {
+    if (n1 < 0 || n2 < 0 || nnodes1 < 0 || nnodes2 < 0) return PLVI_E_BADARG;
+    if (n1 > 0 && !matches12) return PLVI_E_BADARG;
+    if (n1 == 0 || n2 == 0) {  // nothing to match: vpMatches12 is all NULL
+        std::fill(matches12, matches12 + n1, -1);
+        return 0;
+    }
+    if (!desc1 || !angle1 || !live1 || !desc2 || !angle2 || !live2) return PLVI_E_BADARG;
+    if ((nnodes1 && (!node1 || !off1 || !idx1)) || (nnodes2 && (!node2 || !off2 || !idx2))) return PLVI_E_BADARG;
+    const int node_cap = std::max(std::max(nnodes1, nnodes2), 1);
+    const int len1 = nnodes1 ? off1[nnodes1] : 0, len2 = nnodes2 ? off2[nnodes2] : 0;
+    if (len1 < 0 || len1 > n1 || len2 < 0 || len2 > n2) return PLVI_E_BADARG;
+    HostStage h;
+    const size_t sCnt = h.put(5 * sizeof(int));
+    const size_t sD1 = h.put((size_t)n1 * 32), sA1 = h.put((size_t)n1 * 4), sL1 = h.put((size_t)n1);
+    const size_t sN1 = h.put((size_t)node_cap * 4), sO1 = h.put((size_t)(node_cap + 1) * 4);
+    const size_t sI1 = h.put((size_t)n1 * 4);
+    const size_t sD2 = h.put((size_t)n2 * 32), sA2 = h.put((size_t)n2 * 4), sL2 = h.put((size_t)n2);
+    const size_t sN2 = h.put((size_t)node_cap * 4), sO2 = h.put((size_t)(node_cap + 1) * 4);
+    const size_t sI2 = h.put((size_t)n2 * 4), sM = h.put((size_t)n1 * 4);
+    if (int rc = h.alloc(true)) return rc;
+    const int counts[5] = {n1, n2, nnodes1, nnodes2, 0};
+    if (h.up(sCnt, counts, sizeof(counts)) | h.up(sD1, desc1, (size_t)n1 * 32) | h.up(sA1, angle1, (size_t)n1 * 4) |
+        h.up(sL1, live1, (size_t)n1) | h.up(sN1, node1, (size_t)nnodes1 * 4) |
+        h.up(sO1, off1, nnodes1 ? (size_t)(nnodes1 + 1) * 4 : 0) | h.up(sI1, idx1, (size_t)len1 * 4) |
+        h.up(sD2, desc2, (size_t)n2 * 32) | h.up(sA2, angle2, (size_t)n2 * 4) | h.up(sL2, live2, (size_t)n2) |
+        h.up(sN2, node2, (size_t)nnodes2 * 4) | h.up(sO2, off2, nnodes2 ? (size_t)(nnodes2 + 1) * 4 : 0) |
+        h.up(sI2, idx2, (size_t)len2 * 4))
+        return PLVI_E_HIP;
+    int* cnt = h.at<int>(sCnt);
+    if (int rc = plvi_search_by_bow_kf_batch(1, nnratio, check_orientation, n1, n2, node_cap, h.at<uint8_t>(sD1),
+                                             h.at<float>(sA1), h.at<uint8_t>(sL1), cnt, h.at<int>(sN1),
+                                             h.at<int>(sO1), cnt + 2, h.at<int>(sI1), h.at<uint8_t>(sD2),
+                                             h.at<float>(sA2), h.at<uint8_t>(sL2), cnt + 1, h.at<int>(sN2),
+                                             h.at<int>(sO2), cnt + 3, h.at<int>(sI2), h.at<int>(sM), cnt + 4, nullptr))
+        return rc;
+    return h.finish(cnt + 4, matches12, sM, n1);
 }

@@ -7,6 +7,9 @@
 //     (src/ORBmatcher.cc:44-145, the local-map search)
 //   ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist)
 //     (src/ORBmatcher.cc:2180-2300, the relocalization guided search)
+//   ORBmatcher::SearchByProjection(KeyFrame*, Scw, vpPoints, [vpPointsKFs,]
+//     vpMatched, [vpMatchedKF,] th, ratioHamming) (src/ORBmatcher.cc:473-704,
+//     the two Sim3-guided searches of loop closing)
 // The pose product x3Dc = Rcw*x3Dw + tcw (cv::Mat float gemm) stays with the
 // caller (drop-in shim); everything after it runs here.
 //
@@ -662,6 +665,100 @@ __global__ __launch_bounds__(256) void search_reloc_kernel(
                               nmatches + pr, tid);
 }
 
+// ---------------------------------------------------------------------------
+// ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, vpPoints,
+// vpMatched, th, ratioHamming) (src/ORBmatcher.cc:473-586) and the overload
+// with vpPointsKFs / vpMatchedKF (:588-704), the loop-closing guided searches
+// (LoopClosing.cc:954, :1207 and :929).  The greedy two-phase schedule of the
+// relocalization matcher without a rotation filter: phase 1 finds every
+// point's best keypoint in parallel against vpMatched on entry; phase 2 walks
+// the points in order -- every assignment blocks its keypoint for the later
+// points (:558 / :675), so a point whose best was taken meanwhile is
+// re-scanned.  The two overloads differ in the projection only: :519 calls
+// Pinhole::project ((fx*x)/z + cx, no fused operation), :631-636 multiply by
+// 1/z and the reference object fuses fx*x + cx and fy*y + cy.
+__device__ unsigned sim3_scan(const plvi_sim3_proj_params& p, const GridSide& s, const unsigned char* blk, int i,
+                              const float* __restrict__ x3dc, const float* __restrict__ dist,
+                              const double* __restrict__ dot, const int* __restrict__ lvl,
+                              const uint8_t* __restrict__ mpdesc) {
+    const float xc = x3dc[3 * (size_t)i], yc = x3dc[3 * (size_t)i + 1], zc = x3dc[3 * (size_t)i + 2];
+    if (zc < 0.0f) return kScanSkip;  // depth must be positive (:511 / :627)
+    float u, v;
+    if (p.projection) {
+        const float invz = 1 / zc;
+        const float x = xc * invz, y = yc * invz;
+        u = rfmaf(x, p.fx, p.cx);
+        v = rfmaf(y, p.fy, p.cy);
+    } else {
+        u = p.fx * xc / zc + p.cx;
+        v = p.fy * yc / zc + p.cy;
+    }
+    // KeyFrame::IsInImage (KeyFrame.cc:1246-1249): the upper bounds are strict
+    if (!(u >= p.min_x && u < p.max_x && v >= p.min_y && v < p.max_y)) return kScanSkip;
+    const float d3 = dist[3 * (size_t)i], minDistance = dist[3 * (size_t)i + 1], maxDistance = dist[3 * (size_t)i + 2];
+    if (d3 < minDistance || d3 > maxDistance) return kScanSkip;
+    if (dot[i] < 0.5 * (double)d3) return kScanSkip;  // viewing angle (:537 / :654), a double compare
+    const int L = lvl[i];
+    if (L < 0 || L >= p.nlevels) return kScanSkip;  // PredictScale clamps to [0, mnScaleLevels)
+    const float radius = (float)p.th * p.scale_factors[L];
+    GridWindow w;
+    if (!grid_window(p.min_x, p.min_y, p.inv_w, p.inv_h, u, v, radius, w)) return kScanSkip;
+    BestOne best;
+    // kpLevel < L-1 || kpLevel > L (:563 / :680); KeyFrame::GetFeaturesInArea itself has no level filter
+    grid_walk(s, blk, w, u, v, radius, true, L - 1, L, mpdesc + (size_t)32 * i, NoReject{}, best);
+    if (best.idx < 0) return kScanSkip;
+    return scan_pack(best.dist, best.idx);
+}
+
+__global__ __launch_bounds__(256) void search_sim3_proj_kernel(
+    plvi_sim3_proj_params p, const plvi_keypoint* __restrict__ kps_all, const uint8_t* __restrict__ desc_all,
+    const int* __restrict__ kp_n, int kp_cap, const uint8_t* __restrict__ matched_all,
+    const int* __restrict__ cell_off_all, const int* __restrict__ cell_idx_all, const uint8_t* __restrict__ flags_all,
+    const float* __restrict__ x3dc_all, const float* __restrict__ dist_all, const double* __restrict__ dot_all,
+    const int* __restrict__ lvl_all, const uint8_t* __restrict__ mpdesc_all, const int* __restrict__ pt_n, int pt_cap,
+    int* __restrict__ match, int* __restrict__ nmatches) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    const int pr = blockIdx.x, tid = threadIdx.x;
+    const int np = max(min(pt_n[pr], pt_cap), 0);
+    GridSide s;
+    GridGaps g{{(size_t)4 * pt_cap, 0}, {}};
+    unsigned char* q = lds;
+    grid_side_load<false, true>(s, q, pr, kp_cap, kps_all, desc_all, kp_n, matched_all, cell_off_all, cell_idx_all, tid,
+                                &g);
+    unsigned* best = reinterpret_cast<unsigned*>(g.at[0]);  // [pt_cap]
+    __syncthreads();
+    const float* x3dc = x3dc_all + (size_t)pr * pt_cap * 3;
+    const float* dist = dist_all + (size_t)pr * pt_cap * 3;
+    const double* dot = dot_all + (size_t)pr * pt_cap;
+    const int* lvl = lvl_all + (size_t)pr * pt_cap;
+    const uint8_t* mpdesc = mpdesc_all + (size_t)pr * pt_cap * 32;
+    const uint8_t* fl = flags_all + (size_t)pr * pt_cap;
+    // phase 1: every point against vpMatched on entry
+    for (int i = tid; i < np; i += 256)
+        best[i] = (fl[i] & 1) ? sim3_scan(p, s, s.pre, i, x3dc, dist, dot, lvl, mpdesc) : kScanSkip;
+    __syncthreads();
+    // phase 2: the assignment in vpPoints order (:577-581 / :694-699)
+    if (tid == 0) {
+        const float thr = 50.0f * p.ratio_hamming;  // TH_LOW * ratioHamming, a float product
+        int nm = 0;
+        for (int i = 0; i < np; ++i) {
+            unsigned b = best[i];
+            if (b == kScanSkip) continue;
+            if (s.blocked[b & 0xFFFFu] != s.pre[b & 0xFFFFu])  // its best was taken meanwhile: re-scan
+                b = sim3_scan(p, s, s.blocked, i, x3dc, dist, dot, lvl, mpdesc);
+            if (b == kScanSkip || thr < (float)(int)(b >> 16)) continue;  // bestDist <= thr, as the object compares
+            const int i2 = (int)(b & 0xFFFFu);
+            s.assign[i2] = i;
+            s.blocked[i2] = 1;
+            ++nm;
+        }
+        nmatches[pr] = nm;
+    }
+    __syncthreads();
+    int* M = match + (size_t)pr * kp_cap;
+    for (int i = tid; i < s.n; i += 256) M[i] = s.assign[i];
+}
+
 // Dynamic LDS of the kernels above: grid_side_load's arrays per image (with
 // or without `nulled`), the per-point tables, 64 bytes of slack.
 static size_t side_smem(int cap, bool nulled) {
@@ -682,6 +779,8 @@ static size_t proj2_smem(int l_cap, int r_cap, int last_cap) {
 static size_t proj_smem(int cur_cap, int last_cap) {
     return side_smem(cur_cap, true) + (size_t)last_cap * (4 + 4) + 64;
 }
+
+static size_t sim3_smem(int kp_cap, int pt_cap) { return side_smem(kp_cap, false) + (size_t)pt_cap * 4 + 64; }
 
 // Launches a matcher kernel, one 256-thread block per pair with `smem` bytes
 // of dynamic LDS; PLVI_E_CAPACITY where that does not fit a CU.
@@ -830,6 +929,64 @@ extern "C" int plvi_search_reloc(const plvi_reloc_params* p, const plvi_keypoint
                                          st.at<uint8_t>(oMD), dN + 1, kc, st.at<int>(oM), dN + 2, nullptr))
         return rc;
     return st.finish(dN + 2, match, oM, n_cur);
+}
+
+// 50 * ratioHamming >= 256 would accept the bestDist = 256 of a search without
+// a candidate and index vpMatched[-1] in the reference (NaN refused too)
+static bool sim3_params_ok(const plvi_sim3_proj_params* p) {
+    return p && p->nlevels >= 1 && p->nlevels <= 16 && (p->projection == 0 || p->projection == 1) &&
+           50.0f * p->ratio_hamming < 256.0f;
+}
+
+extern "C" int plvi_search_sim3_projection_batch(int n_pairs, const plvi_sim3_proj_params* p,
+                                                 const plvi_keypoint* d_kps, const uint8_t* d_desc, const int* d_kp_n,
+                                                 int kp_cap, const uint8_t* d_matched, const int* d_cell_off,
+                                                 const int* d_cell_idx, const uint8_t* d_flags, const float* d_x3dc,
+                                                 const float* d_dist, const double* d_dot, const int* d_level,
+                                                 const uint8_t* d_mp_desc, const int* d_pt_n, int pt_cap, int* d_match,
+                                                 int* d_nmatches, void* stream) {
+    if (!sim3_params_ok(p) || n_pairs < 0 || kp_cap < 1 || pt_cap < 1 || kp_cap > 65535) return PLVI_E_BADARG;
+    if (n_pairs == 0) return PLVI_OK;
+    if (!d_kps || !d_desc || !d_kp_n || !d_cell_off || !d_cell_idx || !d_flags || !d_x3dc || !d_dist || !d_dot ||
+        !d_level || !d_mp_desc || !d_pt_n || !d_match || !d_nmatches)
+        return PLVI_E_BADARG;
+    return launch_matcher<search_sim3_proj_kernel>(n_pairs, sim3_smem(kp_cap, pt_cap), stream, *p, d_kps, d_desc,
+                                                   d_kp_n, kp_cap, d_matched, d_cell_off, d_cell_idx, d_flags, d_x3dc,
+                                                   d_dist, d_dot, d_level, d_mp_desc, d_pt_n, pt_cap, d_match,
+                                                   d_nmatches);
+}
+
+// One pair from host memory, synchronous (grid built on the device).
+extern "C" int plvi_search_sim3_projection(const plvi_sim3_proj_params* p, const plvi_keypoint* kps,
+                                           const uint8_t* desc, int n_kp, const uint8_t* matched, const uint8_t* flags,
+                                           const float* x3dc, const float* dist, const double* dot, const int* level,
+                                           const uint8_t* mp_desc, int n_pt, int* match) {
+    if (!sim3_params_ok(p) || n_kp < 0 || n_pt < 0 || (n_kp > 0 && (!kps || !desc || !match))) return PLVI_E_BADARG;
+    if (n_pt > 0 && (!flags || !x3dc || !dist || !dot || !level || !mp_desc)) return PLVI_E_BADARG;
+    if (n_kp == 0) return 0;
+    const int kc = n_kp, pc = std::max(n_pt, 1);
+    HostStage st;
+    const size_t oK = st.put(sizeof(plvi_keypoint) * kc), oD = st.put(32 * (size_t)kc), oB = st.put(kc);
+    const size_t oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)kc), oF = st.put(pc);
+    const size_t oX = st.put(12 * (size_t)pc), oS = st.put(12 * (size_t)pc), oT = st.put(8 * (size_t)pc);
+    const size_t oL = st.put(4 * (size_t)pc), oMD = st.put(32 * (size_t)pc), oM = st.put(4 * (size_t)kc);
+    const size_t oN = st.put(16);
+    if (st.alloc()) return PLVI_E_HIP;
+    const int counts[2] = {n_kp, n_pt};
+    if (st.up(oK, kps, sizeof(plvi_keypoint) * kc) | st.up(oD, desc, 32 * (size_t)kc) |
+        st.up_or_zero(oB, matched, kc) | st.up(oF, flags, n_pt) | st.up(oX, x3dc, 12 * (size_t)n_pt) |
+        st.up(oS, dist, 12 * (size_t)n_pt) | st.up(oT, dot, 8 * (size_t)n_pt) | st.up(oL, level, 4 * (size_t)n_pt) |
+        st.up(oMD, mp_desc, 32 * (size_t)n_pt) | st.up(oN, counts, sizeof counts))
+        return PLVI_E_HIP;
+    int* dN = st.at<int>(oN);
+    if (int rc = stage_grid(st, p, oK, dN, kc, oCO, oCI)) return rc;
+    if (int rc = plvi_search_sim3_projection_batch(1, p, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, kc,
+                                                   st.at<uint8_t>(oB), st.at<int>(oCO), st.at<int>(oCI),
+                                                   st.at<uint8_t>(oF), st.at<float>(oX), st.at<float>(oS),
+                                                   st.at<double>(oT), st.at<int>(oL), st.at<uint8_t>(oMD), dN + 1, pc,
+                                                   st.at<int>(oM), dN + 2, nullptr))
+        return rc;
+    return st.finish(dN + 2, match, oM, n_kp);
 }
 
 extern "C" int plvi_search_local_batch(int n_frames, const plvi_local_params* p, const plvi_keypoint* d_kps,

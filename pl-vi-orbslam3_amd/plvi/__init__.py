@@ -155,6 +155,16 @@ class RelocParams(ctypes.Structure):
                 ("nlevels", ctypes.c_int), ("scale_factors", ctypes.c_float * 16)]
 
 
+class Sim3ProjParams(ctypes.Structure):
+    """plvi_sim3_proj_params (include/plvi_frontend.h): ORBmatcher::SearchByProjection(KeyFrame*, Scw, vpPoints,
+    [vpPointsKFs,] vpMatched, [vpMatchedKF,] th, ratioHamming); projection 0 / 1 = the :473 / :588 overload."""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("min_x", ctypes.c_float), ("max_x", ctypes.c_float), ("min_y", ctypes.c_float),
+                ("max_y", ctypes.c_float), ("inv_w", ctypes.c_float), ("inv_h", ctypes.c_float),
+                ("th", ctypes.c_int), ("ratio_hamming", ctypes.c_float), ("projection", ctypes.c_int),
+                ("nlevels", ctypes.c_int), ("scale_factors", ctypes.c_float * 16)]
+
+
 class LineProjParams(ctypes.Structure):
     """plvi_line_proj_params (include/plvi_frontend.h): LineMatcher::SearchByProjection."""
     _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
@@ -348,6 +358,10 @@ def _declare(lib):
         "plvi_search_for_triangulation_batch": ([I, V, I, I, I, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V,
                                                  V, V, V], I),
         "plvi_search_for_triangulation": ([V, V, V, I, V, V, I, V, V, V, V, V, I, V, V, I, V, V, V, V], I),
+        "plvi_search_by_bow_kf_batch": ([I, F, I, I, I, I, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V, V], I),
+        "plvi_search_by_bow_kf": ([F, I, V, V, V, I, V, V, I, V, V, V, V, I, V, V, I, V, V], I),
+        "plvi_search_sim3_projection_batch": ([I, V, V, V, V, I, V, V, V, V, V, V, V, V, V, V, I, V, V, V], I),
+        "plvi_search_sim3_projection": ([V, V, V, I, V, V, V, V, V, V, V, I, V], I),
         "plvi_search_local_batch": ([I, V, V, V, V, I, V, V, V, V, V, V, V, V, V, I, V, V, V], I),
         "plvi_search_local": ([V, V, V, I, V, V, V, V, V, V, I, V], I),
         "plvi_search_by_projection_stereo_batch": ([I, V, V, V, V, V, I, V, V, V, V, V, V, I, V, V, V, V, V, V, V, V,
@@ -950,6 +964,30 @@ class ORBmatcher:
                    "plvi_search_by_bow_stereo")
         return n, out[:len(fd)]
 
+    def SearchByBoWKF(self, desc1, angle1, live1, featvec1, desc2, angle2, live2, featvec2):
+        """SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12)
+        (src/ORBmatcher.cc:823-963), single-camera branch.  Per side: mDescriptors, mvKeysUn angles, live[i] =
+        GetMapPointMatches()[i] is non-NULL and not bad, mFeatVec as {node: [indices]}.  Returns (nmatches,
+        matches12) with matches12[idx1] = the KF2 keypoint index whose MapPoint goes to vpMatches12[idx1], or -1."""
+        d1 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32)
+        d2 = np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
+        a1 = np.ascontiguousarray(angle1, np.float32)
+        a2 = np.ascontiguousarray(angle2, np.float32)
+        l1 = np.ascontiguousarray(live1, np.uint8)
+        l2 = np.ascontiguousarray(live2, np.uint8)
+        n1, n2 = len(d1), len(d2)
+        _same_len(n1, angle1=a1, live1=l1)
+        _same_len(n2, angle2=a2, live2=l2)
+        a, ao, ai = feature_vector_csr(featvec1)
+        b, bo, bi = feature_vector_csr(featvec2)
+        out = np.full(max(n1, 1), -1, np.int32)
+        n = _check(self._lib.plvi_search_by_bow_kf(self.nnratio, int(self.check_orientation), _ptr(d1), _ptr(a1),
+                                                   _ptr(l1), n1, _ptr(a), _ptr(ao), len(a), _ptr(ai), _ptr(d2),
+                                                   _ptr(a2), _ptr(l2), n2, _ptr(b), _ptr(bo), len(b), _ptr(bi),
+                                                   _ptr(out)),
+                   "plvi_search_by_bow_kf")
+        return n, out[:n1]
+
     def SearchForTriangulation(self, kps1, desc1, featvec1, has_point1, uright1, kps2, desc2, featvec2, has_point2,
                                uright2, F12, ep, sigma2, scale_factors, bOnlyStereo=False, bCoarse=False):
         """SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse)
@@ -1119,6 +1157,36 @@ class ORBmatcher:
                                                 None if cb is None else _ptr(cb), _ptr(fl), _ptr(x3), _ptr(ds),
                                                 _ptr(lv), _ptr(ka), _ptr(md), len(fl), _ptr(out)),
                     "plvi_search_reloc")
+        return nm, out[:n]
+
+    def SearchByProjectionSim3(self, params, kps, desc, flags, x3dc, dist, dot, level, mp_desc, matched=None,
+                               projection=0):
+        """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (src/ORBmatcher.cc:473-586,
+        projection=0) and the overload with vpPointsKFs / vpMatchedKF (:588-704, projection=1), the loop-closing
+        guided searches.  params: Sim3ProjParams (camera, bounds, grid, th, ratio_hamming, scale factors; its
+        projection field is set from the argument); kps: pKF->mvKeysUn; matched: vpMatched[idx] != NULL on entry;
+        per candidate MapPoint (vpPoints order): flags (bit0 = not bad and not in spAlreadyFound), x3dc (n x 3,
+        Rcw*p3Dw + tcw), dist (n x 3: |p3Dw - Ow|, min / max distance invariance), dot (float64, PO.dot(Pn)), level
+        (PredictScale), descriptor.  Returns (nmatches, match) with match[idx] = the point index stored in
+        vpMatched[idx] by this call, or -1; vpMatchedKF[idx] is vpPointsKFs[match[idx]]."""
+        params.projection = int(projection)
+        k = np.ascontiguousarray(kps).view(KEYPOINT_DTYPE)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n = len(k)
+        fl = np.ascontiguousarray(flags, np.uint8)
+        x3 = np.ascontiguousarray(x3dc, np.float32).reshape(-1, 3)
+        ds = np.ascontiguousarray(dist, np.float32).reshape(-1, 3)
+        dt = np.ascontiguousarray(dot, np.float64)
+        lv = np.ascontiguousarray(level, np.int32)
+        md = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)
+        _same_len(n, desc=d)
+        _same_len(len(fl), x3dc=x3, dist=ds, dot=dt, level=lv, mp_desc=md)
+        mb = None if matched is None else np.ascontiguousarray(matched, np.uint8)
+        out = np.full(max(n, 1), -1, np.int32)
+        nm = _check(self._lib.plvi_search_sim3_projection(ctypes.byref(params), _ptr(k), _ptr(d), n,
+                                                          None if mb is None else _ptr(mb), _ptr(fl), _ptr(x3),
+                                                          _ptr(ds), _ptr(dt), _ptr(lv), _ptr(md), len(fl), _ptr(out)),
+                    "plvi_search_sim3_projection")
         return nm, out[:n]
 
     @staticmethod
@@ -1393,6 +1461,37 @@ def search_for_triangulation_batch(n_pairs, d_pairs, cap1, cap2, node_cap, kf1, 
                                                       *[V(x) for x in kf1], *[V(x) for x in kf2], V(d_matches12),
                                                       V(d_nmatches), V(stream or 0)),
            "plvi_search_for_triangulation_batch")
+
+
+def search_by_bow_kf_batch(n_pairs, nnratio, check_orientation, cap1, cap2, node_cap, kf1, kf2, d_matches12,
+                           d_nmatches, stream=None):
+    """ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*) over device pair tables (plvi_search_by_bow_kf_batch).
+    kf1 / kf2: the eight device pointers of one side in header order (desc, angle, live, n, node, off, nnodes,
+    idx)."""
+    V = ctypes.c_void_p
+    if len(kf1) != 8 or len(kf2) != 8:
+        raise ValueError("kf1 / kf2: eight device pointers each")
+    _check(load().plvi_search_by_bow_kf_batch(n_pairs, float(nnratio), int(check_orientation), cap1, cap2, node_cap,
+                                              *[V(x) for x in kf1], *[V(x) for x in kf2], V(d_matches12),
+                                              V(d_nmatches), V(stream or 0)),
+           "plvi_search_by_bow_kf_batch")
+
+
+def search_sim3_projection_batch(n_pairs, params, kf, kp_cap, points, pt_cap, d_match, d_nmatches, stream=None):
+    """Both ORBmatcher::SearchByProjection(pKF, Scw, ...) overloads over device tables
+    (plvi_search_sim3_projection_batch).  params: Sim3ProjParams; kf: the six device pointers of the keyframe
+    side in header order (kps, desc, n, matched (0 = none), cell_off, cell_idx); points: the seven of the point
+    side (flags, x3dc, dist, dot, level, desc, n)."""
+    V = ctypes.c_void_p
+    if len(kf) != 6 or len(points) != 7:
+        raise ValueError("kf: six device pointers, points: seven")
+    kps, desc, n, matched, cell_off, cell_idx = kf
+    flags, x3dc, dist, dot, level, mp_desc, pt_n = points
+    _check(load().plvi_search_sim3_projection_batch(n_pairs, ctypes.byref(params), V(kps), V(desc), V(n), kp_cap,
+                                                    V(matched or 0), V(cell_off), V(cell_idx), V(flags), V(x3dc),
+                                                    V(dist), V(dot), V(level), V(mp_desc), V(pt_n), pt_cap,
+                                                    V(d_match), V(d_nmatches), V(stream or 0)),
+           "plvi_search_sim3_projection_batch")
 
 
 def line_search_init(desc1, desc2):
