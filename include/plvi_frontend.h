@@ -820,6 +820,147 @@ int plvi_search_sim3_projection(const plvi_sim3_proj_params* p, const plvi_keypo
                                 const float* dist, const double* dot, const int* level, const uint8_t* mp_desc,
                                 int n_pt, int* match);
 
+/* ------------------------------------------------------------------ Fuse
+ * ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, th,
+ * bRight = false) (src/ORBmatcher.cc:1399-1610; LocalMapping.cc:1383 / :1434
+ * per neighbour and back, LoopClosing.cc:3515 / :3573) -- mode 0 -- and
+ * ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, vpPoints, th, vpReplacePoint)
+ * (:1612-1734; LoopClosing::SearchAndFuse) -- mode 1 --, as a pure search:
+ * inside one call bestIdx / bestDist of a point depend only on the pose
+ * product, the keyframe's immutable tables (mvKeysUn, mvuRight, mDescriptors,
+ * the grid) and the point's own data; the map mutation (GetMapPoint, Replace,
+ * AddObservation, AddMapPoint, vpReplacePoint) starts after the search and
+ * stays with the caller, which replays it in list order.
+ * Single-camera keyframe only: NLeft == -1, bRight == false, mvKeysUn.
+ * The caller provides, per candidate MapPoint i in list order,
+ *   flags bit0 = mode 0: pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF) on
+ *                entry (:1435-1452); mode 1: !pMP->isBad() &&
+ *                !spAlreadyFound.count(pMP) (:1640);
+ *   x3dc [3]   = Rcw*p3Dw + tcw (:1456 / :1647; mode 1 with the Rcw, tcw of
+ *                the decomposed Scw, :1621-1625);
+ *   dist [3]   = { cv::norm(p3Dw - Ow) as float, GetMinDistanceInvariance(),
+ *                  GetMaxDistanceInvariance() };
+ *   dot        = PO.dot(Pn) (cv::Mat::dot returns double; compared in double);
+ *   level      = pMP->PredictScale(dist3D, pKF);  desc = pMP->GetDescriptor().
+ * The device does the rest, bit-exact with the reference build: z < 0.0f
+ * skips; Pinhole::project, (fx*x)/z + cx, no fused operation; KeyFrame::
+ * IsInImage (strict upper bounds); dist < min || dist > max skips; dot <
+ * 0.5 * (double)dist skips; a level outside [0, nlevels) gets no candidate;
+ * radius = th * mvScaleFactors[level] with th a float; KeyFrame::
+ * GetFeaturesInArea(u, v, radius) (no level filter inside); the octave must
+ * lie in [level-1, level]; mode 0 only, the reprojection gate (:1533-1557)
+ * with ur = fma(-bf, invz, u): where mvuRight[idx] >= 0, e2 = fma(er, er,
+ * fma(ex, ex, ey*ey)) and (double)(e2 * mvInvLevelSigma2[octave]) > 7.8
+ * skips, otherwise e2 = fma(ex, ex, ey*ey) against 5.99 (the fused sites are
+ * the reference object's, tests/test_ref_objects_fuse.py; a keypoint with a
+ * negative octave, for which the reference would read mvInvLevelSigma2[-1],
+ * is no candidate in mode 0); the first keypoint with the smallest distance
+ * wins; accepted when bestDist <= TH_LOW = 50.  bestDist starts at 256 in
+ * mode 0 and INT_MAX in mode 1, which differs only for a lone candidate at
+ * distance 256 -- rejected either way, hence one output convention:
+ *   fuse_idx[i]  = the accepted keypoint index (bestIdx), else -1;
+ *   fuse_dist[i] = its distance, else -1;
+ *   nfused       = the number of accepted rows = the return value when no
+ *                  flag changes during the call. */
+#define PLVI_FUSE_CHUNK 64 /* candidates per workgroup of the two Fuse kernels */
+
+typedef struct plvi_fuse_params {
+  float fx, fy, cx, cy;             /* pKF->fx, fy, cx, cy (Pinhole mvParameters) */
+  float min_x, max_x, min_y, max_y; /* pKF->mnMinX, mnMaxX, mnMinY, mnMaxY (ints in KeyFrame, compared as float) */
+  float inv_w, inv_h;               /* pKF->mfGridElementWidthInv / HeightInv */
+  float th;                         /* th, a float here (SearchByProjection(pKF, Scw, ...) has an int) */
+  float bf;                         /* pKF->mbf (mode 0) */
+  int mode;                         /* 0: Fuse(pKF, vpMapPoints, th), 1: Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) */
+  int nlevels;                      /* pKF->mnScaleLevels, in [1, 16] */
+  float scale_factors[16];          /* pKF->mvScaleFactors */
+  float inv_level_sigma2[16];       /* pKF->mvInvLevelSigma2 (mode 0) */
+} plvi_fuse_params;
+
+/* Batched over n_pairs (KeyFrame, point list) pairs, tables laid out as in
+ * plvi_search_sim3_projection_batch.  KeyFrame p: keypoints / descriptors
+ * [p][kp_cap] (counts d_kp_n), the grid CSR from plvi_assign_grid_batch,
+ * d_uright [p][kp_cap] = pKF->mvuRight (NULL = monocular: every entry
+ * negative; not read in mode 1).  Points p: [p][pt_cap] flags, x3dc [3],
+ * dist [3], dot (double), level, desc [32] (counts d_pt_n).  Outputs
+ * fuse_idx / fuse_dist [p][pt_cap], rows [0, pt_n) fully written; nfused [p]
+ * is written by the call (the caller does not zero it).
+ * The kernel runs one workgroup per PLVI_FUSE_CHUNK points of a pair (grid =
+ * point chunks x pairs) and reads the keyframe side through L2, so neither
+ * capacity is bounded by LDS: kp_cap <= 65535 (PLVI_E_BADARG beyond, as
+ * elsewhere); a launch of more than 2^31 - 1 workgroups (chunks of pt_cap
+ * times n_pairs) returns PLVI_E_CAPACITY and nothing is launched.  d_kp_n /
+ * d_pt_n follow the count contract (plvi_hamming_knn2_batch), clamped to
+ * [0, cap]; a grid entry outside [0, kp_n) is ignored.  Asynchronous on
+ * `stream`.  Replaces ORBmatcher.h:85 and :88 (the two Fuse overloads). */
+int plvi_fuse_points_batch(int n_pairs, const plvi_fuse_params* p, const plvi_keypoint* d_kps, const uint8_t* d_desc,
+                           const int* d_kp_n, int kp_cap, const float* d_uright, const int* d_cell_off,
+                           const int* d_cell_idx, const uint8_t* d_flags, const float* d_x3dc, const float* d_dist,
+                           const double* d_dot, const int* d_level, const uint8_t* d_mp_desc, const int* d_pt_n,
+                           int pt_cap, int* d_fuse_idx, int* d_fuse_dist, int* d_nfused, void* stream);
+
+/* One pair from host memory, synchronous (grid built on the device, so
+ * n_kp <= 8192 as in plvi_assign_grid_batch; PLVI_E_BADARG beyond).
+ * fuse_idx / fuse_dist [n_pt]; returns nfused (>= 0) or an error.  n_pt == 0
+ * returns 0; n_kp == 0 writes -1 everywhere and returns 0; neither launches. */
+int plvi_fuse_points(const plvi_fuse_params* p, const plvi_keypoint* kps, const uint8_t* desc, int n_kp,
+                     const float* uright, const uint8_t* flags, const float* x3dc, const float* dist,
+                     const double* dot, const int* level, const uint8_t* mp_desc, int n_pt, int* fuse_idx,
+                     int* fuse_dist);
+
+/* LineMatcher::Fuse(KeyFrame* pKF, const vector<MapLine*>& vpMapLines, th)
+ * (src/LineMatcher.cpp:373-485; LocalMapping.cc:1412 / :1452, LoopClosing.cc
+ * :3555 / :3595), the same split.  The caller provides, per MapLine i,
+ *   flags bit0 = pML && !pML->isBad() (:390);
+ *   spc [3], epc [3] = Rcw*SP + tcw, Rcw*EP + tcw (:398, :403);
+ *   dist [3]   = { cv::norm(0.5*(SP+EP) - Ow) as float, min, max invariance };
+ *   dot        = OM.dot(pn) (double);  level = pML->PredictScale(dist,
+ *                pKF->mfLogScaleFactor);  desc = pML->GetDescriptor().
+ * The device: either z < 0.0f skips; invz = 1.0f/z, u = fma(fx*X, invz, cx)
+ * (the reference object fuses the second product of each of the four sums);
+ * u < mnMinX || u > mnMaxX skips, likewise v -- both ends inclusive, not
+ * IsInImage --, endpoint 1 before endpoint 2; the distance and viewing-angle
+ * tests as for points; a level outside [0, nlevels) gets no candidate;
+ * r = th * pKF->mvScaleFactors[level] (the ORB scale factors, as the
+ * reference indexes); KeyFrame::GetLinesInArea(u1, v1, u2, v2, r)
+ * (KeyFrame.cc:1170-1198) with the header's default levels -1 / -1, i.e. no
+ * level filter: a scan of every keyline in index order with, as
+ * KeyFrame.cc.o computes them, dx = fma(0.5, (double)(u1 + u2), -pt.x), dy
+ * likewise, (float)fma(dx, dx, dy*dy) > r*r (float) skips, and
+ * (double)((v1 - v2)/(u1 - u2) - angle) > (double)r * 0.01 skips -- no
+ * absolute value, and u1 == u2 gives +-inf or NaN (NaN passes): both are the
+ * reference's behaviour and stay; the octave must lie in [level-1, level];
+ * LineMatcher::DescriptorDistance with its >> 25 quirk; the first minimum
+ * wins (bestDist starts at INT_MAX); accepted when bestDist <= 50.  Outputs
+ * as for points, fuse_idx = the keyline index. */
+typedef struct plvi_fuse_line_params {
+  float fx, fy, cx, cy;             /* pKF->fx, fy, cx, cy */
+  float min_x, max_x, min_y, max_y; /* pKF->mnMinX, mnMaxX, mnMinY, mnMaxY */
+  float th;
+  int nlevels;                      /* pKF->mnScaleLevels, in [1, 16] */
+  float scale_factors[16];          /* pKF->mvScaleFactors */
+} plvi_fuse_line_params;
+
+/* Batched: KeyFrame p = the 68-byte KeyLine rows and LBD descriptors
+ * [p][kl_cap] (pKF->mvKeys_Line, mDescriptors_l; counts d_kl_n); MapLines p =
+ * [p][ml_cap] tables as above (counts d_ml_n).  One workgroup per
+ * PLVI_FUSE_CHUNK MapLines of a pair stages the keyframe's pt, angle, octave
+ * and descriptors in LDS: 48 * kl_cap bytes, which with the kernel's static
+ * data must fit the 160 KB of a CU (kl_cap <= 3413); a larger table, or a
+ * launch of more than 2^31 - 1 workgroups, returns PLVI_E_CAPACITY and
+ * nothing is launched.  Counts are clamped to [0, cap]; nfused [p] is written
+ * by the call.  Asynchronous on `stream`.  Replaces LineMatcher.h:105. */
+int plvi_fuse_lines_batch(int n_pairs, const plvi_fuse_line_params* p, const plvi_keyline* d_kl,
+                          const uint8_t* d_kl_desc, const int* d_kl_n, int kl_cap, const uint8_t* d_flags,
+                          const float* d_spc, const float* d_epc, const float* d_dist, const double* d_dot,
+                          const int* d_level, const uint8_t* d_ml_desc, const int* d_ml_n, int ml_cap,
+                          int* d_fuse_idx, int* d_fuse_dist, int* d_nfused, void* stream);
+
+/* One pair from host memory, synchronous.  fuse_idx / fuse_dist [n_ml];
+ * returns nfused (>= 0) or an error; n_ml == 0 or n_kl == 0 as above. */
+int plvi_fuse_lines(const plvi_fuse_line_params* p, const plvi_keyline* kl, const uint8_t* kl_desc, int n_kl,
+                    const uint8_t* flags, const float* spc, const float* epc, const float* dist, const double* dot,
+                    const int* level, const uint8_t* ml_desc, int n_ml, int* fuse_idx, int* fuse_dist);
+
 /* ORBmatcher::SearchByProjection(Frame& F, const vector<MapPoint*>&
  * vpMapPoints, th, bFarPoints, thFarPoints) (src/ORBmatcher.cc:44-145,
  * F.Nleft == -1, RadiusByViewingCos :216-222): the local-map search of
@@ -1184,8 +1325,8 @@ int plvi_stereo_frame_extract_batch(plvi_orb_extractor* orb_left, plvi_orb_extra
  * histogram filter.
  * Out of scope: the KannalaBrandt8 / two-camera branch (:994-1003,
  * :1099-1129; its epipolarConstrain is TriangulateMatches with an OpenCV SVD,
- * VERDICT.md), the overload with vMatchedPoints (:1208), Fuse and
- * SearchBySim3. */
+ * VERDICT.md), the overload with vMatchedPoints (:1208) and SearchBySim3.
+ * (Fuse is plvi_fuse_points / plvi_fuse_lines above.) */
 typedef struct plvi_triangulation_pair {
   float F12[9];
   float ep[2];

@@ -165,6 +165,27 @@ class Sim3ProjParams(ctypes.Structure):
                 ("nlevels", ctypes.c_int), ("scale_factors", ctypes.c_float * 16)]
 
 
+class FuseParams(ctypes.Structure):
+    """plvi_fuse_params (include/plvi_frontend.h): the two ORBmatcher::Fuse overloads; mode 0 / 1 = Fuse(pKF,
+    vpMapPoints, th) / Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)."""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("min_x", ctypes.c_float), ("max_x", ctypes.c_float), ("min_y", ctypes.c_float),
+                ("max_y", ctypes.c_float), ("inv_w", ctypes.c_float), ("inv_h", ctypes.c_float),
+                ("th", ctypes.c_float), ("bf", ctypes.c_float), ("mode", ctypes.c_int), ("nlevels", ctypes.c_int),
+                ("scale_factors", ctypes.c_float * 16), ("inv_level_sigma2", ctypes.c_float * 16)]
+
+
+class FuseLineParams(ctypes.Structure):
+    """plvi_fuse_line_params (include/plvi_frontend.h): LineMatcher::Fuse."""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("min_x", ctypes.c_float), ("max_x", ctypes.c_float), ("min_y", ctypes.c_float),
+                ("max_y", ctypes.c_float), ("th", ctypes.c_float), ("nlevels", ctypes.c_int),
+                ("scale_factors", ctypes.c_float * 16)]
+
+
+FUSE_CHUNK = 64  # PLVI_FUSE_CHUNK: candidates per workgroup of the two Fuse kernels
+
+
 class LineProjParams(ctypes.Structure):
     """plvi_line_proj_params (include/plvi_frontend.h): LineMatcher::SearchByProjection."""
     _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
@@ -362,6 +383,10 @@ def _declare(lib):
         "plvi_search_by_bow_kf": ([F, I, V, V, V, I, V, V, I, V, V, V, V, I, V, V, I, V, V], I),
         "plvi_search_sim3_projection_batch": ([I, V, V, V, V, I, V, V, V, V, V, V, V, V, V, V, I, V, V, V], I),
         "plvi_search_sim3_projection": ([V, V, V, I, V, V, V, V, V, V, V, I, V], I),
+        "plvi_fuse_points_batch": ([I, V, V, V, V, I, V, V, V, V, V, V, V, V, V, V, I, V, V, V, V], I),
+        "plvi_fuse_points": ([V, V, V, I, V, V, V, V, V, V, V, I, V, V], I),
+        "plvi_fuse_lines_batch": ([I, V, V, V, V, I, V, V, V, V, V, V, V, V, I, V, V, V, V], I),
+        "plvi_fuse_lines": ([V, V, V, I, V, V, V, V, V, V, V, I, V, V], I),
         "plvi_search_local_batch": ([I, V, V, V, V, I, V, V, V, V, V, V, V, V, V, I, V, V, V], I),
         "plvi_search_local": ([V, V, V, I, V, V, V, V, V, V, I, V], I),
         "plvi_search_by_projection_stereo_batch": ([I, V, V, V, V, V, I, V, V, V, V, V, V, I, V, V, V, V, V, V, V, V,
@@ -878,6 +903,32 @@ class LineMatcher:
         return n, out[:len(ca)]
 
     @staticmethod
+    def Fuse(params, keylines, kl_desc, flags, spc, epc, dist, dot, level, ml_desc):
+        """LineMatcher::Fuse(pKF, vpMapLines, th) (src/LineMatcher.cpp:373-485) as a pure search.  params:
+        FuseLineParams; keylines: pKF->mvKeys_Line (KEYLINE_DTYPE) with mDescriptors_l; per MapLine (list order):
+        flags (bit0 = non-NULL and not bad), spc / epc (n x 3, Rcw*SP + tcw, Rcw*EP + tcw), dist (n x 3: |0.5*(SP+EP)
+        - Ow|, min / max distance invariance), dot (float64, OM.dot(pn)), level (PredictScale), descriptor.  Returns
+        (nfused, fuse_idx, fuse_dist): the accepted keyline index and its distance per MapLine, else -1 / -1."""
+        kl = np.ascontiguousarray(keylines).view(KEYLINE_DTYPE)
+        kd = np.ascontiguousarray(kl_desc, np.uint8).reshape(-1, 32)
+        fl = np.ascontiguousarray(flags, np.uint8)
+        sp = np.ascontiguousarray(spc, np.float32).reshape(-1, 3)
+        ep = np.ascontiguousarray(epc, np.float32).reshape(-1, 3)
+        ds = np.ascontiguousarray(dist, np.float32).reshape(-1, 3)
+        dt = np.ascontiguousarray(dot, np.float64)
+        lv = np.ascontiguousarray(level, np.int32)
+        md = np.ascontiguousarray(ml_desc, np.uint8).reshape(-1, 32)
+        _same_len(len(kl), kl_desc=kd)
+        _same_len(len(fl), spc=sp, epc=ep, dist=ds, dot=dt, level=lv, ml_desc=md)
+        n = len(fl)
+        oi = np.full(max(n, 1), -1, np.int32)
+        od = np.full(max(n, 1), -1, np.int32)
+        nf = _check(load().plvi_fuse_lines(ctypes.byref(params), _ptr(kl), _ptr(kd), len(kl), _ptr(fl), _ptr(sp),
+                                           _ptr(ep), _ptr(ds), _ptr(dt), _ptr(lv), _ptr(md), n, _ptr(oi), _ptr(od)),
+                    "plvi_fuse_lines")
+        return nf, oi[:n], od[:n]
+
+    @staticmethod
     def SearchForTriangulation(desc1, desc2, has_line1, has_line2):
         """SearchForTriangulation(pKF1, pKF2, vMatchedPairs) (src/LineMatcher.cpp:142-171): has_line =
         GetMapLine(i) != NULL per line.  Returns (nmatches, vMatchedPairs as an n x 2 int array (query, train),
@@ -1189,6 +1240,44 @@ class ORBmatcher:
                     "plvi_search_sim3_projection")
         return nm, out[:n]
 
+    def _fuse(self, mode, params, kps, desc, flags, x3dc, dist, dot, level, mp_desc, uright):
+        params.mode = mode
+        k = np.ascontiguousarray(kps).view(KEYPOINT_DTYPE)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        fl = np.ascontiguousarray(flags, np.uint8)
+        x3 = np.ascontiguousarray(x3dc, np.float32).reshape(-1, 3)
+        ds = np.ascontiguousarray(dist, np.float32).reshape(-1, 3)
+        dt = np.ascontiguousarray(dot, np.float64)
+        lv = np.ascontiguousarray(level, np.int32)
+        md = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)
+        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+        _same_len(len(k), desc=d, **({} if ur is None else {"uright": ur}))
+        _same_len(len(fl), x3dc=x3, dist=ds, dot=dt, level=lv, mp_desc=md)
+        n = len(fl)
+        oi = np.full(max(n, 1), -1, np.int32)
+        od = np.full(max(n, 1), -1, np.int32)
+        nf = _check(self._lib.plvi_fuse_points(ctypes.byref(params), _ptr(k), _ptr(d), len(k),
+                                               None if ur is None else _ptr(ur), _ptr(fl), _ptr(x3), _ptr(ds),
+                                               _ptr(dt), _ptr(lv), _ptr(md), n, _ptr(oi), _ptr(od)),
+                    "plvi_fuse_points")
+        return nf, oi[:n], od[:n]
+
+    def Fuse(self, params, kps, desc, flags, x3dc, dist, dot, level, mp_desc, uright=None):
+        """Fuse(pKF, vpMapPoints, th, bRight=false) (src/ORBmatcher.cc:1399-1610) as a pure search.  params:
+        FuseParams (camera, bounds, grid, th, bf, scale factors, mvInvLevelSigma2; its mode field is set here); kps:
+        pKF->mvKeysUn with mDescriptors; uright: pKF->mvuRight (None = monocular); per candidate MapPoint (list
+        order): flags (bit0 = non-NULL, not bad and not in pKF on entry), x3dc (n x 3, Rcw*p3Dw + tcw), dist (n x 3:
+        |p3Dw - Ow|, min / max distance invariance), dot (float64, PO.dot(Pn)), level (PredictScale), descriptor.
+        Returns (nfused, fuse_idx, fuse_dist): per point the accepted keypoint index (bestIdx) and its distance,
+        else -1 / -1; the caller replays the map mutation in list order."""
+        return self._fuse(0, params, kps, desc, flags, x3dc, dist, dot, level, mp_desc, uright)
+
+    def FuseSim3(self, params, kps, desc, flags, x3dc, dist, dot, level, mp_desc):
+        """Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:1612-1734) as a pure search: no
+        reprojection gate; flags bit0 = not bad and not in spAlreadyFound; x3dc from the decomposed Scw.  Returns as
+        Fuse; vpReplacePoint[i] is pKF->GetMapPoint(fuse_idx[i]) on the caller's side."""
+        return self._fuse(1, params, kps, desc, flags, x3dc, dist, dot, level, mp_desc, None)
+
     @staticmethod
     def DescriptorDistance(a, b, line_matcher_quirk=False):
         """Row-wise distances of two n x 32 descriptor tables on the GPU."""
@@ -1492,6 +1581,38 @@ def search_sim3_projection_batch(n_pairs, params, kf, kp_cap, points, pt_cap, d_
                                                     V(dist), V(dot), V(level), V(mp_desc), V(pt_n), pt_cap,
                                                     V(d_match), V(d_nmatches), V(stream or 0)),
            "plvi_search_sim3_projection_batch")
+
+
+def fuse_points_batch(n_pairs, params, kf, kp_cap, points, pt_cap, d_fuse_idx, d_fuse_dist, d_nfused, stream=None):
+    """Both ORBmatcher::Fuse overloads over device tables (plvi_fuse_points_batch).  params: FuseParams (mode set by
+    the caller); kf: the six device pointers of the keyframe side in header order (kps, desc, n, uright (0 =
+    monocular), cell_off, cell_idx); points: the seven of the point side (flags, x3dc, dist, dot, level, desc, n).
+    nfused is written by the call."""
+    V = ctypes.c_void_p
+    if len(kf) != 6 or len(points) != 7:
+        raise ValueError("kf: six device pointers, points: seven")
+    kps, desc, n, uright, cell_off, cell_idx = kf
+    flags, x3dc, dist, dot, level, mp_desc, pt_n = points
+    _check(load().plvi_fuse_points_batch(n_pairs, ctypes.byref(params), V(kps), V(desc), V(n), kp_cap,
+                                         V(uright or 0), V(cell_off), V(cell_idx), V(flags), V(x3dc), V(dist),
+                                         V(dot), V(level), V(mp_desc), V(pt_n), pt_cap, V(d_fuse_idx),
+                                         V(d_fuse_dist), V(d_nfused), V(stream or 0)),
+           "plvi_fuse_points_batch")
+
+
+def fuse_lines_batch(n_pairs, params, kf, kl_cap, lines, ml_cap, d_fuse_idx, d_fuse_dist, d_nfused, stream=None):
+    """LineMatcher::Fuse over device tables (plvi_fuse_lines_batch).  params: FuseLineParams; kf: the three device
+    pointers of the keyframe side (keylines, desc, n); lines: the eight of the MapLine side (flags, spc, epc, dist,
+    dot, level, desc, n)."""
+    V = ctypes.c_void_p
+    if len(kf) != 3 or len(lines) != 8:
+        raise ValueError("kf: three device pointers, lines: eight")
+    kl, kl_desc, kl_n = kf
+    flags, spc, epc, dist, dot, level, ml_desc, ml_n = lines
+    _check(load().plvi_fuse_lines_batch(n_pairs, ctypes.byref(params), V(kl), V(kl_desc), V(kl_n), kl_cap, V(flags),
+                                        V(spc), V(epc), V(dist), V(dot), V(level), V(ml_desc), V(ml_n), ml_cap,
+                                        V(d_fuse_idx), V(d_fuse_dist), V(d_nfused), V(stream or 0)),
+           "plvi_fuse_lines_batch")
 
 
 def line_search_init(desc1, desc2):
