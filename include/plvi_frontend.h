@@ -961,6 +961,79 @@ int plvi_fuse_lines(const plvi_fuse_line_params* p, const plvi_keyline* kl, cons
                     const uint8_t* flags, const float* spc, const float* epc, const float* dist, const double* dot,
                     const int* level, const uint8_t* ml_desc, int n_ml, int* fuse_idx, int* fuse_dist);
 
+/* ------------------------------------------ ComputeDistinctiveDescriptors
+ * MapPoint::ComputeDistinctiveDescriptors() (src/MapPoint.cc:330-404) and
+ * MapLine::ComputeDistinctiveDescriptors() (src/MapLine.cc:264-331, identical
+ * from the point where vDescriptors is filled): the refresh of a map
+ * feature's descriptor that follows every matcher call site (LocalMapping.cc
+ * :553 / :600 / :621 / :1059 / :1312 / :1416-1429 / :1454-1463, LoopClosing.cc
+ * :1389 / :1630, Tracking.cc, MapPoint::Replace / MapLine::Replace), as a
+ * pure function of the feature's observed 32-byte rows in list order:
+ *   Distances[i][j] = ORBmatcher::DescriptorDistance(row i, row j), the plain
+ *     256-bit popcount, for points AND lines: MapLine.cc:305 calls ORBmatcher's
+ *     function, not LineMatcher::DescriptorDistance with its >> 25 quirk (both
+ *     MapPoint.cc.o and MapLine.cc.o carry a relocation to ORBmatcher::
+ *     DescriptorDistance(cv::Mat const&, cv::Mat const&) inside the function
+ *     and none to LineMatcher's; tests/test_ref_objects_distinctive.py).  The
+ *     reference's float storage is exact (every value <= 256);
+ *   median(i) = element floor((N-1)/2) of row i's N distances sorted
+ *     ascending, the self-distance 0 included (`vDists[0.5*(N-1)]`);
+ *   BestIdx = the first i with the smallest median (`median < BestMedian`,
+ *     strict, from INT_MAX): the lexicographic minimum of (median, position).
+ * N = 1 and N = 2 give row 0.  The result depends on the list order only
+ * through that first-wins tie; the reference's order is the iteration order of
+ * std::map<KeyFrame*, ...>, i.e. heap-address order, so the library takes the
+ * order the caller gives.  Integers only: there is no float
+ * on this path.
+ *
+ * One implementation serves points and lines: a pool of descriptor rows plus
+ * a CSR observation list.
+ *   d_pool [pool_rows][32]: descriptor rows (e.g. K keyframe tables
+ *     [K][cap][32]: row = kf*cap + idx); byte offsets are computed in size_t.
+ *   d_obs_off [n_feat+1], d_obs_row [d_obs_off[n_feat]]: feature i lists pool
+ *     rows d_obs_row[off[i] .. off[i+1]).
+ * List length: off[i+1] - off[i], read as clamped to [0, max_obs] (the count
+ * contract of plvi_hamming_knn2_batch: entries past the clamp are never read,
+ * a decreasing offset reads as an empty list).  An entry whose row is outside
+ * [0, pool_rows) is ignored, as a grid entry outside [0, kp_n) is elsewhere --
+ * which doubles as the way to pass leftIndex / rightIndex pairs with -1 for
+ * the absent one; N is the number of entries that remain.
+ * Outputs [n_feat], always written for every feature:
+ *   best_pos    = the position of BestIdx inside the feature's list, ignored
+ *                 entries counted (the pool row is obs_row[off[i] + best_pos]);
+ *                 -1 when N == 0;
+ *   best_median = BestMedian, -1 when N == 0;
+ *   d_out_desc [n_feat][32] (may be NULL): row i = the chosen descriptor,
+ *                 written only when N > 0 (the reference leaves mDescriptor
+ *                 alone otherwise).
+ * max_obs above PLVI_DISTINCTIVE_MAX_OBS returns PLVI_E_CAPACITY and nothing
+ * is launched; no list is ever truncated below the max_obs the caller passed.
+ * (The reference's `float Distances[N][N]` on a default 8 MiB thread stack
+ * cannot exceed N ~ 1448, so no reference run has produced a longer list.)
+ * Lists of up to 64 entries share waves (one lane per entry, several features
+ * per wave when max_obs <= 32); a longer list has its rows staged in LDS once
+ * per workgroup -- 36 * max_obs (rounded up to a multiple of 4) + 16656
+ * bytes, 90 KB at the limit -- and its
+ * N*N distances spread over several workgroups, so that it does not hold up
+ * the short ones.
+ * n_feat == 0 returns 0 without a launch; negative n_feat, pool_rows or
+ * max_obs returns PLVI_E_BADARG; n_feat times the workgroups of a long list
+ * beyond 2^31 - 1 returns PLVI_E_CAPACITY.  Asynchronous on `stream`, no host
+ * read of device data, capturable in a graph like the other batch calls. */
+#define PLVI_DISTINCTIVE_MAX_OBS 2048 /* longest observation list of plvi_distinctive_descriptors[_batch] */
+
+int plvi_distinctive_descriptors_batch(int n_feat, const uint8_t* d_pool, int pool_rows, const int* d_obs_off,
+                                       const int* d_obs_row, int max_obs, int* d_best_pos, int* d_best_median,
+                                       uint8_t* d_out_desc, void* stream);
+
+/* From host memory, synchronous.  obs_off must start at >= 0 and be
+ * non-decreasing (PLVI_E_BADARG otherwise); max_obs is the longest list
+ * (PLVI_E_CAPACITY above the limit).  best_pos / best_median [n_feat];
+ * out_desc [n_feat][32] may be NULL, rows with best_pos = -1 are not written.
+ * Returns the number of features with best_pos >= 0, or an error. */
+int plvi_distinctive_descriptors(const uint8_t* pool, int pool_rows, const int* obs_off, const int* obs_row,
+                                 int n_feat, int* best_pos, int* best_median, uint8_t* out_desc);
+
 /* ORBmatcher::SearchByProjection(Frame& F, const vector<MapPoint*>&
  * vpMapPoints, th, bFarPoints, thFarPoints) (src/ORBmatcher.cc:44-145,
  * F.Nleft == -1, RadiusByViewingCos :216-222): the local-map search of

@@ -184,6 +184,7 @@ class FuseLineParams(ctypes.Structure):
 
 
 FUSE_CHUNK = 64  # PLVI_FUSE_CHUNK: candidates per workgroup of the two Fuse kernels
+DISTINCTIVE_MAX_OBS = 2048  # PLVI_DISTINCTIVE_MAX_OBS: longest observation list of distinctive_descriptors
 
 
 class LineProjParams(ctypes.Structure):
@@ -387,6 +388,8 @@ def _declare(lib):
         "plvi_fuse_points": ([V, V, V, I, V, V, V, V, V, V, V, I, V, V], I),
         "plvi_fuse_lines_batch": ([I, V, V, V, V, I, V, V, V, V, V, V, V, V, I, V, V, V, V], I),
         "plvi_fuse_lines": ([V, V, V, I, V, V, V, V, V, V, V, I, V, V], I),
+        "plvi_distinctive_descriptors_batch": ([I, V, I, V, V, I, V, V, V, V], I),
+        "plvi_distinctive_descriptors": ([V, I, V, V, I, V, V, V], I),
         "plvi_search_local_batch": ([I, V, V, V, V, I, V, V, V, V, V, V, V, V, V, I, V, V, V], I),
         "plvi_search_local": ([V, V, V, I, V, V, V, V, V, V, I, V], I),
         "plvi_search_by_projection_stereo_batch": ([I, V, V, V, V, V, I, V, V, V, V, V, V, I, V, V, V, V, V, V, V, V,
@@ -1613,6 +1616,44 @@ def fuse_lines_batch(n_pairs, params, kf, kl_cap, lines, ml_cap, d_fuse_idx, d_f
                                         V(spc), V(epc), V(dist), V(dot), V(level), V(ml_desc), V(ml_n), ml_cap,
                                         V(d_fuse_idx), V(d_fuse_dist), V(d_nfused), V(stream or 0)),
            "plvi_fuse_lines_batch")
+
+
+def distinctive_descriptors_batch(n_feat, d_pool, pool_rows, d_obs_off, d_obs_row, max_obs, d_best_pos, d_best_median,
+                                  d_out_desc=0, stream=None):
+    """MapPoint / MapLine::ComputeDistinctiveDescriptors over device tables (plvi_distinctive_descriptors_batch).
+    d_pool: pool_rows descriptor rows of 32 bytes (e.g. the keyframes' device tables back to back); d_obs_off
+    [n_feat + 1], d_obs_row: the CSR observation lists (pool rows in the caller's order; a row outside the pool is
+    ignored); max_obs: the clamp of every list length (<= DISTINCTIVE_MAX_OBS).  Outputs d_best_pos, d_best_median
+    [n_feat] (-1 / -1 where no entry remains) and d_out_desc [n_feat][32] (0 = not wanted; a row is written only
+    where best_pos >= 0).  Asynchronous on `stream`."""
+    V = ctypes.c_void_p
+    _check(load().plvi_distinctive_descriptors_batch(n_feat, V(d_pool or 0), pool_rows, V(d_obs_off), V(d_obs_row or 0),
+                                                     max_obs, V(d_best_pos), V(d_best_median), V(d_out_desc or 0),
+                                                     V(stream or 0)),
+           "plvi_distinctive_descriptors_batch")
+
+
+def distinctive_descriptors(pool, obs_off, obs_row, out_desc=None):
+    """MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:330-404) / MapLine::ComputeDistinctiveDescriptors
+    (src/MapLine.cc:264-331) from host arrays.  pool: n x 32 uint8 descriptor rows; obs_off [n_feat + 1]
+    (non-decreasing), obs_row: per feature the pool rows of its observations in the reference's list order (a row
+    outside [0, n) is ignored, e.g. -1 for an absent leftIndex / rightIndex).  Returns (count, best_pos, best_median,
+    out_desc): per feature the position inside its list of the first row with the least median distance (ignored
+    entries counted; -1 when none remains), that median, and the row itself -- rows of `out_desc` (n_feat x 32,
+    default zeros) with best_pos = -1 are left as passed in; count = features with best_pos >= 0."""
+    pool = np.ascontiguousarray(pool, np.uint8).reshape(-1, 32)
+    off = np.ascontiguousarray(obs_off, np.int32)
+    rows = np.ascontiguousarray(obs_row, np.int32)
+    n_feat = len(off) - 1
+    if n_feat < 0 or (n_feat > 0 and len(rows) < int(off[-1])):
+        raise ValueError("obs_off: n_feat + 1 offsets into obs_row")
+    out = np.zeros((max(n_feat, 0), 32), np.uint8) if out_desc is None else out_desc
+    if out.dtype != np.uint8 or out.shape != (n_feat, 32) or not out.flags.c_contiguous:
+        raise ValueError("out_desc: a C-contiguous n_feat x 32 uint8 array")
+    bp, bm = np.full(max(n_feat, 1), -7, np.int32), np.full(max(n_feat, 1), -7, np.int32)
+    n = _check(load().plvi_distinctive_descriptors(_ptr(pool), len(pool), _ptr(off), _ptr(rows), n_feat, _ptr(bp),
+                                                   _ptr(bm), _ptr(out)), "plvi_distinctive_descriptors")
+    return n, bp[:n_feat], bm[:n_feat], out
 
 
 def line_search_init(desc1, desc2):
