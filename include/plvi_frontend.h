@@ -1034,6 +1034,174 @@ int plvi_distinctive_descriptors_batch(int n_feat, const uint8_t* d_pool, int po
 int plvi_distinctive_descriptors(const uint8_t* pool, int pool_rows, const int* obs_off, const int* obs_row,
                                  int n_feat, int* best_pos, int* best_median, uint8_t* out_desc);
 
+/* -------------------------------------------------------- KeyFrameDatabase
+ * ORB_SLAM3::KeyFrameDatabase (src/KeyFrameDatabase.cc): add (:46-52), erase
+ * (:54-73), clear (:75-79), clearMap (:81-105) and the two detectors the
+ * reference calls, DetectRelocalizationCandidates (:790-902; Tracking.cc:5752)
+ * and DetectNBestCandidates (:619-787; LoopClosing.cc:660 with 3 candidates).
+ * DetectLoopCandidates, DetectCandidates and DetectBestCandidates have no
+ * caller in the reference and are not provided.
+ *
+ * A keyframe lives in a caller-chosen slot in [0, slot_cap); slot numbers are
+ * what every table and output below speaks (INTEGRATION.md maps them to
+ * KeyFrame*).  Per slot the handle keeps, on the device: the BowVector
+ * forward (words ascending as unsigned, values as double, word_cap entries),
+ * a map id, a monotone add-sequence number, and two floats that stand for the
+ * members KeyFrame::mPlaceRecognitionScore and KeyFrame::mRelocScore, which
+ * persist from one query to the next.  There is no inverted file: the order
+ * of the reference's lKFsSharingWords (semantics 3) follows from the forward
+ * tables.
+ *
+ * Limits.  word_cap and q_cap <= PLVI_KFDB_MAX_WORDS: a query's words and
+ * values are staged in LDS, 12 bytes a word (96 KB of a CU's 160 KB at the
+ * limit); the reference's largest BowVector has 5 * nFeatures entries (the
+ * initial keyframes' extractor, Tracking.cc:921).  slot_cap <= 2^24.  Both
+ * return PLVI_E_CAPACITY beyond.  The handle's device memory is 12 * slot_cap
+ * * word_cap bytes plus 28 * slot_cap per query of the largest batch seen.
+ *
+ * scoring is the vocabulary's DBoW2::ScoringType (info[2] of plvi_vocab_info):
+ * only L1_NORM = 0 is supported, any other value returns PLVI_E_BADARG.
+ * n_words is the vocabulary's word count; a word id at or above it sets bit 1
+ * of the handle's error word (the reference would index mvInvertedFile out of
+ * range).
+ *
+ * Calls on one handle must be ordered by the caller: issue them on one stream,
+ * or order the streams with events.  The occupancy test of add is made on the
+ * host at call time, in call order. */
+#define PLVI_KFDB_MAX_WORDS 8192 /* longest BowVector of a slot or a query: 12 bytes of LDS per query word */
+#define PLVI_KFDB_NEIGHBOURS 10  /* row length of d_covis: GetBestCovisibilityKeyFrames(10) */
+typedef struct plvi_kf_database plvi_kf_database;
+
+int plvi_kfdb_create(int n_words, int slot_cap, int word_cap, int scoring, int device, plvi_kf_database** out);
+int plvi_kfdb_destroy(plvi_kf_database* h);
+
+/* add (:46-52) of n keyframes straight from the [frame][cap] tables that
+ * plvi_vocab_transform_batch writes.  entries (host) [n][3] = frame row,
+ * slot, map id.  d_bow_n follows the count contract (plvi_hamming_knn2_batch)
+ * with the addition of plvi_vocab_transform_batch: a count above word_cap is
+ * clamped to it and sets bit 0 of the handle's error word (plvi_kfdb_errors).
+ * A slot outside [0, slot_cap), a negative row, a slot that is occupied or
+ * named twice returns PLVI_E_BADARG and nothing is added.  add zeroes both
+ * score members of the slot.  For mPlaceRecognitionScore that is the
+ * reference's own value (the KeyFrame constructors, KeyFrame.cc:37 / :55); it
+ * never initialises mRelocScore, so a read before the first score (semantics
+ * 4) is undefined there, and the handle models one outcome, 0, as emulate_tail
+ * does for the vocabulary loader.  A keyframe with an empty BowVector occupies its slot
+ * and shares a word with nothing.  After 2^32 - 1 adds since create or the last
+ * clear the call returns PLVI_E_OVERFLOW.  Asynchronous on `stream`; the
+ * entries are read before the call returns. */
+int plvi_kfdb_add_batch(plvi_kf_database* h, int n, const int* entries, const unsigned* d_bow_word,
+                        const double* d_bow_value, const int* d_bow_n, int cap, void* stream);
+
+/* One keyframe from host memory, synchronous.  n above word_cap adds the first
+ * word_cap words and returns PLVI_E_OVERFLOW. */
+int plvi_kfdb_add(plvi_kf_database* h, int slot, int map_id, const unsigned* word, const double* value, int n);
+
+/* erase (:54-73) of n slots (host array); an empty slot is left alone, as the
+ * reference's erase of a keyframe that is in no list; a slot outside
+ * [0, slot_cap) returns PLVI_E_BADARG.  A later add to the slot gets a later
+ * sequence number.  clear_map (:81-105) erases every slot of one map id, clear
+ * (:75-79) all of them.  Asynchronous on `stream`. */
+int plvi_kfdb_erase(plvi_kf_database* h, int n, const int* slots, void* stream);
+int plvi_kfdb_clear_map(plvi_kf_database* h, int map_id, void* stream);
+int plvi_kfdb_clear(plvi_kf_database* h, void* stream);
+
+/* Waits for `stream`, reads and clears the handle's error word into *flags
+ * (may be NULL; bit 0 = a count above word_cap, bit 1 = a word id >= n_words)
+ * and returns PLVI_E_OVERFLOW if it was not zero. */
+int plvi_kfdb_errors(plvi_kf_database* h, int* flags, void* stream);
+
+/* n_queries queries against the handle.  mode 0 =
+ * DetectRelocalizationCandidates(F, pMap), mode 1 = DetectNBestCandidates(pKF,
+ * vpLoopCand, vpMergeCand, n_best).
+ * Inputs (device):
+ *   d_q_word / d_q_value [q][q_cap], d_q_n [q]: the queries' BowVectors in the
+ *     layout of plvi_vocab_transform_batch, counts under the count contract;
+ *     words strictly ascending (a std::map's order);
+ *   d_q_map [q]: F's / pKF's map id;
+ *   d_conn_off [q+1], d_conn_slot (mode 1; both NULL = none): per query the
+ *     slots of pKF->GetConnectedKeyFrames(); slots outside [0, slot_cap) are
+ *     ignored.  Unused in mode 0;
+ *   d_covis [slot_cap][PLVI_KFDB_NEIGHBOURS] (NULL = no keyframe has
+ *     neighbours): row s = the slots of GetBestCovisibilityKeyFrames(10) of
+ *     the keyframe in slot s, in that order; a negative entry ends the row;
+ *     an entry naming an empty slot, or one outside [0, slot_cap), is skipped;
+ *   d_map_bad [n_maps] (NULL = none): Map::IsBad() by map id; an id outside
+ *     [0, n_maps) is not bad.
+ * Stage outputs (device, each may be NULL):
+ *   d_words [q][slot_cap]: the final mnRelocWords / mnPlaceRecognitionWords of
+ *     the keyframes in lKFsSharingWords, -1 for every other slot;
+ *   d_score [q][slot_cap] double: what mpVoc->score returned, before the float
+ *     store, for the scored keyframes; other cells are not written;
+ *   d_order [q][slot_cap], d_norder [q]: the slots in lKFsSharingWords order
+ *     and their number; cells past the number are not written.
+ * Final outputs (device):
+ *   mode 0: d_cand [q][cand_cap], d_ncand [q]: vpRelocCandidates.  The full
+ *     count is always written; rows at or past cand_cap are not;
+ *   mode 1: d_loop / d_merge [q][n_best], d_nloop / d_nmerge [q].
+ * Semantics:
+ *   1. Sharing list (:631-660 / :798-813).  A keyframe sharing at least one
+ *      word with the query enters lKFsSharingWords; in mode 1 the connected
+ *      keyframes never enter it and never receive the query's stamp (:645).
+ *      words = |common words|; minCommonWords = (int)(maxCommonWords * 0.8f)
+ *      (:673 / :826), and only words > minCommonWords is scored (:684 / :837).
+ *   2. Score (ScoringObject.cpp:23-68).  score += (fabs(vi - wi) - fabs(vi)) -
+ *      fabs(wi) over the common words in ascending word id, in double, vi the
+ *      query's value; then -score * 0.5 (the object negates and multiplies:
+ *      tests/test_ref_objects_kfdb.py); then the float store into the score
+ *      member (:688 / :841).  The sum is taken strictly in that order.
+ *   3. Encounter order.  The reference walks the query's words ascending and
+ *      each word's std::list in insertion order, and a keyframe enters the list
+ *      at its first hit: lKFsSharingWords is ordered by (smallest word id shared
+ *      with the query, add sequence).  Mode 0's output order and every tie
+ *      below depend on it.
+ *   4. Accumulation (:700-725 / :853-878).  Per scored keyframe in list order:
+ *      accScore starts as its own float score; its neighbours are walked in
+ *      table order, those without this query's stamp (sharing no word,
+ *      connected in mode 1, or an empty slot) are skipped; accScore += the
+ *      neighbour's score MEMBER, and pBestKF moves on a strict >.  A neighbour
+ *      that shares a word but failed the threshold contributes its stale
+ *      member: the value of the latest earlier query of the same mode that
+ *      scored it, or 0 after add.
+ *   5. Mode 0 selection (:880-899).  bestAccScore starts at 0 and moves on >;
+ *      entries with accScore > 0.75f * bestAccScore are kept, those whose
+ *      pBestKF is of another map than the query's dropped, then de-duplicated
+ *      by pBestKF; output in list order, unsorted.
+ *   6. Mode 1 selection (:729-759).  std::list::sort(compFirst) is a stable
+ *      descending sort by accScore (ties keep list order); the sorted list is
+ *      walked while either output has room: same map and room in loop -> loop;
+ *      else another map, room in merge and a map that is not bad -> merge;
+ *      every visited pBestKF is marked as added.  The caller must erase a
+ *      keyframe before it goes bad, as KeyFrame::SetBadFlag does: the
+ *      reference's `continue` without an increment (:742-743) would spin on
+ *      a bad one, and the handle has no such flag.
+ *   7. Batch = sequential.  The queries of one call behave as n_queries single
+ *      calls in index order, the stale members of 4 included; after the call
+ *      the members hold the last write.  Each query is a fresh stamp: the
+ *      reference's stamp 0 (a frame or keyframe id 0 equals the initial
+ *      mnRelocQuery / mnPlaceRecognitionQuery) and a repeated query id are
+ *      outside the model.
+ * q_cap above PLVI_KFDB_MAX_WORDS, n_queries above 65535 or n_queries *
+ * slot_cap above 2^31 - 1 returns PLVI_E_CAPACITY; n_best <= 65535.
+ * n_queries == 0 returns 0 without a launch.  A batch larger than any before
+ * grows the handle's scratch (an allocation); otherwise the call is
+ * asynchronous on `stream` with no host read of device data. */
+int plvi_kfdb_query_batch(plvi_kf_database* h, int n_queries, const unsigned* d_q_word, const double* d_q_value,
+                          const int* d_q_n, int q_cap, const int* d_q_map, int mode, int n_best,
+                          const int* d_conn_off, const int* d_conn_slot, const int* d_covis, const uint8_t* d_map_bad,
+                          int n_maps, int* d_words, double* d_score, int* d_order, int* d_norder, int* d_cand,
+                          int cand_cap, int* d_ncand, int* d_loop, int* d_nloop, int* d_merge, int* d_nmerge,
+                          void* stream);
+
+/* One query from host memory, synchronous.  conn [n_conn], covis
+ * [slot_cap][PLVI_KFDB_NEIGHBOURS] (may be NULL), map_bad [n_maps] (may be
+ * NULL).  Mode 0: cand [cand_cap] receives at most cand_cap candidates and the
+ * full count is returned.  Mode 1: loop / merge [n_best] and *n_loop /
+ * *n_merge; returns their sum.  Negative = error. */
+int plvi_kfdb_query(plvi_kf_database* h, const unsigned* q_word, const double* q_value, int q_n, int q_map, int mode,
+                    int n_best, const int* conn, int n_conn, const int* covis, const uint8_t* map_bad, int n_maps,
+                    int* cand, int cand_cap, int* loop, int* n_loop, int* merge, int* n_merge);
+
 /* ORBmatcher::SearchByProjection(Frame& F, const vector<MapPoint*>&
  * vpMapPoints, th, bFarPoints, thFarPoints) (src/ORBmatcher.cc:44-145,
  * F.Nleft == -1, RadiusByViewingCos :216-222): the local-map search of

@@ -10,6 +10,8 @@ Class and method names follow the reference interfaces they replace:
   hamming_knn2  -> cv::BFMatcher(NORM_HAMMING).knnMatch(k=2) (LineMatcher.cpp:47-48)
   ORBVocabulary -> DBoW2::TemplatedVocabulary<FORB> (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h):
                    loadFromTextFile, transform(features, BowVector&, FeatureVector&, levelsup)
+  KeyFrameDatabase -> ORB_SLAM3::KeyFrameDatabase (include/KeyFrameDatabase.h): add, erase, clearMap, clear,
+                   DetectRelocalizationCandidates, DetectNBestCandidates
 
 There is no CPU fallback: if the HIP library is missing or no GPU is
 visible, construction raises.  PyTorch is only used by bench.py for device
@@ -185,6 +187,8 @@ class FuseLineParams(ctypes.Structure):
 
 FUSE_CHUNK = 64  # PLVI_FUSE_CHUNK: candidates per workgroup of the two Fuse kernels
 DISTINCTIVE_MAX_OBS = 2048  # PLVI_DISTINCTIVE_MAX_OBS: longest observation list of distinctive_descriptors
+KFDB_MAX_WORDS = 8192       # PLVI_KFDB_MAX_WORDS: longest BowVector of a KeyFrameDatabase slot or query
+KFDB_NEIGHBOURS = 10        # PLVI_KFDB_NEIGHBOURS: row length of the covisibility table
 
 
 class LineProjParams(ctypes.Structure):
@@ -390,6 +394,16 @@ def _declare(lib):
         "plvi_fuse_lines": ([V, V, V, I, V, V, V, V, V, V, V, I, V, V], I),
         "plvi_distinctive_descriptors_batch": ([I, V, I, V, V, I, V, V, V, V], I),
         "plvi_distinctive_descriptors": ([V, I, V, V, I, V, V, V], I),
+        "plvi_kfdb_create": ([I, I, I, I, I, c_void_pp], I),
+        "plvi_kfdb_destroy": ([V], I),
+        "plvi_kfdb_add_batch": ([V, I, V, V, V, V, I, V], I),
+        "plvi_kfdb_add": ([V, I, I, V, V, I], I),
+        "plvi_kfdb_erase": ([V, I, V, V], I),
+        "plvi_kfdb_clear_map": ([V, I, V], I),
+        "plvi_kfdb_clear": ([V, V], I),
+        "plvi_kfdb_errors": ([V, P, V], I),
+        "plvi_kfdb_query_batch": ([V, I, V, V, V, I, V, I, I, V, V, V, V, I, V, V, V, V, V, I, V, V, V, V, V, V], I),
+        "plvi_kfdb_query": ([V, V, V, I, I, I, I, V, I, V, V, I, V, I, V, P, V, P], I),
         "plvi_search_local_batch": ([I, V, V, V, V, I, V, V, V, V, V, V, V, V, V, I, V, V, V], I),
         "plvi_search_local": ([V, V, V, I, V, V, V, V, V, V, I, V], I),
         "plvi_search_by_projection_stereo_batch": ([I, V, V, V, V, V, I, V, V, V, V, V, V, I, V, V, V, V, V, V, V, V,
@@ -1461,6 +1475,183 @@ class ORBVocabulary:
         _check(self._lib.plvi_vocab_transform_features(self._h, _ptr(d), n, levelsup, _ptr(w), _ptr(ni)),
                "plvi_vocab_transform_features")
         return w[:n], ni[:n]
+
+
+def _bow_arrays(bow):
+    """A BowVector as (ascending uint32 words, float64 values): a {word: value} dict or a (words, values) pair."""
+    if isinstance(bow, dict):
+        ws = sorted(bow)
+        return np.array(ws, np.uint32), np.array([bow[w] for w in ws], np.float64)
+    w, v = bow
+    return np.ascontiguousarray(w, np.uint32), np.ascontiguousarray(v, np.float64)
+
+
+def pack_bow(bows, cap=None):
+    """BowVectors -> the [frame][cap] tables of plvi_vocab_transform_batch: (word, value, n)."""
+    arrs = [_bow_arrays(b) for b in bows]
+    cap = max([len(w) for w, _ in arrs] + [1]) if cap is None else cap
+    word, value = np.zeros((len(arrs), cap), np.uint32), np.zeros((len(arrs), cap), np.float64)
+    n = np.zeros(max(len(arrs), 1), np.int32)
+    for i, (w, v) in enumerate(arrs):
+        word[i, :len(w)], value[i, :len(w)], n[i] = w, v, len(w)
+    return word, value, n
+
+
+def kfdb_add_batch(db, entries, d_bow_word, d_bow_value, d_bow_n, cap, stream=None):
+    """KeyFrameDatabase::add of device BowVector tables (plvi_kfdb_add_batch).  entries: host n x 3 ints
+    (frame row, slot, map id).  Asynchronous on `stream`."""
+    V = ctypes.c_void_p
+    e = np.ascontiguousarray(entries, np.int32).reshape(-1, 3)
+    _check(load().plvi_kfdb_add_batch(db._h, len(e), _ptr(e), V(d_bow_word or 0), V(d_bow_value or 0), V(d_bow_n), cap,
+                                      V(stream or 0)), "plvi_kfdb_add_batch")
+
+
+def kfdb_query_batch(db, n_queries, d_q_word, d_q_value, d_q_n, q_cap, d_q_map, mode, n_best=3, d_conn_off=0,
+                     d_conn_slot=0, d_covis=0, d_map_bad=0, n_maps=0, d_words=0, d_score=0, d_order=0, d_norder=0,
+                     d_cand=0, cand_cap=0, d_ncand=0, d_loop=0, d_nloop=0, d_merge=0, d_nmerge=0, stream=None):
+    """DetectRelocalizationCandidates (mode 0) / DetectNBestCandidates (mode 1) of n_queries device BowVectors
+    (plvi_kfdb_query_batch; every pointer is a device address, 0 = NULL).  Asynchronous on `stream`."""
+    V = ctypes.c_void_p
+    _check(load().plvi_kfdb_query_batch(db._h, n_queries, V(d_q_word or 0), V(d_q_value or 0), V(d_q_n), q_cap,
+                                        V(d_q_map), mode, n_best, V(d_conn_off or 0), V(d_conn_slot or 0),
+                                        V(d_covis or 0), V(d_map_bad or 0), n_maps, V(d_words or 0), V(d_score or 0),
+                                        V(d_order or 0), V(d_norder or 0), V(d_cand or 0), cand_cap, V(d_ncand or 0),
+                                        V(d_loop or 0), V(d_nloop or 0), V(d_merge or 0), V(d_nmerge or 0),
+                                        V(stream or 0)), "plvi_kfdb_query_batch")
+
+
+class KeyFrameDatabase:
+    """ORB_SLAM3::KeyFrameDatabase (src/KeyFrameDatabase.cc) on the GPU: keyframes live in caller-chosen slots
+    [0, slot_cap) and every method speaks slot numbers.  ``voc`` is an ORBVocabulary (its word count and scoring
+    type are taken; only L1_NORM is supported) or a word count.  BowVectors are {word: value} dicts or
+    (words, values) pairs."""
+
+    def __init__(self, voc, slot_cap, word_cap, scoring=0, device=0):
+        self._lib = load()
+        n_words = voc.n_words if hasattr(voc, "n_words") else int(voc)
+        scoring = voc.scoring if hasattr(voc, "scoring") else scoring
+        h = ctypes.c_void_p()
+        _check(self._lib.plvi_kfdb_create(n_words, slot_cap, word_cap, scoring, device, ctypes.byref(h)),
+               "plvi_kfdb_create")
+        self._h, self.n_words, self.slot_cap, self.word_cap = h, n_words, slot_cap, word_cap
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.plvi_kfdb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, slot, bow, map_id=0):
+        w, v = _bow_arrays(bow)
+        _check(self._lib.plvi_kfdb_add(self._h, slot, map_id, _ptr(w), _ptr(v), len(w)), "plvi_kfdb_add")
+
+    def add_many(self, slots, bows, map_ids):
+        """add of several keyframes in the given order through plvi_kfdb_add_batch."""
+        word, value, n = pack_bow(bows)
+        bufs = [DeviceBuffer(a.nbytes) for a in (word, value, n)]
+        for b, a in zip(bufs, (word, value, n)):
+            b.upload(a)
+        entries = np.stack([np.arange(len(slots)), np.asarray(slots), np.asarray(map_ids)], axis=1)
+        kfdb_add_batch(self, entries, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, word.shape[1])
+        return self.errors()
+
+    def erase(self, slots, stream=None):
+        s = np.atleast_1d(np.asarray(slots, np.int32))
+        _check(self._lib.plvi_kfdb_erase(self._h, len(s), _ptr(s), ctypes.c_void_p(stream or 0)), "plvi_kfdb_erase")
+
+    def clearMap(self, map_id, stream=None):
+        _check(self._lib.plvi_kfdb_clear_map(self._h, map_id, ctypes.c_void_p(stream or 0)), "plvi_kfdb_clear_map")
+
+    def clear(self, stream=None):
+        _check(self._lib.plvi_kfdb_clear(self._h, ctypes.c_void_p(stream or 0)), "plvi_kfdb_clear")
+
+    def errors(self, stream=None):
+        """Read and clear the error word (bit 0: a count above word_cap, bit 1: a word id >= n_words)."""
+        f = ctypes.c_int()
+        self._lib.plvi_kfdb_errors(self._h, ctypes.byref(f), ctypes.c_void_p(stream or 0))
+        return f.value
+
+    def _covis(self, covis):
+        if covis is None:
+            return None
+        c = np.ascontiguousarray(covis, np.int32)
+        if c.shape != (self.slot_cap, KFDB_NEIGHBOURS):
+            raise ValueError("covis: slot_cap x 10 slots, -1 ends a row")
+        return c
+
+    def DetectRelocalizationCandidates(self, bow, map_id, covis=None, cand_cap=None):
+        """vpRelocCandidates as slots, in the reference's order (KeyFrameDatabase.cc:790-902)."""
+        w, v = _bow_arrays(bow)
+        c = self._covis(covis)
+        cap = self.slot_cap if cand_cap is None else cand_cap
+        cand = np.full(max(cap, 1), -1, np.int32)
+        n = _check(self._lib.plvi_kfdb_query(self._h, _ptr(w), _ptr(v), len(w), map_id, 0, 0, None, 0,
+                                             None if c is None else _ptr(c), None, 0, _ptr(cand), cap, None, None,
+                                             None, None), "plvi_kfdb_query")
+        return [int(x) for x in cand[:min(n, cap)]]
+
+    def DetectNBestCandidates(self, bow, map_id, connected=(), n_best=3, covis=None, map_bad=None):
+        """(vpLoopCand, vpMergeCand) as slots (KeyFrameDatabase.cc:619-787)."""
+        w, v = _bow_arrays(bow)
+        c = self._covis(covis)
+        conn = np.ascontiguousarray(sorted(connected), np.int32)
+        bad = None if map_bad is None else np.ascontiguousarray(map_bad, np.uint8)
+        loop, merge = np.full(max(n_best, 1), -1, np.int32), np.full(max(n_best, 1), -1, np.int32)
+        nl, nm = ctypes.c_int(), ctypes.c_int()
+        _check(self._lib.plvi_kfdb_query(self._h, _ptr(w), _ptr(v), len(w), map_id, 1, n_best,
+                                         _ptr(conn) if len(conn) else None, len(conn),
+                                         None if c is None else _ptr(c), None if bad is None else _ptr(bad),
+                                         0 if bad is None else len(bad), None, 0, _ptr(loop), ctypes.byref(nl),
+                                         _ptr(merge), ctypes.byref(nm)), "plvi_kfdb_query")
+        return [int(x) for x in loop[:nl.value]], [int(x) for x in merge[:nm.value]]
+
+    def query_arrays(self, bows, map_ids, mode, n_best=3, connected=None, covis=None, map_bad=None, cand_cap=None,
+                     q_cap=None, counts=None, fill=-7):
+        """One plvi_kfdb_query_batch call from host data with every stage output downloaded: a dict of words, score,
+        order, norder and cand / ncand (mode 0) or loop / nloop / merge / nmerge (mode 1).  Outputs are pre-filled
+        with `fill` (score with NaN) so that unwritten cells show.  `counts` overrides the per-query counts (to
+        pass values outside [0, q_cap])."""
+        nq, S = len(bows), self.slot_cap
+        word, value, n = pack_bow(bows, q_cap)
+        if counts is not None:
+            n = np.ascontiguousarray(counts, np.int32)
+        c = self._covis(covis)
+        conn = [sorted(x) for x in connected] if connected is not None else None
+        ins = {"word": word, "value": value, "n": n, "map": np.ascontiguousarray(map_ids, np.int32)}
+        if conn is not None:
+            off = np.zeros(nq + 1, np.int32)
+            off[1:] = np.cumsum([len(x) for x in conn])
+            ins["coff"], ins["cslot"] = off, np.array([s for x in conn for s in x] + [0], np.int32)
+        if c is not None:
+            ins["covis"] = c
+        if map_bad is not None:
+            ins["bad"] = np.ascontiguousarray(map_bad, np.uint8)
+        cap = S if cand_cap is None else cand_cap
+        outs = {"words": np.full((nq, S), fill, np.int32), "score": np.full((nq, S), np.nan, np.float64),
+                "order": np.full((nq, S), fill, np.int32), "norder": np.full(nq, fill, np.int32)}
+        if mode == 0:
+            outs.update(cand=np.full((nq, max(cap, 1)), fill, np.int32), ncand=np.full(nq, fill, np.int32))
+        else:
+            outs.update(loop=np.full((nq, max(n_best, 1)), fill, np.int32), nloop=np.full(nq, fill, np.int32),
+                        merge=np.full((nq, max(n_best, 1)), fill, np.int32), nmerge=np.full(nq, fill, np.int32))
+        d = {}
+        for k, a in list(ins.items()) + list(outs.items()):
+            d[k] = DeviceBuffer(a.nbytes)
+            d[k].upload(a)
+        g = lambda k: d[k].ptr if k in d else 0  # noqa: E731
+        kfdb_query_batch(self, nq, g("word"), g("value"), g("n"), word.shape[1], g("map"), mode, n_best, g("coff"),
+                         g("cslot"), g("covis"), g("bad"), len(ins["bad"]) if "bad" in ins else 0, g("words"),
+                         g("score"), g("order"), g("norder"), g("cand"), cap, g("ncand"), g("loop"), g("nloop"),
+                         g("merge"), g("nmerge"))
+        _check(self._lib.plvi_device_synchronize(), "plvi_device_synchronize")
+        for k, a in outs.items():
+            d[k].download(a)
+        return outs
 
 
 def assign_grid_batch(d_kps, d_count, cap, n_frames, grid, d_cell_off, d_cell_idx, stream=None):
