@@ -7,17 +7,22 @@
 //   distance  : ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:2350-2366)
 //               = popcount of the 256-bit XOR.
 //
-// Kernel: one thread per query row, 256 queries per workgroup; train rows
-// are staged through LDS in 256-row chunks and read as wave-uniform
-// broadcasts.  VALU-bound: 8 x (v_xor + v_bcnt) per descriptor pair.
+// Kernels: hamming_knn2_mfma_kernel takes the distances from int8 matrix-core
+// tiles (below; train capacities up to 65535).  hamming_knn2_kernel, for
+// larger capacities and PLVI_MATCH_MFMA=0: one thread per query row, 256
+// queries per workgroup; train rows are staged through LDS in 256-row chunks
+// and read as wave-uniform broadcasts.  VALU-bound: 8 x (v_xor + v_bcnt) per
+// descriptor pair.
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <algorithm>
 #include <vector>
 
+#include "match_tile.h"
 #include "plvi_common.h"
 
 namespace plvi {
@@ -103,12 +108,220 @@ __global__ __launch_bounds__(256) void line_match_finish_kernel(const int* __res
     if (threadIdx.x == 0) nmatch[p] = s_cnt;
 }
 
+// ---------------------------------------------------------------------------
+// kNN-2 from matrix-core distance tiles (arithmetic: match_tile.h).
+//
+// v_mfma_i32_16x16x64_i8 with the trains as tile rows (A) and the queries as
+// tile columns (B): lane l = (c = l & 15, g = l >> 4) supplies bytes
+// [8g, 8g + 8) of train row r = c of the tile and of query column c, and gets
+// the accumulators of trains 4g .. 4g + 3 against query c.  A wave keeps
+// kTileQ query tiles (64 queries) expanded in registers for the whole train
+// sweep; a train tile is read from LDS as one 8-byte piece per lane and
+// expanded once for the kTileQ tiles.  Each lane carries the two smallest
+// keys of its query over the train rows of its lane group; the four groups
+// merge once at the end, after which lane l holds the result of query l of
+// the wave's 64.
+typedef int v4i __attribute__((ext_vector_type(4)));
+constexpr int kTileQ = 4;                   // query tiles per wave
+constexpr int kLdsPieces = kKnnChunk * 4;   // 8-byte pieces of a staged train chunk
+
+// Train rows [base, base + kKnnChunk) of a pair's table into LDS as
+// [tile][g][r] pieces, so a tile is 512 contiguous bytes in lane order; rows
+// at or past nT are not loaded (zeros).
+__device__ __forceinline__ void stage_train_chunk(uint2* lds, const uint4* tp, int base, int nT) {
+    for (int i = threadIdx.x; i < kKnnChunk * 2; i += 256) {
+        const int row = i >> 1, h = i & 1;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (base + row < nT) v = tp[(size_t)base * 2 + i];
+        uint2* d = lds + (row >> 4) * 64 + h * 32 + (row & 15);
+        d[0] = make_uint2(v.x, v.y);
+        d[16] = make_uint2(v.z, v.w);
+    }
+}
+
+template <bool kMask>
+__device__ __forceinline__ void knn2_tile(const v4i (&qa)[kTileQ][4], uint2 w, int j0, int nT, int (&b0)[kTileQ],
+                                          int (&b1)[kTileQ]) {
+    uint32_t e[16];
+    expand_train_word(w.x, e);
+    expand_train_word(w.y, e + 8);
+    v4i a[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) a[m] = v4i{(int)e[4 * m], (int)e[4 * m + 1], (int)e[4 * m + 2], (int)e[4 * m + 3]};
+#pragma unroll
+    for (int qt = 0; qt < kTileQ; ++qt) {
+        v4i acc = {0, 0, 0, 0};
+#pragma unroll
+        for (int m = 0; m < 4; ++m) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[m], qa[qt][m], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            int k = make_key(acc[r], j0 + r);
+            if (kMask) k = j0 + r < nT ? k : kKeySentinel;
+            top2_update(b0[qt], b1[qt], k);
+        }
+    }
+}
+
+// One sweep of a workgroup (4 waves, 256 queries from q0) over a pair's train
+// table.  Block-uniform control flow (it synchronises); on return lane l of a
+// wave holds the two keys and popc of query q0 + 64 * wave + l (unspecified
+// for a query at or past nQ).
+__device__ __forceinline__ void knn2_sweep(const uint8_t* __restrict__ qtab, int nQ, int q0,
+                                           const uint8_t* __restrict__ ttab, int nT, uint2* lds, int& k0, int& k1,
+                                           int& popq) {
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    const int qw = q0 + (threadIdx.x >> 6) * 64;
+    const bool waveActive = qw < nQ;
+    v4i qa[kTileQ][4];
+    int b0[kTileQ], b1[kTileQ], pq[kTileQ];
+#pragma unroll
+    for (int qt = 0; qt < kTileQ; ++qt) {
+        const int qi = qw + qt * 16 + c;
+        uint2 w = make_uint2(0, 0);
+        if (qi < nQ) w = *reinterpret_cast<const uint2*>(qtab + (size_t)qi * 32 + 8 * g);
+        uint32_t e[16];
+        expand_query_word(w.x, e);
+        expand_query_word(w.y, e + 8);
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+            qa[qt][m] = v4i{(int)e[4 * m], (int)e[4 * m + 1], (int)e[4 * m + 2], (int)e[4 * m + 3]};
+        pq[qt] = popc32(w.x) + popc32(w.y);
+        b0[qt] = b1[qt] = kKeySentinel;
+    }
+    const uint4* tp = reinterpret_cast<const uint4*>(ttab);
+    for (int base = 0; base < nT; base += kKnnChunk) {
+        __syncthreads();
+        stage_train_chunk(lds, tp, base, nT);
+        __syncthreads();
+        if (!waveActive) continue;
+        const int n = min(kKnnChunk, nT - base);
+        const int full = n >> 4;
+        for (int tl = 0; tl < full; ++tl)
+            knn2_tile<false>(qa, lds[tl * 64 + lane], base + tl * 16 + 4 * g, nT, b0, b1);
+        if (n & 15) knn2_tile<true>(qa, lds[full * 64 + lane], base + full * 16 + 4 * g, nT, b0, b1);
+    }
+    // the four lane groups of a query merge; then lane (c, g) takes tile g
+    k0 = k1 = kKeySentinel;
+    popq = 0;
+#pragma unroll
+    for (int qt = 0; qt < kTileQ; ++qt) {
+#pragma unroll
+        for (int x = 16; x <= 32; x <<= 1) {
+            const int p0 = __shfl_xor(b0[qt], x), p1 = __shfl_xor(b1[qt], x);
+            top2_merge(b0[qt], b1[qt], p0, p1);
+            pq[qt] += __shfl_xor(pq[qt], x);
+        }
+        if (qt == g) {
+            k0 = b0[qt];
+            k1 = b1[qt];
+            popq = pq[qt];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void hamming_knn2_mfma_kernel(const uint8_t* __restrict__ q,
+                                                                const int* __restrict__ nq, int nq_cap,
+                                                                const uint8_t* __restrict__ t,
+                                                                const int* __restrict__ nt, int nt_cap,
+                                                                int* __restrict__ idx0, int* __restrict__ d0o,
+                                                                int* __restrict__ idx1, int* __restrict__ d1o) {
+    __shared__ uint2 lds[kLdsPieces];
+    const int pair = blockIdx.y;
+    const int nQ = min(nq[pair], nq_cap), nT = min(nt[pair], nt_cap);
+    const int q0 = blockIdx.x * kKnnQ;
+    if (q0 >= nQ) return;
+    int k0, k1, popq;
+    knn2_sweep(q + (size_t)pair * nq_cap * 32, nQ, q0, t + (size_t)pair * nt_cap * 32, nT, lds, k0, k1, popq);
+    const int qi = q0 + threadIdx.x;
+    if (qi < nQ) {
+        const size_t o = (size_t)pair * nq_cap + qi;
+        int j0, j1, e0, e1;
+        decode_key(k0, popq, j0, e0);
+        decode_key(k1, popq, j1, e1);
+        idx0[o] = j0; d0o[o] = e0; idx1[o] = j1; d1o[o] = e1;
+    }
+}
+
+// LineMatcher::match of one pair per workgroup: both directions' kNN-2 by the
+// sweep above (desc1 as queries, then desc2 as queries), each followed by its
+// ratio test into LDS, then the mutual check and the count.
+// Dynamic LDS: the train chunk, then cap1 + cap2 ints.
+__global__ __launch_bounds__(256, 2) void line_match_fused_kernel(const uint8_t* __restrict__ desc1,
+                                                               const int* __restrict__ n1, int cap1,
+                                                               const uint8_t* __restrict__ desc2,
+                                                               const int* __restrict__ n2, int cap2, float nnr,
+                                                               int* __restrict__ m12, int* __restrict__ nmatch) {
+    extern __shared__ uint2 lm_lds[];
+    __shared__ int s_cnt;
+    int* fwd = reinterpret_cast<int*>(lm_lds + kLdsPieces);  // desc1 row -> accepted desc2 row or -1
+    int* back = fwd + cap1;                                  // desc2 row -> accepted desc1 row or -1
+    const int p = blockIdx.x;
+    const int a = min(n1[p], cap1), b = min(n2[p], cap2);
+    const uint8_t* t1 = desc1 + (size_t)p * cap1 * 32;
+    const uint8_t* t2 = desc2 + (size_t)p * cap2 * 32;
+    if (threadIdx.x == 0) s_cnt = 0;
+    const bool both = a >= 2 && b >= 2;  // fewer rows on either side: no ratio test passes, no mutual match
+    if (both) {
+        for (int q0 = 0; q0 < a; q0 += kKnnQ) {
+            int k0, k1, popq;
+            knn2_sweep(t1, a, q0, t2, b, lm_lds, k0, k1, popq);
+            const int qi = q0 + threadIdx.x;
+            if (qi < a) {
+                int j0, j1, e0, e1;
+                decode_key(k0, popq, j0, e0);
+                decode_key(k1, popq, j1, e1);
+                fwd[qi] = (float)e0 < (float)e1 * nnr ? j0 : -1;
+            }
+        }
+        for (int q0 = 0; q0 < b; q0 += kKnnQ) {
+            int k0, k1, popq;
+            knn2_sweep(t2, b, q0, t1, a, lm_lds, k0, k1, popq);
+            const int qi = q0 + threadIdx.x;
+            if (qi < b) {
+                int j0, j1, e0, e1;
+                decode_key(k0, popq, j0, e0);
+                decode_key(k1, popq, j1, e1);
+                back[qi] = (float)e0 < (float)e1 * nnr ? j0 : -1;
+            }
+        }
+    }
+    __syncthreads();
+    int local = 0;
+    for (int i = threadIdx.x; i < a; i += 256) {
+        int m = both ? fwd[i] : -1;
+        if (m >= 0 && back[m] != i) m = -1;
+        m12[(size_t)p * cap1 + i] = m;
+        local += m >= 0;
+    }
+    if (local) atomicAdd(&s_cnt, local);
+    __syncthreads();
+    if (threadIdx.x == 0) nmatch[p] = s_cnt;
+}
+
+// The matrix-core kernels serve train capacities the key's index field holds;
+// PLVI_MATCH_MFMA=0 (environment, read at every call; or -DPLVI_MATCH_MFMA=0 as
+// the default) sends every call to the VALU kernel and the three-launch line
+// matcher instead.
+#ifndef PLVI_MATCH_MFMA
+#define PLVI_MATCH_MFMA 1
+#endif
+constexpr int kLineFusedCap = 1024;  // one workgroup per pair up to this capacity on both sides
+
+static bool match_mfma_enabled() {
+    const char* e = getenv("PLVI_MATCH_MFMA");
+    return e && *e ? atoi(e) != 0 : PLVI_MATCH_MFMA != 0;
+}
+
 int launch_knn2(const uint8_t* d_q, const int* d_nq, int nq_cap, const uint8_t* d_t, const int* d_nt, int nt_cap,
                 int n_pairs, int* i0, int* d0, int* i1, int* d1, hipStream_t st) {
     if (n_pairs <= 0 || nq_cap <= 0) return PLVI_OK;
     dim3 grid((nq_cap + kKnnQ - 1) / kKnnQ, n_pairs);
-    hipLaunchKernelGGL(hamming_knn2_kernel, grid, dim3(256), 0, st, d_q, d_nq, nq_cap, d_t, d_nt, nt_cap, i0, d0, i1,
-                       d1);
+    if (nt_cap <= kKeyMaxTrain && match_mfma_enabled())
+        hipLaunchKernelGGL(hamming_knn2_mfma_kernel, grid, dim3(256), 0, st, d_q, d_nq, nq_cap, d_t, d_nt, nt_cap, i0,
+                           d0, i1, d1);
+    else
+        hipLaunchKernelGGL(hamming_knn2_kernel, grid, dim3(256), 0, st, d_q, d_nq, nq_cap, d_t, d_nt, nt_cap, i0, d0,
+                           i1, d1);
     PLVI_CHECK(hipGetLastError());
     return PLVI_OK;
 }
@@ -182,6 +395,14 @@ extern "C" int plvi_line_match_batch(const uint8_t* d_desc1, const int* d_n1, in
         return PLVI_E_BADARG;
     if (n_pairs == 0) return PLVI_OK;
     hipStream_t st = (hipStream_t)stream;
+    if (cap1 <= plvi::kLineFusedCap && cap2 <= plvi::kLineFusedCap && plvi::match_mfma_enabled()) {
+        // one launch, d_scratch unused
+        const size_t lds = plvi::kLdsPieces * sizeof(uint2) + (size_t)(std::max(cap1, 0) + std::max(cap2, 0)) * 4;
+        hipLaunchKernelGGL(plvi::line_match_fused_kernel, dim3(n_pairs), dim3(256), lds, st, d_desc1, d_n1, cap1,
+                           d_desc2, d_n2, cap2, nnr, d_matches_12, d_nmatch);
+        PLVI_CHECK(hipGetLastError());
+        return PLVI_OK;
+    }
     int* s = d_scratch;
     int *i0a = s, *d0a = s + (size_t)n_pairs * cap1, *i1a = s + 2 * (size_t)n_pairs * cap1,
         *d1a = s + 3 * (size_t)n_pairs * cap1;
