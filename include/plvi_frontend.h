@@ -1387,6 +1387,198 @@ int plvi_local_lines_filter_batch(int n_frames, const plvi_frustum_params* d_par
                                   const double* d_angle, const plvi_keyline* d_kl, const int* d_nkl, int kl_cap,
                                   const uint8_t* d_blocked, int* d_assign, int* d_nassigned, void* stream);
 
+/* -------------------------------------------------------------- Local map
+ * Tracking::UpdateLocalMap() / UpdateLocalMapWithLines() (src/Tracking.cc:
+ * 5304-5323; called once per tracked frame from TrackLocalMap :4153 /
+ * TrackLocalMapWithLines :4268): UpdateLocalKeyFrames[WithLines] (:5399-5551
+ * / :5553-5745) and UpdateLocalPoints[AndLines] (:5325-5352 / :5354-5397) for
+ * every frame of a batch.  The local lists come out as keyframe slots and
+ * pool ids, in the reference's order, together with the input tables of
+ * plvi_frustum_points_batch / plvi_frustum_lines_batch (and the desc table of
+ * plvi_search_local_batch), so the per-frame chain local map -> frustum ->
+ * grid -> search stays on the device.  Integers only: every output equals the
+ * reference's entry for entry.
+ *
+ * Keyframes live in the caller-chosen slots of the keyframe database
+ * ([0, kf_cap)); MapPoints and MapLines live in two pools indexed by id.
+ * All pointers of the four structs are device pointers for
+ * plvi_local_map_batch and host pointers for plvi_local_map.
+ *
+ * Semantics:
+ *   1. Vote (:5405-5421, :5559-5592).  Each voting feature that is not bad
+ *      adds 1 to every keyframe of its observation list; with lines, points
+ *      and lines vote into one counter.  A bad voting entry is written back
+ *      as -1 (:5418 / :5442, :5589 / :5632) and casts no vote.  An id outside
+ *      [0, n) is read as NULL.
+ *   2. K1 (:5456-5471).  `order` is walked; a keyframe with a count that is
+ *      not bad is listed (a bad one is skipped even with votes, :5460).
+ *      ref_kf = pKFmax = the first keyframe in that order whose count is
+ *      strictly above every earlier one (max starts at 0), -1 when nothing
+ *      was counted (mpReferenceKF is then left alone, :5546).  K1 is not
+ *      bounded; the 80 of :5477 limits the expansion only.
+ *   3. Expansion (:5474-5524).  itEndKF is taken before the loop and the
+ *      reserve(3 * size) of :5453 keeps it valid, so the loop visits the K1
+ *      members only, in order, and stops once the list holds more than 80
+ *      (size() > 80, tested before each visit).  Per visited keyframe: the
+ *      first covisible that is not bad and not listed; then the first child
+ *      in set order that is not bad and not listed; then the parent if it is
+ *      not listed -- no isBad() test -- and adding a parent leaves the OUTER
+ *      loop (:5521 / :5712): no later K1 member is expanded.
+ *   4. Temporal walk (:5527-5544).  Only with last_kf[f] >= 0 (and prev_kf
+ *      given) and fewer than 80 listed; at most 20 rounds; the walk moves to
+ *      mPrevKF only after an insertion, so it ends at the first listed
+ *      keyframe.
+ *   5. Points (:5331-5351).  The local keyframes in REVERSE list order, each
+ *      keyframe's table in index order, the first occurrence of every id that
+ *      is not NULL and not bad.  Lines likewise; the reference interleaves
+ *      them per keyframe (:5382-5395) into a list and a stamp of their own,
+ *      which the two outputs cannot show.
+ *   6. Not modelled.  mnTrackReferenceForFrame is written by these functions
+ *      only and they run once per frame id, so "already listed" is state of
+ *      one call: each frame of a batch is a fresh stamp.  A frame with mnId
+ *      == 0 equals the constructors' stamp 0 and would list nothing in the
+ *      reference; that is outside the model.
+ *
+ * Limits.  The vote histogram and the listed-set of a frame are kept in LDS
+ * up to PLVI_LOCAL_MAP_LDS_KF slots (33 KB) and in the scratch block above.
+ * The list passes run ceil(kf_cap * max(kp_cap, kl_cap) /
+ * PLVI_LOCAL_MAP_GROUP_ENTRIES) workgroups per frame and kind, at least 1 and
+ * at most PLVI_LOCAL_MAP_MAX_GROUPS, each over a contiguous
+ * ceil(n_local_kf * cap / workgroups) entries of the walk.  An entry's
+ * position in the walk is an int kept in a table whose "none" value is the
+ * byte fill 0x7f7f7f7f, so kf_cap * max(kp_cap, kl_cap) is at most
+ * PLVI_LOCAL_MAP_MAX_ENTRIES; more, or n_frames above 65535, returns
+ * PLVI_E_CAPACITY and nothing is launched. */
+#define PLVI_LOCAL_MAP_MAX_ENTRIES 0x7f7f7f7f /* largest kf_cap * max(kp_cap, kl_cap) */
+#define PLVI_LOCAL_MAP_LDS_KF 8192        /* largest kf_cap whose vote histogram is kept in LDS */
+#define PLVI_LOCAL_MAP_GROUP_ENTRIES 2048 /* keyframe-table entries per workgroup of the list passes */
+#define PLVI_LOCAL_MAP_MAX_GROUPS 64
+enum {
+  PLVI_LOCAL_MAP_ERR_KF = 1, /* mvpLocalKeyFrames is longer than lkf_cap */
+  PLVI_LOCAL_MAP_ERR_MP = 2, /* mvpLocalMapPoints is longer than lmp_cap */
+  PLVI_LOCAL_MAP_ERR_ML = 4, /* mvpLocalMapLines is longer than lml_cap */
+};
+
+/* The keyframe side, by slot. */
+typedef struct plvi_local_map_keyframes {
+  int kf_cap;           /* slots */
+  int n_order;          /* entries of order */
+  int kp_cap, kl_cap;   /* row lengths of mp / ml */
+  const uint8_t* bad;   /* [kf_cap] isBad(); 1 for an empty slot */
+  const int* order;     /* [n_order] the occupied slots as a std::map<KeyFrame*, int> iterates them
+                           (ascending address: INTEGRATION.md "Order"); a slot outside [0, kf_cap)
+                           is ignored; a slot named twice is listed once, at either of its two positions (which one is
+                           not specified: a std::map has no second key) */
+  const int* covis;     /* [kf_cap][PLVI_KFDB_NEIGHBOURS] GetBestCovisibilityKeyFrames(10), ended by -1
+                           (the table of plvi_kfdb_query_batch); NULL = none */
+  const int* child_off; /* [kf_cap + 1] CSR of GetChilds() in std::set<KeyFrame*> order; NULL (both) = none */
+  const int* child;
+  const int* parent;    /* [kf_cap] GetParent() or -1; NULL = none */
+  const int* prev_kf;   /* [kf_cap] mPrevKF or -1; NULL = no IMU sensor: the temporal walk never runs */
+  const int* mp;        /* [kf_cap][kp_cap] GetMapPointMatches() as pool ids, -1 = NULL */
+  const int* nmp;       /* [kf_cap] counts (count contract against kp_cap) */
+  const int* ml;        /* [kf_cap][kl_cap] GetMapLineMatches(); NULL selects the point-only functions */
+  const int* nml;
+} plvi_local_map_keyframes;
+
+/* One feature pool (MapPoints or MapLines), by id.  The attribute rows are
+ * optional: a NULL row cannot be gathered.  desc rows are moved as dwords and
+ * must be 4-byte aligned. */
+typedef struct plvi_local_map_pool {
+  int n;
+  const uint8_t* bad;  /* [n] isBad() */
+  const int* obs_off;  /* [n + 1] CSR of GetObservations() as keyframe slots; a keyframe appears once per */
+  const int* obs_kf;   /*         feature (observations are map keys); a slot outside [0, kf_cap) is ignored */
+  const float* pos;    /* MapPoints: [n][3] GetWorldPos() */
+  const double* sep;   /* MapLines:  [n][6] GetWorldPos() */
+  const float* normal; /* [n][3] GetNormal() */
+  const float* dist;   /* [n][2] mfMinDistance, mfMaxDistance */
+  const uint8_t* desc; /* [n][32] GetDescriptor() */
+} plvi_local_map_pool;
+
+/* Per frame f.  vote_*: the features that vote -- mCurrentFrame.mvpMapPoints,
+ * or mLastFrame.mvpMapPoints in the IMU branch (:5403 against :5423), the
+ * caller chooses -- as pool ids, -1 = NULL; in/out (semantics 1).  seen_*:
+ * the CURRENT frame's own tables, which decide in_flags bit0; NULL = the vote
+ * tables.  Every count follows the count contract (plvi_hamming_knn2_batch)
+ * against its capacity.  vote_ml / seen_ml are read only with keyframes->ml. */
+typedef struct plvi_local_map_frames {
+  int* vote_mp;         /* [f][vote_mp_cap]; NULL = no point votes */
+  const int* n_vote_mp; /* [f] */
+  int vote_mp_cap;
+  int* vote_ml;
+  const int* n_vote_ml;
+  int vote_ml_cap;
+  const int* seen_mp;   /* [f][seen_mp_cap] */
+  const int* n_seen_mp;
+  int seen_mp_cap;
+  const int* seen_ml;
+  const int* n_seen_ml;
+  int seen_ml_cap;
+  const int* last_kf;   /* [f] mCurrentFrame.mpLastKeyFrame for IMU sensors, -1 otherwise; NULL = all -1 */
+} plvi_local_map_frames;
+
+/* Per frame f.  The n_* counts are always written and are the FULL list
+ * lengths; list cells and gathered rows at or past min(count, capacity) are
+ * never written, and a list longer than its capacity sets its bit of err[f]
+ * (err[f] is written by every call, 0 when all three fit).  As counts they can
+ * be handed to the frustum calls as they are (the count contract clamps
+ * them).  The gathered tables have the layouts of plvi_frustum_points_batch
+ * (pos, normal, dist, in_flags; desc is the d_mp_desc of
+ * plvi_search_local_batch) and plvi_frustum_lines_batch (sep, normal, dist,
+ * in_flags, desc), row stride lmp_cap / lml_cap; each may be NULL (no
+ * gather).  in_flags bit0 = the id does not occur in the frame's seen table,
+ * bad entries not counted (mnLastFrameSeen != mnId after the first loop of
+ * SearchLocalPoints[AndLines], :5052-5069 / :5126-5161; a listed feature is
+ * never bad); bit1 = its observation list is not empty (Observations() > 0). */
+typedef struct plvi_local_map_outputs {
+  int lkf_cap, lmp_cap, lml_cap;
+  int* local_kf;   /* [f][lkf_cap] mvpLocalKeyFrames as slots */
+  int* n_local_kf; /* [f] */
+  int* ref_kf;     /* [f] pKFmax, -1 = leave mpReferenceKF alone */
+  int* local_mp;   /* [f][lmp_cap] mvpLocalMapPoints as pool ids */
+  int* n_local_mp;
+  int* local_ml;   /* [f][lml_cap] mvpLocalMapLines; written with keyframes->ml only */
+  int* n_local_ml;
+  float* mp_pos;
+  float* mp_normal;
+  float* mp_dist;
+  uint8_t* mp_in_flags;
+  uint8_t* mp_desc;
+  double* ml_sep;
+  float* ml_normal;
+  float* ml_dist;
+  uint8_t* ml_in_flags;
+  uint8_t* ml_desc;
+  int* err;        /* [f] PLVI_LOCAL_MAP_ERR_* */
+} plvi_local_map_outputs;
+
+/* Bytes of the scratch block of plvi_local_map_batch: per frame 4 * (mp_n +
+ * ml_n) for the first-occurrence tables, (mp_n + ml_n) / 8 for the seen-sets,
+ * 4 * kf_cap for the full keyframe list (+ 4.125 * kf_cap above
+ * PLVI_LOCAL_MAP_LDS_KF).  0 for a negative argument. */
+size_t plvi_local_map_scratch_bytes(int n_frames, int kf_cap, int mp_n, int ml_n);
+
+/* The batch call.  The structs themselves are host memory, read before the
+ * call returns; ml may be NULL without keyframes->ml.  d_scratch holds at
+ * least plvi_local_map_scratch_bytes(n_frames, kf_cap, mp->n, ml ? ml->n : 0)
+ * bytes (PLVI_E_BADARG below) and needs no initialisation; calls that share a
+ * scratch block must be ordered.  PLVI_E_BADARG for a negative size or a
+ * missing required pointer, PLVI_E_CAPACITY as stated under Limits, 0 without
+ * a launch for n_frames == 0.  Asynchronous on `stream`, no host read of
+ * device data, no allocation: capturable like the other batch calls. */
+int plvi_local_map_batch(int n_frames, const plvi_local_map_keyframes* kf, const plvi_local_map_pool* mp,
+                         const plvi_local_map_pool* ml, const plvi_local_map_frames* frames,
+                         const plvi_local_map_outputs* out, void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* One frame from host memory, synchronous: the same structs with host
+ * pointers (per-frame arrays of one frame).  Lists and gathered rows are
+ * copied back up to min(count, capacity); the vote tables are updated in
+ * place.  Returns 0, PLVI_E_CAPACITY when err[0] != 0 (counts and err are
+ * still written), or another error. */
+int plvi_local_map(const plvi_local_map_keyframes* kf, const plvi_local_map_pool* mp, const plvi_local_map_pool* ml,
+                   const plvi_local_map_frames* frames, const plvi_local_map_outputs* out);
+
 /* ---------------------------------------------------------------- Stereo
  * Rectified stereo of the stereo Frame constructors (src/Frame.cc:95-140,
  * :225-300). */

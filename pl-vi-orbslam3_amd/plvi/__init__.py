@@ -434,6 +434,9 @@ def _declare(lib):
         "plvi_frustum_lines_batch": ([I, V, V, V, V, V, V, V, I, V, V, V, V, V, V, V], I),
         "plvi_frustum_lines": ([V, V, V, V, V, V, I, V, V, V, V, V], I),
         "plvi_local_lines_filter_batch": ([I, V, V, V, V, I, V, V, V, V, I, V, V, V, V], I),
+        "plvi_local_map_scratch_bytes": ([I, I, I, I], S),
+        "plvi_local_map_batch": ([I, V, V, V, V, V, V, S, V], I),
+        "plvi_local_map": ([V, V, V, V, V], I),
         "plvi_device_malloc": ([c_void_pp, S], I),
         "plvi_device_free": ([V], I),
         "plvi_memcpy": ([V, V, S, I], I),
@@ -1950,3 +1953,258 @@ def stereo_lines_batch(n_frames, d_klL, d_descL, d_nL, capL, d_klR, d_descR, d_n
                                           V(d_nR), capR, V(d_klUn or 0), width, height, float(mbf), range_hint,
                                           idx_cap, V(d_scratch), scratch_bytes, V(d_m12), V(d_disp), V(d_depth),
                                           V(d_le), V(d_nstereo), V(d_err), V(stream or 0)), "plvi_stereo_lines_batch")
+
+
+LOCAL_MAP_LDS_KF = 8192         # PLVI_LOCAL_MAP_LDS_KF: largest kf_cap whose vote histogram is kept in LDS
+LOCAL_MAP_GROUP_ENTRIES = 2048  # PLVI_LOCAL_MAP_GROUP_ENTRIES: keyframe-table entries per workgroup of the list passes
+LOCAL_MAP_MAX_GROUPS = 64       # PLVI_LOCAL_MAP_MAX_GROUPS
+LOCAL_MAP_MAX_ENTRIES = 0x7f7f7f7f  # PLVI_LOCAL_MAP_MAX_ENTRIES: largest kf_cap * max(kp_cap, kl_cap)
+LOCAL_MAP_ERR_KF, LOCAL_MAP_ERR_MP, LOCAL_MAP_ERR_ML = 1, 2, 4
+
+_LM_V, _LM_I = ctypes.c_void_p, ctypes.c_int
+
+
+class LocalMapKeyframes(ctypes.Structure):
+    """plvi_local_map_keyframes (include/plvi_frontend.h); pointers as integers, 0 / None = NULL."""
+    _fields_ = [("kf_cap", _LM_I), ("n_order", _LM_I), ("kp_cap", _LM_I), ("kl_cap", _LM_I)] + \
+               [(k, _LM_V) for k in ("bad", "order", "covis", "child_off", "child", "parent", "prev_kf", "mp", "nmp",
+                                     "ml", "nml")]
+
+
+class LocalMapPool(ctypes.Structure):
+    """plvi_local_map_pool: MapPoints (pos) or MapLines (sep) by id."""
+    _fields_ = [("n", _LM_I)] + [(k, _LM_V) for k in ("bad", "obs_off", "obs_kf", "pos", "sep", "normal", "dist",
+                                                      "desc")]
+
+
+class LocalMapFrames(ctypes.Structure):
+    """plvi_local_map_frames: the per-frame vote / seen tables."""
+    _fields_ = [("vote_mp", _LM_V), ("n_vote_mp", _LM_V), ("vote_mp_cap", _LM_I),
+                ("vote_ml", _LM_V), ("n_vote_ml", _LM_V), ("vote_ml_cap", _LM_I),
+                ("seen_mp", _LM_V), ("n_seen_mp", _LM_V), ("seen_mp_cap", _LM_I),
+                ("seen_ml", _LM_V), ("n_seen_ml", _LM_V), ("seen_ml_cap", _LM_I), ("last_kf", _LM_V)]
+
+
+class LocalMapOutputs(ctypes.Structure):
+    """plvi_local_map_outputs: the lists, their full lengths, the gathered frustum tables and err."""
+    _fields_ = [("lkf_cap", _LM_I), ("lmp_cap", _LM_I), ("lml_cap", _LM_I)] + \
+               [(k, _LM_V) for k in ("local_kf", "n_local_kf", "ref_kf", "local_mp", "n_local_mp", "local_ml",
+                                     "n_local_ml", "mp_pos", "mp_normal", "mp_dist", "mp_in_flags", "mp_desc",
+                                     "ml_sep", "ml_normal", "ml_dist", "ml_in_flags", "ml_desc", "err")]
+
+
+def local_map_scratch_bytes(n_frames, kf_cap, mp_n, ml_n=0):
+    return load().plvi_local_map_scratch_bytes(n_frames, kf_cap, mp_n, ml_n)
+
+
+def local_map_batch(n_frames, kf, mp, ml, frames, out, d_scratch, scratch_bytes, stream=None):
+    """Tracking::UpdateLocalMap[WithLines] of n_frames frames on device tables (plvi_local_map_batch): kf / mp / ml
+    / frames / out are the four structs above holding device addresses (ml may be None).  Asynchronous on
+    `stream`; returns the status (negative = refused, nothing launched)."""
+    ref = lambda s: None if s is None else ctypes.byref(s)  # noqa: E731
+    return load().plvi_local_map_batch(n_frames, ref(kf), ref(mp), ref(ml), ref(frames), ref(out),
+                                       ctypes.c_void_p(d_scratch or 0), scratch_bytes, ctypes.c_void_p(stream or 0))
+
+
+_LM_ROWS = {"pos": (np.float32, 3), "sep": (np.float64, 6), "normal": (np.float32, 3), "dist": (np.float32, 2),
+            "desc": (np.uint8, 32)}
+
+
+class LocalMap:
+    """Tracking::UpdateLocalMap() / UpdateLocalMapWithLines() (src/Tracking.cc:5304-5323) over resident tables.
+
+    ``keyframes``: a dict of numpy arrays named as the fields of plvi_local_map_keyframes -- bad [kf_cap], order,
+    mp [kf_cap][kp_cap], nmp, and optionally covis [kf_cap][10], child_off / child, parent, prev_kf, ml / nml
+    (ml selects the points-and-lines functions).  ``points`` / ``lines``: dicts named as plvi_local_map_pool --
+    bad, obs_off, obs_kf and optionally pos (points) / sep (lines), normal, dist, desc.
+
+    ``update`` runs one frame through the synchronous host form; ``update_batch`` uploads the tables once (they
+    stay resident in ``self.dev``) and runs plvi_local_map_batch."""
+
+    def __init__(self, keyframes, points, lines=None):
+        self._lib = load()
+        kf = dict(keyframes)
+        i32 = lambda a: np.ascontiguousarray(a, np.int32)  # noqa: E731
+        self.kf = {"bad": np.ascontiguousarray(kf["bad"], np.uint8)}
+        for k in ("order", "covis", "child_off", "child", "parent", "prev_kf", "mp", "nmp", "ml", "nml"):
+            if kf.get(k) is not None:
+                self.kf[k] = i32(kf[k])
+        self.kf_cap = len(self.kf["bad"])
+        self.kp_cap = self.kf["mp"].shape[1] if "mp" in self.kf and self.kf["mp"].ndim == 2 else 0
+        self.kl_cap = self.kf["ml"].shape[1] if "ml" in self.kf and self.kf["ml"].ndim == 2 else 0
+        self.pools = [self._pool(points), None if lines is None else self._pool(lines)]
+        self.dev = None
+
+    @staticmethod
+    def _pool(p):
+        q = {"bad": np.ascontiguousarray(p["bad"], np.uint8), "obs_off": np.ascontiguousarray(p["obs_off"], np.int32),
+             "obs_kf": np.ascontiguousarray(p["obs_kf"], np.int32)}
+        for k, (dt, w) in _LM_ROWS.items():
+            if p.get(k) is not None:
+                q[k] = np.ascontiguousarray(p[k], dt).reshape(len(q["bad"]), w)
+        return q
+
+    def _structs(self, ptr):
+        """The keyframe and pool structs; ptr(group, name) -> the address of that table or None."""
+        kf = LocalMapKeyframes(self.kf_cap, len(self.kf.get("order", ())), self.kp_cap, self.kl_cap)
+        for k in self.kf:
+            setattr(kf, k, ptr("kf", k))
+        pools = []
+        for g, p in zip(("mp", "ml"), self.pools):
+            if p is None:
+                pools.append(None)
+                continue
+            s = LocalMapPool(len(p["bad"]))
+            for k in p:
+                setattr(s, k, ptr(g, k))
+            pools.append(s)
+        return kf, pools[0], pools[1]
+
+    def _tables(self):
+        t = {("kf", k): a for k, a in self.kf.items()}
+        for g, p in zip(("mp", "ml"), self.pools):
+            if p is not None:
+                t.update({(g, k): a for k, a in p.items()})
+        return t
+
+    def update(self, vote_mp, vote_ml=None, seen_mp=None, seen_ml=None, last_kf=-1, lkf_cap=None, lmp_cap=None,
+               lml_cap=None, counts=None):
+        """One frame from host arrays (plvi_local_map).  vote_* are updated in place when they are int32 arrays.
+        `counts` ({"vote_mp": n, ...}) overrides a table's count, which is its length otherwise (to pass values
+        outside [0, capacity]).
+        Returns a dict: local_kf, ref_kf, local_mp, local_ml, the gathered tables the pools have rows for
+        (mp_pos, mp_normal, mp_dist, mp_in_flags, mp_desc, ml_sep, ...), the full counts n_local_* and err."""
+        tabs = self._tables()
+        kf, mp, ml = self._structs(lambda g, k: tabs[(g, k)].ctypes.data)
+        lines = "ml" in self.kf
+        n_mp, n_ml = len(self.pools[0]["bad"]), len(self.pools[1]["bad"]) if self.pools[1] else 0
+        caps = [self.kf_cap if lkf_cap is None else lkf_cap, n_mp if lmp_cap is None else lmp_cap,
+                n_ml if lml_cap is None else lml_cap]
+        keep = []
+
+        def table(a, count):
+            if a is None:
+                return None, None, 0
+            a = a if isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous else \
+                np.ascontiguousarray(a, np.int32)
+            n = np.array([len(a) if count is None else count], np.int32)
+            keep.extend([a, n])
+            return a.ctypes.data if len(a) else None, n.ctypes.data, len(a)
+        fr = LocalMapFrames()
+        for name, a in (("vote_mp", vote_mp), ("vote_ml", vote_ml), ("seen_mp", seen_mp), ("seen_ml", seen_ml)):
+            p, n, cap = table(a, (counts or {}).get(name))
+            if a is not None and p is None:  # an empty table: a valid pointer with count 0
+                z = np.zeros(1, np.int32)
+                keep.append(z)
+                p = z.ctypes.data
+            setattr(fr, name, p)
+            setattr(fr, "n_" + name, n)
+            setattr(fr, name + "_cap", cap)
+        last = np.array([last_kf], np.int32)
+        fr.last_kf = last.ctypes.data
+        res = self._outputs(1, caps, lines, -1)
+        out = LocalMapOutputs(*caps)
+        for k, a in res.items():
+            setattr(out, k, a.ctypes.data)
+        rc = self._lib.plvi_local_map(ctypes.byref(kf), ctypes.byref(mp), None if ml is None else ctypes.byref(ml),
+                                      ctypes.byref(fr), ctypes.byref(out))
+        if rc < 0 and rc != PLVI_E_CAPACITY:
+            raise PlviError(rc, "plvi_local_map")
+        r = {k: a[0] for k, a in res.items()}
+        nk, npnt = min(r["n_local_kf"], caps[0]), min(r["n_local_mp"], caps[1])
+        r["local_kf"], r["local_mp"] = r["local_kf"][:nk], r["local_mp"][:npnt]
+        for k in list(r):
+            if k.startswith("mp_"):
+                r[k] = r[k][:npnt]
+        if lines:
+            nl = min(r["n_local_ml"], caps[2])
+            r["local_ml"] = r["local_ml"][:nl]
+            for k in list(r):
+                if k.startswith("ml_"):
+                    r[k] = r[k][:nl]
+        return r
+
+    def _outputs(self, B, caps, lines, fill, gathers=None):
+        """Host arrays for every output, pre-filled so that unwritten cells show."""
+        o = {"local_kf": np.full((B, max(caps[0], 1)), fill, np.int32), "n_local_kf": np.full(B, fill, np.int32),
+             "ref_kf": np.full(B, fill, np.int32), "local_mp": np.full((B, max(caps[1], 1)), fill, np.int32),
+             "n_local_mp": np.full(B, fill, np.int32), "err": np.full(B, fill, np.int32)}
+        if lines:
+            o["local_ml"] = np.full((B, max(caps[2], 1)), fill, np.int32)
+            o["n_local_ml"] = np.full(B, fill, np.int32)
+        for g, p, cap in (("mp", self.pools[0], caps[1]), ("ml", self.pools[1] if lines else None, caps[2])):
+            if p is None:
+                continue
+            for k, (dt, w) in list(_LM_ROWS.items()) + [("in_flags", (np.uint8, 1))]:
+                if (k == "in_flags" or k in p) and (gathers is None or k in gathers):
+                    shape = (B, max(cap, 1), w) if w > 1 else (B, max(cap, 1))
+                    o[f"{g}_{k}"] = np.full(shape, fill & 0x7f if dt == np.uint8 else fill, dt)
+        return o
+
+    def upload(self):
+        """Make the keyframe tables and pools resident (self.dev: (group, name) -> DeviceBuffer)."""
+        if self.dev is None:
+            self.dev = {}
+            for key, a in self._tables().items():
+                self.dev[key] = DeviceBuffer(a.nbytes)
+                self.dev[key].upload(a)
+        return self.dev
+
+    def update_batch(self, vote_mp, n_vote_mp, vote_ml=None, n_vote_ml=None, seen_mp=None, n_seen_mp=None,
+                     seen_ml=None, n_seen_ml=None, last_kf=None, lkf_cap=None, lmp_cap=None, lml_cap=None,
+                     gathers=None, fill=-7, stream=None, run=True):
+        """plvi_local_map_batch from host per-frame tables [B][cap] with every output downloaded: a dict of the
+        output arrays (whole, sentinel-filled with `fill` where nothing was written), the in/out vote tables
+        ("vote_mp" / "vote_ml"), "rc" and "d" (the output DeviceBuffers, for a device-side consumer).  `gathers`
+        limits the gathered tables (None = all the pools have rows for).  run=False returns a callable
+        step(stream) and a fetch() instead, for graph capture."""
+        dev = self.upload()
+        kf, mp, ml = self._structs(lambda g, k: dev[(g, k)].ptr)
+        lines = "ml" in self.kf
+        vote_mp = np.ascontiguousarray(vote_mp, np.int32)
+        B = vote_mp.shape[0]
+        n_mp, n_ml = len(self.pools[0]["bad"]), len(self.pools[1]["bad"]) if self.pools[1] else 0
+        caps = [self.kf_cap if lkf_cap is None else lkf_cap, n_mp if lmp_cap is None else lmp_cap,
+                n_ml if lml_cap is None else lml_cap]
+        fr, fbuf, host_in = LocalMapFrames(), {}, {}
+        for name, a, n in (("vote_mp", vote_mp, n_vote_mp), ("vote_ml", vote_ml, n_vote_ml),
+                           ("seen_mp", seen_mp, n_seen_mp), ("seen_ml", seen_ml, n_seen_ml)):
+            if a is None:
+                continue
+            a, n = np.ascontiguousarray(a, np.int32), np.ascontiguousarray(n, np.int32)
+            host_in[name] = a
+            for key, arr in ((name, a), ("n_" + name, n)):
+                fbuf[key] = DeviceBuffer(arr.nbytes)
+                fbuf[key].upload(arr)
+                setattr(fr, key, fbuf[key].ptr)
+            setattr(fr, name + "_cap", a.shape[1])
+        if last_kf is not None:
+            lk = np.ascontiguousarray(last_kf, np.int32)
+            fbuf["last_kf"] = DeviceBuffer(lk.nbytes)
+            fbuf["last_kf"].upload(lk)
+            fr.last_kf = fbuf["last_kf"].ptr
+        res = self._outputs(B, caps, lines, fill, gathers)
+        out, obuf = LocalMapOutputs(*caps), {}
+        for k, a in res.items():
+            obuf[k] = DeviceBuffer(a.nbytes)
+            obuf[k].upload(a)
+            setattr(out, k, obuf[k].ptr)
+        sb = local_map_scratch_bytes(B, self.kf_cap, n_mp, n_ml if lines else 0)
+        scratch = DeviceBuffer(sb)
+
+        def step(s=None):
+            return local_map_batch(B, kf, mp, ml if lines else None, fr, out, scratch.ptr, sb, s)
+
+        def fetch(rc=0):
+            _check(self._lib.plvi_device_synchronize(), "plvi_device_synchronize")
+            for k, a in res.items():
+                obuf[k].download(a)
+            r = dict(res)
+            for name in ("vote_mp", "vote_ml"):
+                if name in host_in:
+                    r[name] = fbuf[name].download(np.empty_like(host_in[name]))
+            r.update(rc=rc, d=obuf, keep=(fbuf, scratch))
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
