@@ -1579,6 +1579,157 @@ int plvi_local_map_batch(int n_frames, const plvi_local_map_keyframes* kf, const
 int plvi_local_map(const plvi_local_map_keyframes* kf, const plvi_local_map_pool* mp, const plvi_local_map_pool* ml,
                    const plvi_local_map_frames* frames, const plvi_local_map_outputs* out);
 
+/* ------------------------------------------------------ Covisibility graph
+ * KeyFrame::UpdateConnections / UpdateConnectionsWithLines
+ * (src/KeyFrame.cc:499-622 / :624-769) for a batch of keyframes, with
+ * AddConnection (:201-214), UpdateBestCovisibles (:216-238), EraseConnection
+ * (:1154-1168), GetCovisiblesByWeight (:265-286) and GetWeight (:288-295), over
+ * a device-resident graph.  It writes the covis table that plvi_kfdb_query_batch
+ * and plvi_local_map_batch read, and the parent table of the latter.  Integers
+ * only: every list equals the reference's entry for entry.
+ *
+ * The graph (plvi_covis_graph) holds, per keyframe slot of [0, kf_cap):
+ *   the weight map   mConnectedKeyFrameWeights as unsorted (slot, weight)
+ *                    pairs, at most conn_cap;
+ *   the ordered list mvpOrderedConnectedKeyFrames / mvOrderedWeights, at most
+ *                    conn_cap, descending by (weight, address);
+ *   an error bit     set when either would exceed conn_cap: the excess is
+ *                    dropped, the slot's state is then unspecified (memory
+ *                    safety is not) until the slot is erased or updated again.
+ *
+ * Semantics of one query keyframe q (plvi_covis_update_batch):
+ *   1. Count (:512-531).  Every entry of mp[q] (and of ml[q] with lines) that
+ *      is not NULL, in range and not bad adds 1 to every keyframe of its
+ *      observation list; one id twice counts twice.  A keyframe is left out if
+ *      it is q itself, is bad, has another map_id, lies outside [0, kf_cap) or
+ *      is not named in `order`.  An empty counter changes nothing (:534):
+ *      n_counted = n_conn = 0, kf_max = -1, new_parent = -1.
+ *   2. Walk (:547-567) in `order`.  kf_max / w_max = the first keyframe whose
+ *      count is strictly above every earlier one.  Every keyframe with a count
+ *      >= PLVI_COVIS_TH is listed and receives AddConnection(q, count); if
+ *      there is none, kf_max alone.
+ *   3. q's ordered list = the listed pairs, descending by (weight, address)
+ *      -- sort() on pair<int, KeyFrame*> and push_front, :569-576; the address
+ *      is the position in `order`, so of two equal weights the LATER keyframe
+ *      of `order` comes first; NOT filtered for bad.  q's weight map = the whole counter,
+ *      entries below the threshold included (:582).
+ *   4. AddConnection on a neighbour: insert or overwrite q's entry; an entry
+ *      that already held the weight leaves the neighbour alone; otherwise its
+ *      ordered list becomes its WHOLE weight map minus the bad keyframes,
+ *      sorted as in 3.  A list built by 3 and one built by 4 differ.
+ *   5. Parent (:593-619).  With first_conn[q] set and init_kf[q] clear:
+ *      parent[q] = the front of the new list, first_conn[q] = 0, new_parent =
+ *      that slot (the caller does AddChild); -1 otherwise.
+ * A batch equals the reference applied to the queries one after another in
+ * index order: a keyframe that is itself query j (with a counter) loses the
+ * connections added by the queries before j, whose own update overwrites them.
+ * A slot of a map entry that `order` no longer names has an address above
+ * the named ones, by slot.
+ *
+ * covis rows.  Every slot whose ordered list is rewritten gets its row of the
+ * caller's covis [kf_cap][PLVI_KFDB_NEIGHBOURS] rewritten whole: the first
+ * min(n, 10) entries, -1 in the cells after them.
+ *
+ * Limits.  conn_cap <= PLVI_COVIS_MAX_CONN (a list is sorted in LDS), kf_cap
+ * <= 2^24, n_queries <= 65535: PLVI_E_CAPACITY beyond.  The vote histogram is
+ * in LDS up to PLVI_COVIS_LDS_KF slots and in the scratch block above.  The
+ * calls on one graph must be ordered (one stream, or events): they share its
+ * work tables. */
+#define PLVI_COVIS_LDS_KF 8192   /* largest kf_cap whose vote histogram is kept in LDS */
+#define PLVI_COVIS_MAX_CONN 2048 /* largest conn_cap */
+#define PLVI_COVIS_TH 15         /* th of KeyFrame.cc:541 */
+#define PLVI_COVIS_MAX_QUERIES 65535
+
+typedef struct plvi_covis_graph plvi_covis_graph;
+
+/* The keyframe side, by slot; the layouts of plvi_local_map_keyframes.  Device
+ * pointers for the batch call, host pointers for plvi_covis_update. */
+typedef struct plvi_covis_keyframes {
+  int kf_cap;             /* slots; equals the graph's */
+  int n_order;            /* entries of order */
+  int kp_cap, kl_cap;     /* row lengths of mp / ml */
+  const uint8_t* bad;     /* [kf_cap] isBad(); 1 for an empty slot */
+  const int* order;       /* [n_order] the occupied slots in ascending address; a slot named twice counts at its
+                             first position */
+  const int* mp;          /* [kf_cap][kp_cap] mvpMapPoints as pool ids, -1 = NULL */
+  const int* nmp;         /* [kf_cap] counts (count contract against kp_cap) */
+  const int* ml;          /* [kf_cap][kl_cap] mvpMapLines; NULL selects UpdateConnections */
+  const int* nml;
+  const int* map_id;      /* [kf_cap] GetMap() as an id; NULL = one map */
+  const uint8_t* init_kf; /* [kf_cap] mnId == mpMap->GetInitKFid(); NULL = none */
+  uint8_t* first_conn;    /* [kf_cap] mbFirstConnection, in/out; NULL (with parent) = semantics 5 is skipped */
+  int* parent;            /* [kf_cap] mpParent as a slot, in/out */
+  int* covis;             /* [kf_cap][PLVI_KFDB_NEIGHBOURS] out; may be NULL */
+} plvi_covis_keyframes;
+
+/* Per query, all required. */
+typedef struct plvi_covis_outputs {
+  int* n_counted;  /* KFcounter.size() */
+  int* n_conn;     /* length of the ordered list built (before the cut at conn_cap) */
+  int* kf_max;     /* pKFmax, -1 for an empty counter */
+  int* w_max;      /* nmax */
+  int* new_parent; /* the parent set by semantics 5, -1 = unchanged */
+  int* err;        /* 1 = the query's map or list exceeded conn_cap */
+} plvi_covis_outputs;
+
+/* PLVI_E_BADARG for kf_cap < 1 or conn_cap < 1, PLVI_E_CAPACITY above the
+ * limits.  Device memory: 16 * kf_cap * conn_cap + 32 * kf_cap bytes. */
+int plvi_covis_create(int kf_cap, int conn_cap, int device, plvi_covis_graph** out);
+int plvi_covis_destroy(plvi_covis_graph* h);
+
+/* Bytes of the scratch block of plvi_covis_update_batch: 4 * n_queries *
+ * kf_cap above PLVI_COVIS_LDS_KF, a few bytes below.  0 for a negative
+ * argument. */
+size_t plvi_covis_scratch_bytes(int n_queries, int kf_cap);
+
+/* The batch call.  q_slot [n_queries] is host memory, read before the call
+ * returns; a slot outside [0, kf_cap) or named twice returns PLVI_E_BADARG and
+ * nothing is launched.  mp / ml: only n, bad, obs_off, obs_kf are read; ml ==
+ * NULL or kf->ml == NULL selects the point-only function.  n_queries == 0
+ * returns 0 without a launch.  Asynchronous on `stream`, no host read of
+ * device data, no allocation: capturable like the other batch calls. */
+int plvi_covis_update_batch(plvi_covis_graph* h, int n_queries, const int* q_slot, const plvi_covis_keyframes* kf,
+                            const plvi_local_map_pool* mp, const plvi_local_map_pool* ml,
+                            const plvi_covis_outputs* out, void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* The connection part of SetBadFlag (:894-897, :915-916) for n slots (host
+ * array, distinct, in range: PLVI_E_BADARG otherwise): EraseConnection(slot) on
+ * every key of the slot's weight map -- the entry removed if present and only
+ * then the neighbour re-sorted as in semantics 4 -- then the slot's own map,
+ * list and error bit cleared.  Order-free.  d_bad / d_order as in
+ * plvi_covis_keyframes; d_covis may be NULL.  The spanning tree stays with
+ * the caller. */
+int plvi_covis_erase_batch(plvi_covis_graph* h, int n, const int* slots, const uint8_t* d_bad, const int* d_order,
+                           int n_order, int* d_covis, void* stream);
+
+/* A bare UpdateBestCovisibles (LocalMapping.cc:1573, :1727) of n slots. */
+int plvi_covis_resort_batch(plvi_covis_graph* h, int n, const int* slots, const uint8_t* d_bad, const int* d_order,
+                            int n_order, int* d_covis, void* stream);
+
+/* GetCovisiblesByWeight(d_w[i]) of slot d_slot[i]: d_count[i] = the length of
+ * the prefix of the ordered list with weight >= w (0 for a slot out of
+ * range). */
+int plvi_covis_by_weight_batch(plvi_covis_graph* h, int n, const int* d_slot, const int* d_w, int* d_count,
+                               void* stream);
+
+/* d_weight[i] = d_a[i]->GetWeight(d_b[i]): the map entry or 0. */
+int plvi_covis_weight_batch(plvi_covis_graph* h, int n, const int* d_a, const int* d_b, int* d_weight, void* stream);
+
+/* Device pointers to the ordered tables [kf_cap][conn_cap] and their counts
+ * [kf_cap] (GetVectorCovisibleKeyFrames without a copy); each may be NULL. */
+int plvi_covis_rows(plvi_covis_graph* h, const int** d_ord_kf, const int** d_ord_w, const int** d_ord_n, int* conn_cap);
+
+/* Host copies of one slot, synchronous: the map in ascending slot order, the
+ * ordered list as stored; tables of conn_cap entries, each may be NULL. */
+int plvi_covis_download(plvi_covis_graph* h, int slot, int* map_kf, int* map_w, int* n_map, int* ord_kf, int* ord_w,
+                        int* n_ord, int* err);
+
+/* One keyframe from host tables, synchronous: first_conn, parent and covis
+ * are updated in place (whole tables), out holds one entry each.  Returns 0,
+ * PLVI_E_CAPACITY when err[0] != 0, or another error. */
+int plvi_covis_update(plvi_covis_graph* h, int slot, const plvi_covis_keyframes* kf, const plvi_local_map_pool* mp,
+                      const plvi_local_map_pool* ml, const plvi_covis_outputs* out);
+
 /* ---------------------------------------------------------------- Stereo
  * Rectified stereo of the stereo Frame constructors (src/Frame.cc:95-140,
  * :225-300). */

@@ -28,6 +28,7 @@
 #include <cstring>
 
 #include "host_stage.h"
+#include "kf_vote.h"
 #include "plvi_common.h"
 
 namespace plvi {
@@ -75,32 +76,6 @@ struct LmArgs {
     LmSide s[2];
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// exclusive scan of v over a workgroup of NW waves (every thread calls it); *total = the sum
-template <int NW>
-__device__ int block_scan(int v, int* s_wave, int tid, int* total) {
-    const int lane = tid & (kWave - 1), wv = tid / kWave;
-    int incl = v;
-#pragma unroll
-    for (int m = 1; m < kWave; m <<= 1) {
-        const int up = __shfl_up(incl, m, kWave);
-        if (lane >= m) incl += up;
-    }
-    __syncthreads();  // s_wave may still be read from the previous call
-    if (lane == kWave - 1) s_wave[wv] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        const int x = s_wave[w];
-        if (w < wv) base += x;
-        tot += x;
-    }
-    *total = tot;
-    return base + incl - v;
-}
-
 __device__ __forceinline__ bool is_listed(const unsigned* listed, int s) { return listed[s >> 5] >> (s & 31) & 1u; }
 
 __global__ __launch_bounds__(kKfThreads) void lm_keyframes_kernel(LmArgs a) {
@@ -141,11 +116,7 @@ __global__ __launch_bounds__(kKfThreads) void lm_keyframes_kernel(LmArgs a) {
                     continue;
                 }
                 if (!S.seen) atomicOr(bits + (id >> 5), 1u << (id & 31));
-                const int o1 = S.obs_off[id + 1];
-                for (int o = S.obs_off[id]; o < o1; ++o) {
-                    const int kf = S.obs_kf[o];
-                    if ((unsigned)kf < (unsigned)K) atomicAdd(hist + kf, 1);
-                }
+                vote_observations(hist, K, S.obs_off, S.obs_kf, id);
             }
         }
         // the current frame's own table where it is not the voting one (the IMU branch votes with

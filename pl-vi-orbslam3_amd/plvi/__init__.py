@@ -437,6 +437,17 @@ def _declare(lib):
         "plvi_local_map_scratch_bytes": ([I, I, I, I], S),
         "plvi_local_map_batch": ([I, V, V, V, V, V, V, S, V], I),
         "plvi_local_map": ([V, V, V, V, V], I),
+        "plvi_covis_create": ([I, I, I, c_void_pp], I),
+        "plvi_covis_destroy": ([V], I),
+        "plvi_covis_scratch_bytes": ([I, I], S),
+        "plvi_covis_update_batch": ([V, I, V, V, V, V, V, V, S, V], I),
+        "plvi_covis_erase_batch": ([V, I, V, V, V, I, V, V], I),
+        "plvi_covis_resort_batch": ([V, I, V, V, V, I, V, V], I),
+        "plvi_covis_by_weight_batch": ([V, I, V, V, V, V], I),
+        "plvi_covis_weight_batch": ([V, I, V, V, V, V], I),
+        "plvi_covis_rows": ([V, c_void_pp, c_void_pp, c_void_pp, P], I),
+        "plvi_covis_download": ([V, I, V, V, P, V, V, P, P], I),
+        "plvi_covis_update": ([V, I, V, V, V, V], I),
         "plvi_device_malloc": ([c_void_pp, S], I),
         "plvi_device_free": ([V], I),
         "plvi_memcpy": ([V, V, S, I], I),
@@ -2208,3 +2219,203 @@ class LocalMap:
         if not run:
             return step, fetch
         return fetch(step(stream))
+
+
+COVIS_LDS_KF = 8192     # PLVI_COVIS_LDS_KF: largest kf_cap whose vote histogram is kept in LDS
+COVIS_MAX_CONN = 2048   # PLVI_COVIS_MAX_CONN: largest conn_cap
+COVIS_TH = 15           # PLVI_COVIS_TH: th of KeyFrame::UpdateConnections
+COVIS_MAX_QUERIES = 65535  # PLVI_COVIS_MAX_QUERIES
+
+
+class CovisKeyframes(ctypes.Structure):
+    """plvi_covis_keyframes (include/plvi_frontend.h); pointers as integers, 0 / None = NULL."""
+    _fields_ = [("kf_cap", _LM_I), ("n_order", _LM_I), ("kp_cap", _LM_I), ("kl_cap", _LM_I)] + \
+               [(k, _LM_V) for k in ("bad", "order", "mp", "nmp", "ml", "nml", "map_id", "init_kf", "first_conn",
+                                     "parent", "covis")]
+
+
+class CovisOutputs(ctypes.Structure):
+    """plvi_covis_outputs: one int per query each."""
+    _fields_ = [(k, _LM_V) for k in ("n_counted", "n_conn", "kf_max", "w_max", "new_parent", "err")]
+
+
+def covis_scratch_bytes(n_queries, kf_cap):
+    return load().plvi_covis_scratch_bytes(n_queries, kf_cap)
+
+
+_COVIS_KF = {"bad": np.uint8, "order": np.int32, "mp": np.int32, "nmp": np.int32, "ml": np.int32, "nml": np.int32,
+             "map_id": np.int32, "init_kf": np.uint8, "first_conn": np.uint8, "parent": np.int32, "covis": np.int32}
+_COVIS_OUT = tuple(k for k, _ in CovisOutputs._fields_)
+
+
+class Covisibility:
+    """The covisibility graph of KeyFrame::UpdateConnections[WithLines] (src/KeyFrame.cc:499-769) over resident
+    tables (plvi_covis_*): per keyframe slot the weight map and the ordered list, kept on the device.
+
+    ``set_tables(keyframes, points, lines=None)``: dicts of numpy arrays named as the fields of
+    plvi_covis_keyframes (bad, order, mp, nmp and optionally ml / nml, map_id, init_kf, first_conn, parent, covis)
+    and plvi_local_map_pool (bad, obs_off, obs_kf).  ``update_batch`` runs on device copies of them (``self.dev``;
+    first_conn / parent / covis are updated there, ``table(name)`` downloads one); ``update`` runs one keyframe
+    through the synchronous host form and updates the host arrays in place."""
+
+    def __init__(self, kf_cap, conn_cap, device=0):
+        self._lib = load()
+        h = ctypes.c_void_p()
+        _check(self._lib.plvi_covis_create(kf_cap, conn_cap, device, ctypes.byref(h)), "plvi_covis_create")
+        self.h, self.kf_cap, self.conn_cap = h, kf_cap, conn_cap
+        self.kf, self.pools, self.dev = {}, [None, None], {}
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._lib.plvi_covis_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_tables(self, keyframes, points, lines=None):
+        self.kf = {k: np.ascontiguousarray(keyframes[k], dt) for k, dt in _COVIS_KF.items()
+                   if keyframes.get(k) is not None}
+        pool = lambda p: None if p is None else {  # noqa: E731
+            "bad": np.ascontiguousarray(p["bad"], np.uint8), "obs_off": np.ascontiguousarray(p["obs_off"], np.int32),
+            "obs_kf": np.ascontiguousarray(p["obs_kf"], np.int32)}
+        self.pools = [pool(points), pool(lines)]
+        self.dev = {}
+        for key, a in self._tables().items():
+            self.put(key[0], key[1], a)
+        return self
+
+    def _tables(self):
+        t = {("kf", k): a for k, a in self.kf.items()}
+        for g, p in zip(("mp", "ml"), self.pools):
+            if p is not None:
+                t.update({(g, k): a for k, a in p.items()})
+        return t
+
+    def put(self, group, name, a):
+        """Replace one resident table (group "kf", "mp" or "ml")."""
+        a = np.ascontiguousarray(a, _COVIS_KF[name] if group == "kf" else (np.uint8 if name == "bad" else np.int32))
+        (self.kf if group == "kf" else self.pools[group == "ml"])[name] = a
+        self.dev[(group, name)] = DeviceBuffer(a.nbytes)
+        self.dev[(group, name)].upload(a)
+
+    def table(self, name):
+        """Download a keyframe table (first_conn, parent, covis, ...) from the device."""
+        return self.dev[("kf", name)].download(np.empty_like(self.kf[name]))
+
+    def _structs(self, ptr):
+        shape = lambda k: self.kf[k].shape[1] if k in self.kf and self.kf[k].ndim == 2 else 0  # noqa: E731
+        kf = CovisKeyframes(self.kf_cap, len(self.kf.get("order", ())), shape("mp"), shape("ml"))
+        for k in self.kf:
+            setattr(kf, k, ptr("kf", k))
+        pools = []
+        for g, p in zip(("mp", "ml"), self.pools):
+            if p is None:
+                pools.append(None)
+                continue
+            s = LocalMapPool(len(p["bad"]))
+            for k in p:
+                setattr(s, k, ptr(g, k))
+            pools.append(s)
+        return kf, pools[0], pools[1]
+
+    def update_batch(self, q_slots, fill=-7, stream=None, run=True):
+        """plvi_covis_update_batch of the keyframes q_slots, in that order.  Returns a dict of the per-query
+        outputs (sentinel-filled with `fill` where nothing was written), "past" (the cell after the last query of
+        each output: `fill` unless something wrote past the batch) and "rc".  run=False returns (step(stream),
+        fetch()) instead, for graph capture."""
+        q = np.ascontiguousarray(q_slots, np.int32)
+        B = len(q)
+        kf, mp, ml = self._structs(lambda g, k: self.dev[(g, k)].ptr)
+        res = {k: np.full(B + 1, fill, np.int32) for k in _COVIS_OUT}   # one cell more than is written
+        out, obuf = CovisOutputs(), {}
+        for k, a in res.items():
+            obuf[k] = DeviceBuffer(a.nbytes)
+            obuf[k].upload(a)
+            setattr(out, k, obuf[k].ptr)
+        sb = covis_scratch_bytes(B, self.kf_cap)
+        scratch = DeviceBuffer(sb)
+        ref = lambda s: None if s is None else ctypes.byref(s)  # noqa: E731
+
+        def step(s=None):
+            return self._lib.plvi_covis_update_batch(self.h, B, _ptr(q), ref(kf), ref(mp), ref(ml), ref(out),
+                                                     ctypes.c_void_p(scratch.ptr), sb, ctypes.c_void_p(s or 0))
+
+        def fetch(rc=0):
+            _check(self._lib.plvi_device_synchronize(), "plvi_device_synchronize")
+            r = {k: obuf[k].download(a)[:B] for k, a in res.items()}
+            r.update(rc=rc, past=[int(a[B]) for a in res.values()], keep=(scratch, q))
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
+
+    def update(self, slot):
+        """One keyframe through the host form (plvi_covis_update): the host arrays first_conn / parent / covis
+        given to set_tables are updated in place.  Returns the dict of outputs (ints) and "rc"."""
+        tabs = self._tables()
+        kf, mp, ml = self._structs(lambda g, k: tabs[(g, k)].ctypes.data)
+        res = {k: np.full(1, -7, np.int32) for k in _COVIS_OUT}
+        out = CovisOutputs(*[a.ctypes.data for a in res.values()])
+        rc = self._lib.plvi_covis_update(self.h, int(slot), ctypes.byref(kf), ctypes.byref(mp),
+                                         None if ml is None else ctypes.byref(ml), ctypes.byref(out))
+        if rc < 0 and rc != PLVI_E_CAPACITY:
+            raise PlviError(rc, "plvi_covis_update")
+        r = {k: int(a[0]) for k, a in res.items()}
+        r["rc"] = rc
+        return r
+
+    def _slots_call(self, fn, slots, stream):
+        s = np.ascontiguousarray(slots, np.int32)
+        cov = self.dev.get(("kf", "covis"))
+        return fn(self.h, len(s), _ptr(s), ctypes.c_void_p(self.dev[("kf", "bad")].ptr),
+                  ctypes.c_void_p(self.dev[("kf", "order")].ptr), len(self.kf["order"]),
+                  ctypes.c_void_p(cov.ptr if cov else 0), ctypes.c_void_p(stream or 0))
+
+    def erase(self, slots, stream=None):
+        """The connection part of SetBadFlag for `slots` (plvi_covis_erase_batch); returns the status."""
+        return self._slots_call(self._lib.plvi_covis_erase_batch, slots, stream)
+
+    def resort(self, slots, stream=None):
+        """UpdateBestCovisibles of `slots` (plvi_covis_resort_batch); returns the status."""
+        return self._slots_call(self._lib.plvi_covis_resort_batch, slots, stream)
+
+    def _pairs(self, fn, a, b, what):
+        a, b = np.ascontiguousarray(a, np.int32), np.ascontiguousarray(b, np.int32)
+        assert a.shape == b.shape
+        da, db, do = DeviceBuffer(a.nbytes), DeviceBuffer(b.nbytes), DeviceBuffer(a.nbytes)
+        da.upload(a)
+        db.upload(b)
+        _check(fn(self.h, len(a), ctypes.c_void_p(da.ptr), ctypes.c_void_p(db.ptr), ctypes.c_void_p(do.ptr), None), what)
+        _check(self._lib.plvi_device_synchronize(), "plvi_device_synchronize")
+        return do.download(np.empty_like(a))
+
+    def by_weight(self, slots, weights):
+        """len(GetCovisiblesByWeight(w)) per (slot, w)."""
+        return self._pairs(self._lib.plvi_covis_by_weight_batch, slots, weights, "plvi_covis_by_weight_batch")
+
+    def weight(self, a, b):
+        """a->GetWeight(b) per pair of slots."""
+        return self._pairs(self._lib.plvi_covis_weight_batch, a, b, "plvi_covis_weight_batch")
+
+    def rows(self):
+        """(ord_kf, ord_w, ord_n) device addresses of the ordered tables [kf_cap][conn_cap] and their counts."""
+        p = [ctypes.c_void_p() for _ in range(3)]
+        c = ctypes.c_int()
+        _check(self._lib.plvi_covis_rows(self.h, *[ctypes.byref(x) for x in p], ctypes.byref(c)), "plvi_covis_rows")
+        return tuple(x.value for x in p)
+
+    def download(self, slot, fill=-7):
+        """One slot's state: dict(map_kf, map_w (ascending slot), ord_kf, ord_w (as stored), err).  The arrays are
+        conn_cap + 1 long and sentinel-filled past their counts n_map / n_ord."""
+        C = self.conn_cap
+        t = {k: np.full(C + 1, fill, np.int32) for k in ("map_kf", "map_w", "ord_kf", "ord_w")}
+        n = [ctypes.c_int() for _ in range(3)]
+        _check(self._lib.plvi_covis_download(self.h, int(slot), _ptr(t["map_kf"]), _ptr(t["map_w"]), ctypes.byref(n[0]),
+                                             _ptr(t["ord_kf"]), _ptr(t["ord_w"]), ctypes.byref(n[1]),
+                                             ctypes.byref(n[2])), "plvi_covis_download")
+        t.update(n_map=n[0].value, n_ord=n[1].value, err=n[2].value)
+        return t
