@@ -375,46 +375,25 @@ extern "C" int plvi_search_by_bow_stereo(float nnratio, int check_orientation, c
     const int kf_cap = std::max(kf_n, 1), f_cap = f_n, node_cap = std::max(std::max(kf_nnodes, f_nnodes), 1);
     const int nkf_idx = kf_nnodes ? kf_off[kf_nnodes] : 0, nf_idx = f_nnodes ? f_off[f_nnodes] : 0;
     if (nkf_idx > kf_cap || nf_idx > f_cap) return PLVI_E_BADARG;
-    // one device block: [kf_desc | f_desc | kf_angle | f_angle | kf_live | ints...]
-    std::vector<int> ints;
-    auto put = [&](const int* src, int n, int cap) {
-        const size_t at = ints.size();
-        ints.resize(at + (size_t)cap, 0);
-        if (n > 0) std::copy(src, src + n, ints.begin() + at);
-        return at;
-    };
-    const size_t oKN = put(kf_node, kf_nnodes, node_cap), oKO = put(kf_off, kf_nnodes + 1, node_cap + 1);
-    const size_t oKC = put(&kf_nnodes, 1, 1), oKI = put(kf_idx, nkf_idx, kf_cap);
-    const size_t oFN = put(f_node, f_nnodes, node_cap), oFO = put(f_off, f_nnodes + 1, node_cap + 1);
-    const size_t oFC = put(&f_nnodes, 1, 1), oFI = put(f_idx, nf_idx, f_cap), oFn = put(&f_n, 1, 1);
-    const size_t oOut = put(nullptr, 0, f_cap), oCnt = put(nullptr, 0, 1), oNl = put(&f_nleft, 1, 1);
-    const size_t bytes8 = (size_t)(kf_cap + f_cap) * 32 + (size_t)(kf_cap + f_cap) * 4 + (size_t)kf_cap;
-    const size_t intOff = (bytes8 + 15) / 16 * 16;
-    DevBuf d;
-    if (d.alloc(intOff + ints.size() * 4)) return PLVI_E_HIP;
-    uint8_t* base = d.as<uint8_t>();
-    uint8_t* dKD = base;
-    uint8_t* dFD = dKD + (size_t)kf_cap * 32;
-    float* dKA = reinterpret_cast<float*>(dFD + (size_t)f_cap * 32);
-    float* dFA = dKA + kf_cap;
-    uint8_t* dKL = reinterpret_cast<uint8_t*>(dFA + f_cap);
-    int* dI = reinterpret_cast<int*>(base + intOff);
-    if (kf_n) {
-        PLVI_CHECK(hipMemcpy(dKD, kf_desc, (size_t)kf_n * 32, hipMemcpyHostToDevice));
-        PLVI_CHECK(hipMemcpy(dKA, kf_angle, (size_t)kf_n * 4, hipMemcpyHostToDevice));
-        PLVI_CHECK(hipMemcpy(dKL, kf_live, (size_t)kf_n, hipMemcpyHostToDevice));
-    }
-    PLVI_CHECK(hipMemcpy(dFD, f_desc, (size_t)f_n * 32, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(dFA, f_angle, (size_t)f_n * 4, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(dI, ints.data(), ints.size() * 4, hipMemcpyHostToDevice));
-    int rc = plvi_search_by_bow_stereo_batch(1, nnratio, check_orientation, kf_cap, f_cap, node_cap, dKD, dKA, dKL,
-                                             dI + oKN, dI + oKO, dI + oKC, dI + oKI, dFD, dFA, dI + oFn, dI + oFN,
-                                             dI + oFO, dI + oFC, dI + oFI, dI + oNl, dI + oOut, dI + oCnt, nullptr);
-    if (rc) return rc;
-    int cnt = 0;
-    PLVI_CHECK(hipMemcpy(match_kf, dI + oOut, (size_t)f_n * 4, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(&cnt, dI + oCnt, 4, hipMemcpyDeviceToHost));
-    return cnt;
+    int counts[5] = {kf_nnodes, f_nnodes, f_n, f_nleft, 0};  // [4]: nmatches
+    HostStage h;
+    const auto KD = h.in_or_zero(kf_desc, kf_n, 32), KL = h.in_or_zero(kf_live, kf_n);
+    const auto FD = h.in_or_zero(f_desc, f_n, 32);
+    const auto KA = h.in_or_zero(kf_angle, kf_n), FA = h.in_or_zero(f_angle, f_n);
+    const auto KN = h.in_or_zero(kf_node, kf_nnodes, 1, node_cap), FN = h.in_or_zero(f_node, f_nnodes, 1, node_cap);
+    const auto KO = h.in_or_zero(kf_off, kf_nnodes + 1, 1, node_cap + 1);
+    const auto FO = h.in_or_zero(f_off, f_nnodes + 1, 1, node_cap + 1);
+    const auto KI = h.in_or_zero(kf_idx, nkf_idx, 1, kf_cap), FI = h.in_or_zero(f_idx, nf_idx, 1, f_cap);
+    const auto M = h.out_or_scratch(match_kf, f_n), Cnt = h.inout(counts, 5);
+    if (int rc = h.commit()) return rc;
+    int* cnt = h.dev(Cnt);
+    if (int rc = plvi_search_by_bow_stereo_batch(1, nnratio, check_orientation, kf_cap, f_cap, node_cap, h.dev(KD),
+                                                 h.dev(KA), h.dev(KL), h.dev(KN), h.dev(KO), cnt, h.dev(KI), h.dev(FD),
+                                                 h.dev(FA), cnt + 2, h.dev(FN), h.dev(FO), cnt + 1, h.dev(FI), cnt + 3,
+                                                 h.dev(M), cnt + 4, nullptr))
+        return rc;
+    if (int rc = h.fetch()) return rc;
+    return counts[4];
 }
 
 extern "C" int plvi_search_by_bow(float nnratio, int check_orientation, const uint8_t* kf_desc, const float* kf_angle,
@@ -469,29 +448,22 @@ extern "C" int plvi_search_by_bow_kf(float nnratio, int check_orientation, const
     const int node_cap = std::max(std::max(nnodes1, nnodes2), 1);
     const int len1 = nnodes1 ? off1[nnodes1] : 0, len2 = nnodes2 ? off2[nnodes2] : 0;
     if (len1 < 0 || len1 > n1 || len2 < 0 || len2 > n2) return PLVI_E_BADARG;
+    int counts[5] = {n1, n2, nnodes1, nnodes2, 0};  // [4]: nmatches
     HostStage h;
-    const size_t sCnt = h.put(5 * sizeof(int));
-    const size_t sD1 = h.put((size_t)n1 * 32), sA1 = h.put((size_t)n1 * 4), sL1 = h.put((size_t)n1);
-    const size_t sN1 = h.put((size_t)node_cap * 4), sO1 = h.put((size_t)(node_cap + 1) * 4);
-    const size_t sI1 = h.put((size_t)n1 * 4);
-    const size_t sD2 = h.put((size_t)n2 * 32), sA2 = h.put((size_t)n2 * 4), sL2 = h.put((size_t)n2);
-    const size_t sN2 = h.put((size_t)node_cap * 4), sO2 = h.put((size_t)(node_cap + 1) * 4);
-    const size_t sI2 = h.put((size_t)n2 * 4), sM = h.put((size_t)n1 * 4);
-    if (int rc = h.alloc(true)) return rc;
-    const int counts[5] = {n1, n2, nnodes1, nnodes2, 0};
-    if (h.up(sCnt, counts, sizeof(counts)) | h.up(sD1, desc1, (size_t)n1 * 32) | h.up(sA1, angle1, (size_t)n1 * 4) |
-        h.up(sL1, live1, (size_t)n1) | h.up(sN1, node1, (size_t)nnodes1 * 4) |
-        h.up(sO1, off1, nnodes1 ? (size_t)(nnodes1 + 1) * 4 : 0) | h.up(sI1, idx1, (size_t)len1 * 4) |
-        h.up(sD2, desc2, (size_t)n2 * 32) | h.up(sA2, angle2, (size_t)n2 * 4) | h.up(sL2, live2, (size_t)n2) |
-        h.up(sN2, node2, (size_t)nnodes2 * 4) | h.up(sO2, off2, nnodes2 ? (size_t)(nnodes2 + 1) * 4 : 0) |
-        h.up(sI2, idx2, (size_t)len2 * 4))
-        return PLVI_E_HIP;
-    int* cnt = h.at<int>(sCnt);
-    if (int rc = plvi_search_by_bow_kf_batch(1, nnratio, check_orientation, n1, n2, node_cap, h.at<uint8_t>(sD1),
-                                             h.at<float>(sA1), h.at<uint8_t>(sL1), cnt, h.at<int>(sN1),
-                                             h.at<int>(sO1), cnt + 2, h.at<int>(sI1), h.at<uint8_t>(sD2),
-                                             h.at<float>(sA2), h.at<uint8_t>(sL2), cnt + 1, h.at<int>(sN2),
-                                             h.at<int>(sO2), cnt + 3, h.at<int>(sI2), h.at<int>(sM), cnt + 4, nullptr))
+    const auto D1 = h.in(desc1, n1, 32), L1 = h.in(live1, n1), D2 = h.in(desc2, n2, 32), L2 = h.in(live2, n2);
+    const auto A1 = h.in(angle1, n1), A2 = h.in(angle2, n2);
+    const auto N1 = h.in_or_zero(node1, nnodes1, 1, node_cap), N2 = h.in_or_zero(node2, nnodes2, 1, node_cap);
+    const auto O1 = h.in_or_zero(off1, nnodes1 ? nnodes1 + 1 : 0, 1, node_cap + 1);
+    const auto O2 = h.in_or_zero(off2, nnodes2 ? nnodes2 + 1 : 0, 1, node_cap + 1);
+    const auto I1 = h.in_or_zero(idx1, len1, 1, n1), I2 = h.in_or_zero(idx2, len2, 1, n2);
+    const auto M = h.out(matches12, n1), Cnt = h.inout(counts, 5);
+    if (int rc = h.commit()) return rc;
+    int* cnt = h.dev(Cnt);
+    if (int rc = plvi_search_by_bow_kf_batch(1, nnratio, check_orientation, n1, n2, node_cap, h.dev(D1), h.dev(A1),
+                                             h.dev(L1), cnt, h.dev(N1), h.dev(O1), cnt + 2, h.dev(I1), h.dev(D2),
+                                             h.dev(A2), h.dev(L2), cnt + 1, h.dev(N2), h.dev(O2), cnt + 3, h.dev(I2),
+                                             h.dev(M), cnt + 4, nullptr))
         return rc;
-    return h.finish(cnt + 4, matches12, sM, n1);
+    if (int rc = h.fetch()) return rc;
+    return counts[4];
 }

@@ -26,8 +26,8 @@
 #include <cstring>
 #include <vector>
 
-#include "host_stage.h"
 #include "kf_vote.h"
+#include "map_pool.h"
 #include "plvi_common.h"
 
 namespace plvi {
@@ -373,8 +373,6 @@ __global__ void covis_weight_kernel(CovState g, int n, const int* a, const int* 
     weight[i] = w;
 }
 
-static size_t cov_up256(size_t v) { return (v + 255) & ~size_t(255); }
-
 }  // namespace plvi
 
 using namespace plvi;
@@ -396,7 +394,7 @@ extern "C" int plvi_covis_create(int kf_cap, int conn_cap, int device, plvi_covi
     plvi_covis_graph* h = new plvi_covis_graph;
     h->device = device;
     h->stamp.assign(kf_cap, 0);
-    const size_t K = (size_t)kf_cap, cells = 4 * K * conn_cap, row = cov_up256(4 * K);
+    const size_t K = (size_t)kf_cap, cells = 4 * K * conn_cap, row = up256(4 * K);
     if (h->map_kf.alloc(cells) || h->map_w.alloc(cells) || h->ord_kf.alloc(cells) || h->ord_w.alloc(cells) ||
         h->small.alloc(8 * row) || hipMemset(h->small.p, 0, 8 * row) != hipSuccess) {
         delete h;
@@ -425,7 +423,7 @@ extern "C" int plvi_covis_destroy(plvi_covis_graph* h) {
 
 extern "C" size_t plvi_covis_scratch_bytes(int n_queries, int kf_cap) {
     if (n_queries < 0 || kf_cap < 0) return 0;
-    return 256 + (kf_cap > kCovLdsKf ? cov_up256(4 * (size_t)n_queries * kf_cap) : 0);
+    return 256 + (kf_cap > kCovLdsKf ? up256(4 * (size_t)n_queries * kf_cap) : 0);
 }
 
 // every slot in range and named once
@@ -471,15 +469,11 @@ static int cov_resort(plvi_covis_graph* h, const uint8_t* d_bad, int n_order, in
     return PLVI_OK;
 }
 
-static bool cov_pool_ok(const plvi_local_map_pool* p) {
-    return p->n >= 0 && (p->n == 0 || (p->bad && p->obs_off && p->obs_kf));
-}
-
 static int cov_validate(plvi_covis_graph* h, int n_queries, const plvi_covis_keyframes* kf,
                         const plvi_local_map_pool* mp, const plvi_local_map_pool* ml, const plvi_covis_outputs* out) {
     if (!h || n_queries < 0 || !kf || !mp || !out) return PLVI_E_BADARG;
-    if (kf->kf_cap != h->g.K || kf->n_order < 0 || kf->kp_cap < 0 || kf->kl_cap < 0 || !cov_pool_ok(mp) ||
-        (ml && !cov_pool_ok(ml)))
+    if (kf->kf_cap != h->g.K || kf->n_order < 0 || kf->kp_cap < 0 || kf->kl_cap < 0 || !pool_ok(mp) ||
+        (ml && !pool_ok(ml)))
         return PLVI_E_BADARG;
     if (n_queries == 0) return PLVI_OK;
     const bool with_lines = kf->ml && ml;
@@ -663,71 +657,34 @@ extern "C" int plvi_covis_update(plvi_covis_graph* h, int slot, const plvi_covis
     PLVI_CHECK(hipSetDevice(h->device));
     const bool with_lines = kf->ml && ml;
     const size_t K = (size_t)kf->kf_cap;
-    HostStage hs;
-    struct Copy {
-        size_t slot;
-        const void* src;
-        void* back;
-        size_t bytes;
-    };
-    std::vector<Copy> cp;
-    const size_t none = (size_t)-1;
-    auto stage = [&](const void* src, size_t bytes, void* back) {
-        if (!src && !back) return none;
-        cp.push_back({hs.put(bytes + 4), src, back, bytes});
-        return cp.size() - 1;
-    };
-    auto in = [&](const void* src, size_t bytes) { return stage(src, bytes, nullptr); };
-    const size_t i_bad = in(kf->bad, K), i_ord = in(kf->order, 4 * (size_t)kf->n_order),
-                 i_mp = in(kf->mp, 4 * K * kf->kp_cap), i_nmp = in(kf->nmp, 4 * K),
-                 i_ml = with_lines ? in(kf->ml, 4 * K * kf->kl_cap) : none, i_nml = with_lines ? in(kf->nml, 4 * K) : none,
-                 i_mid = in(kf->map_id, 4 * K), i_init = in(kf->init_kf, K),
-                 i_fc = stage(kf->first_conn, K, kf->first_conn), i_par = stage(kf->parent, 4 * K, kf->parent),
-                 i_cov = stage(kf->covis, 4 * K * kCovNb, kf->covis);
-    size_t i_p[2][3] = {{none, none, none}, {none, none, none}};
-    for (int k = 0; k < 1 + (with_lines ? 1 : 0); ++k) {
-        const plvi_local_map_pool* p = k ? ml : mp;
-        const size_t n = (size_t)p->n;
-        const size_t n_obs = n ? (size_t)(p->obs_off[n] > 0 ? p->obs_off[n] : 0) : 0;
-        i_p[k][0] = in(p->bad, n);
-        i_p[k][1] = in(p->obs_off, 4 * (n + 1));
-        i_p[k][2] = in(p->obs_kf, 4 * n_obs);
-    }
-    int* outs[6] = {out->n_counted, out->n_conn, out->kf_max, out->w_max, out->new_parent, out->err};
-    size_t i_out[6];
-    for (int i = 0; i < 6; ++i) i_out[i] = stage(nullptr, 4, outs[i]);
-    const size_t sb = plvi_covis_scratch_bytes(1, kf->kf_cap);
-    const size_t i_scr = hs.put(sb);
-    if (int rc = hs.alloc()) return rc;
-    for (const Copy& c : cp)
-        if (int rc = hs.up(c.slot, c.src, c.bytes)) return rc;
-    auto dev = [&](size_t i) -> void* { return i == none ? nullptr : hs.at<void>(cp[i].slot); };
+    // copies of the caller's structs: commit() turns their host pointers into device pointers
     plvi_covis_keyframes dk = *kf;
-    dk.bad = (const uint8_t*)dev(i_bad);
-    dk.order = (const int*)dev(i_ord);
-    dk.mp = (const int*)dev(i_mp);
-    dk.nmp = (const int*)dev(i_nmp);
-    dk.ml = (const int*)dev(i_ml);
-    dk.nml = (const int*)dev(i_nml);
-    dk.map_id = (const int*)dev(i_mid);
-    dk.init_kf = (const uint8_t*)dev(i_init);
-    dk.first_conn = (uint8_t*)dev(i_fc);
-    dk.parent = (int*)dev(i_par);
-    dk.covis = (int*)dev(i_cov);
-    plvi_local_map_pool dp[2] = {*mp, with_lines ? *ml : *mp};
-    for (int k = 0; k < 2; ++k) {
-        dp[k].bad = (const uint8_t*)dev(i_p[k][0]);
-        dp[k].obs_off = (const int*)dev(i_p[k][1]);
-        dp[k].obs_kf = (const int*)dev(i_p[k][2]);
-    }
-    plvi_covis_outputs dout;
-    int** douts[6] = {&dout.n_counted, &dout.n_conn, &dout.kf_max, &dout.w_max, &dout.new_parent, &dout.err};
-    for (int i = 0; i < 6; ++i) *douts[i] = (int*)dev(i_out[i]);
-    if (int rc = plvi_covis_update_batch(h, 1, &slot, &dk, &dp[0], with_lines ? &dp[1] : nullptr, &dout,
-                                         hs.at<void>(i_scr), sb, nullptr))
+    plvi_local_map_pool dmp = *mp, dml = with_lines ? *ml : plvi_local_map_pool{};
+    plvi_covis_outputs dout = *out;
+    if (!with_lines) dk.ml = dk.nml = nullptr;
+    HostStage hs;
+    const HostStage::Dir In = HostStage::In, InOut = HostStage::InOut, Out = HostStage::Out;
+    hs.field(dk.bad, In, K);
+    hs.field(dk.order, In, kf->n_order);
+    hs.field(dk.mp, In, K, kf->kp_cap);
+    hs.field(dk.nmp, In, K);
+    hs.field(dk.ml, In, K, kf->kl_cap);
+    hs.field(dk.nml, In, K);
+    hs.field(dk.map_id, In, K);
+    hs.field(dk.init_kf, In, K);
+    hs.field(dk.first_conn, InOut, K);
+    hs.field(dk.parent, InOut, K);
+    hs.field(dk.covis, InOut, K, kCovNb);
+    stage_pool(hs, dmp, kPoolObs);
+    if (with_lines) stage_pool(hs, dml, kPoolObs);
+    for (int** o : {&dout.n_counted, &dout.n_conn, &dout.kf_max, &dout.w_max, &dout.new_parent, &dout.err})
+        hs.field(*o, Out, 1);
+    const size_t sb = plvi_covis_scratch_bytes(1, kf->kf_cap);
+    const auto scr = hs.scratch<uint8_t>(sb);
+    if (int rc = hs.commit()) return rc;
+    if (int rc = plvi_covis_update_batch(h, 1, &slot, &dk, &dmp, with_lines ? &dml : nullptr, &dout, hs.dev(scr), sb,
+                                         nullptr))
         return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    for (const Copy& c : cp)
-        if (c.back && c.bytes) PLVI_CHECK(hipMemcpy(c.back, hs.at<void>(c.slot), c.bytes, hipMemcpyDeviceToHost));
+    if (int rc = hs.fetch()) return rc;
     return *out->err ? PLVI_E_CAPACITY : PLVI_OK;
 }

@@ -29,6 +29,7 @@
 #include <cstring>
 #include <vector>
 
+#include "host_stage.h"
 #include "plvi_common.h"
 
 namespace plvi {
@@ -299,27 +300,25 @@ extern "C" int plvi_distinctive_descriptors(const uint8_t* pool, int pool_rows, 
     const size_t n_obs = (size_t)obs_off[n_feat];
     if ((n_obs && !obs_row) || (pool_rows && !pool)) return PLVI_E_BADARG;
     if (max_obs > PLVI_DISTINCTIVE_MAX_OBS) return PLVI_E_CAPACITY;
-    DevBuf dP, dO, dR, dB, dM, dD;
-    if (dP.alloc(32 * (size_t)pool_rows + 32) || dO.alloc(4 * ((size_t)n_feat + 1)) || dR.alloc(4 * n_obs + 4) ||
-        dB.alloc(4 * (size_t)n_feat) || dM.alloc(4 * (size_t)n_feat) || dD.alloc(32 * (size_t)n_feat))
-        return PLVI_E_HIP;
-    if (pool_rows) PLVI_CHECK(hipMemcpy(dP.p, pool, 32 * (size_t)pool_rows, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(dO.p, obs_off, 4 * ((size_t)n_feat + 1), hipMemcpyHostToDevice));
-    if (n_obs) PLVI_CHECK(hipMemcpy(dR.p, obs_row, 4 * n_obs, hipMemcpyHostToDevice));
-    if (int rc = plvi_distinctive_descriptors_batch(n_feat, dP.as<uint8_t>(), pool_rows, dO.as<int>(), dR.as<int>(),
-                                                    max_obs, dB.as<int>(), dM.as<int>(), dD.as<uint8_t>(), nullptr))
+    // rows with best_pos = -1 stay as the caller left them: the rows come back into a copy
+    std::vector<uint8_t> rows(out_desc ? 32 * (size_t)n_feat : 0);
+    HostStage st;
+    const auto P = st.in_or_zero(pool, pool_rows, 32);
+    const auto O = st.in(obs_off, n_feat + 1);
+    const auto R = st.in_or_zero(obs_row, n_obs);
+    const auto B = st.out(best_pos, n_feat);
+    const auto M = st.out(best_median, n_feat);
+    const auto D = st.out_or_scratch(out_desc ? rows.data() : nullptr, n_feat, 32);
+    if (int rc = st.commit()) return rc;
+    if (int rc = plvi_distinctive_descriptors_batch(n_feat, st.dev(P), pool_rows, st.dev(O), st.dev(R), max_obs,
+                                                    st.dev(B), st.dev(M), st.dev(D), nullptr))
         return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    PLVI_CHECK(hipMemcpy(best_pos, dB.p, 4 * (size_t)n_feat, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(best_median, dM.p, 4 * (size_t)n_feat, hipMemcpyDeviceToHost));
+    if (int rc = st.fetch()) return rc;
     int count = 0;
-    for (int i = 0; i < n_feat; ++i) count += best_pos[i] >= 0;
-    if (out_desc && count) {
-        // rows with best_pos = -1 stay as the caller left them
-        std::vector<uint8_t> tmp(32 * (size_t)n_feat);
-        PLVI_CHECK(hipMemcpy(tmp.data(), dD.p, tmp.size(), hipMemcpyDeviceToHost));
-        for (int i = 0; i < n_feat; ++i)
-            if (best_pos[i] >= 0) memcpy(out_desc + 32 * (size_t)i, tmp.data() + 32 * (size_t)i, 32);
+    for (int i = 0; i < n_feat; ++i) {
+        if (best_pos[i] < 0) continue;
+        ++count;
+        if (out_desc) memcpy(out_desc + 32 * (size_t)i, rows.data() + 32 * (size_t)i, 32);
     }
     return count;
 }

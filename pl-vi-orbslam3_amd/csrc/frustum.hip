@@ -34,6 +34,7 @@
 #include <cstring>
 #include <vector>
 
+#include "host_stage.h"
 #include "plvi_common.h"
 #include "plvi_math.h"
 
@@ -395,19 +396,6 @@ extern "C" int plvi_frustum_points_batch(int n_frames, const plvi_frustum_params
     return PLVI_OK;
 }
 
-namespace {
-// Device scratch of the synchronous one-frame entry points.
-struct Slots {
-    std::vector<size_t> off;
-    size_t tot = 0;
-    size_t put(size_t bytes) {
-        off.push_back(tot);
-        tot += (bytes + 255) & ~size_t(255);
-        return off.size() - 1;
-    }
-};
-}  // namespace
-
 extern "C" int plvi_frustum_points(const plvi_frustum_params* p, const float* pos, const float* normal,
                                    const float* dist, const uint8_t* in_flags, int n, uint8_t* flags, float* proj,
                                    int* level, float* proj_r, int* level_r, float* depth) {
@@ -415,46 +403,24 @@ extern "C" int plvi_frustum_points(const plvi_frustum_params* p, const float* po
     if (n == 0) return 0;
     if (!pos || !normal || !dist || !in_flags || !flags || !proj || !level || !depth) return PLVI_E_BADARG;
     if (p->two_camera && (!proj_r || !level_r)) return PLVI_E_BADARG;
-    Slots s;
-    const size_t oPar = s.put(sizeof(plvi_frustum_params)), oPos = s.put(12 * (size_t)n), oNr = s.put(12 * (size_t)n);
-    const size_t oD = s.put(8 * (size_t)n), oIF = s.put(n), oF = s.put(n), oP = s.put(16 * (size_t)n);
-    const size_t oL = s.put(4 * (size_t)n), oPR = s.put(16 * (size_t)n), oLR = s.put(4 * (size_t)n);
-    const size_t oDe = s.put(4 * (size_t)n), oN = s.put(8);
-    DevBuf d;
-    if (d.alloc(s.tot)) return PLVI_E_HIP;
-    uint8_t* B = d.as<uint8_t>();
-    auto up = [&](size_t slot, const void* src, size_t bytes) -> int {
-        PLVI_CHECK(hipMemcpy(B + s.off[slot], src, bytes, hipMemcpyHostToDevice));
-        return PLVI_OK;
-    };
-    int rc = up(oPar, p, sizeof *p) | up(oPos, pos, 12 * (size_t)n) | up(oNr, normal, 12 * (size_t)n) |
-             up(oD, dist, 8 * (size_t)n) | up(oIF, in_flags, n) | up(oP, proj, 16 * (size_t)n) |
-             up(oL, level, 4 * (size_t)n) | up(oDe, depth, 4 * (size_t)n);
-    if (p->two_camera) rc |= up(oPR, proj_r, 16 * (size_t)n) | up(oLR, level_r, 4 * (size_t)n);
-    rc |= up(oN, &n, 4);
-    if (rc) return PLVI_E_HIP;
-    int* dN = reinterpret_cast<int*>(B + s.off[oN]);
-    rc = plvi_frustum_points_batch(1, reinterpret_cast<const plvi_frustum_params*>(B + s.off[oPar]),
-                                   reinterpret_cast<const float*>(B + s.off[oPos]),
-                                   reinterpret_cast<const float*>(B + s.off[oNr]),
-                                   reinterpret_cast<const float*>(B + s.off[oD]), B + s.off[oIF], dN, n, B + s.off[oF],
-                                   reinterpret_cast<float*>(B + s.off[oP]), reinterpret_cast<int*>(B + s.off[oL]),
-                                   p->two_camera ? reinterpret_cast<float*>(B + s.off[oPR]) : nullptr,
-                                   p->two_camera ? reinterpret_cast<int*>(B + s.off[oLR]) : nullptr,
-                                   reinterpret_cast<float*>(B + s.off[oDe]), dN + 1, nullptr);
-    if (rc) return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    int nvis = 0;
-    PLVI_CHECK(hipMemcpy(flags, B + s.off[oF], n, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(proj, B + s.off[oP], 16 * (size_t)n, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(level, B + s.off[oL], 4 * (size_t)n, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(depth, B + s.off[oDe], 4 * (size_t)n, hipMemcpyDeviceToHost));
-    if (p->two_camera) {
-        PLVI_CHECK(hipMemcpy(proj_r, B + s.off[oPR], 16 * (size_t)n, hipMemcpyDeviceToHost));
-        PLVI_CHECK(hipMemcpy(level_r, B + s.off[oLR], 4 * (size_t)n, hipMemcpyDeviceToHost));
-    }
-    PLVI_CHECK(hipMemcpy(&nvis, dN + 1, 4, hipMemcpyDeviceToHost));
-    return nvis;
+    int counts[2] = {n, 0};  // [1]: nvisible
+    HostStage st;
+    const auto Par = st.in(p, 1);
+    const auto Pos = st.in(pos, n, 3), Nr = st.in(normal, n, 3), D = st.in(dist, n, 2);
+    const auto IF = st.in(in_flags, n), F = st.out(flags, n);
+    // in/out: an entry the kernel does not write keeps the caller's value
+    const auto P = st.inout(proj, n, 4), De = st.inout(depth, n);
+    const auto PR = p->two_camera ? st.inout(proj_r, n, 4) : Staged<float>{};
+    const auto LR = p->two_camera ? st.inout(level_r, n) : Staged<int>{};
+    const auto L = st.inout(level, n), N = st.inout(counts, 2);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = plvi_frustum_points_batch(1, st.dev(Par), st.dev(Pos), st.dev(Nr), st.dev(D), st.dev(IF), dN, n,
+                                           st.dev(F), st.dev(P), st.dev(L), st.dev(PR), st.dev(LR), st.dev(De), dN + 1,
+                                           nullptr))
+        return rc;
+    if (int rc = st.fetch()) return rc;
+    return counts[1];
 }
 
 extern "C" int plvi_frustum_lines_batch(int n_frames, const plvi_frustum_params* d_params, const double* d_sep,
@@ -480,45 +446,26 @@ extern "C" int plvi_frustum_lines(const plvi_frustum_params* p, const double* se
     if (!p || n < 0) return PLVI_E_BADARG;
     if (n == 0) return 0;
     if (!sep || !normal || !dist || !in_flags || !inview || !proj || !angle || !compact) return PLVI_E_BADARG;
-    Slots s;
-    const size_t oPar = s.put(sizeof(plvi_frustum_params)), oS = s.put(48 * (size_t)n), oNr = s.put(12 * (size_t)n);
-    const size_t oD = s.put(8 * (size_t)n), oIF = s.put(n), oDs = s.put(32 * (size_t)n), oIV = s.put(n);
-    const size_t oP = s.put(16 * (size_t)n), oA = s.put(8 * (size_t)n), oC = s.put(4 * (size_t)n);
-    const size_t oCD = s.put(32 * (size_t)n), oN = s.put(8);
-    DevBuf d;
-    if (d.alloc(s.tot)) return PLVI_E_HIP;
-    uint8_t* B = d.as<uint8_t>();
-    auto up = [&](size_t slot, const void* src, size_t bytes) -> int {
-        PLVI_CHECK(hipMemcpy(B + s.off[slot], src, bytes, hipMemcpyHostToDevice));
-        return PLVI_OK;
-    };
-    int rc = up(oPar, p, sizeof *p) | up(oS, sep, 48 * (size_t)n) | up(oNr, normal, 12 * (size_t)n) |
-             up(oD, dist, 8 * (size_t)n) | up(oIF, in_flags, n) | up(oP, proj, 16 * (size_t)n) |
-             up(oA, angle, 8 * (size_t)n) | up(oN, &n, 4);
-    if (desc) rc |= up(oDs, desc, 32 * (size_t)n);
-    if (rc) return PLVI_E_HIP;
-    int* dN = reinterpret_cast<int*>(B + s.off[oN]);
-    rc = plvi_frustum_lines_batch(1, reinterpret_cast<const plvi_frustum_params*>(B + s.off[oPar]),
-                                  reinterpret_cast<const double*>(B + s.off[oS]),
-                                  reinterpret_cast<const float*>(B + s.off[oNr]),
-                                  reinterpret_cast<const float*>(B + s.off[oD]), B + s.off[oIF],
-                                  desc ? B + s.off[oDs] : nullptr, dN, n, B + s.off[oIV],
-                                  reinterpret_cast<float*>(B + s.off[oP]), reinterpret_cast<double*>(B + s.off[oA]),
-                                  reinterpret_cast<int*>(B + s.off[oC]), desc ? B + s.off[oCD] : nullptr, dN + 1,
-                                  nullptr);
-    if (rc) return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    int nc = 0;
-    PLVI_CHECK(hipMemcpy(&nc, dN + 1, 4, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(inview, B + s.off[oIV], n, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(proj, B + s.off[oP], 16 * (size_t)n, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(angle, B + s.off[oA], 8 * (size_t)n, hipMemcpyDeviceToHost));
-    if (nc > 0) {
-        PLVI_CHECK(hipMemcpy(compact, B + s.off[oC], 4 * (size_t)nc, hipMemcpyDeviceToHost));
-        if (desc && compact_desc)
-            PLVI_CHECK(hipMemcpy(compact_desc, B + s.off[oCD], 32 * (size_t)nc, hipMemcpyDeviceToHost));
-    }
-    return nc;
+    int counts[2] = {n, 0};  // [1]: ncompact
+    HostStage st;
+    const auto Par = st.in(p, 1);
+    const auto S = st.in(sep, n, 6), A = st.inout(angle, n);
+    const auto Nr = st.in(normal, n, 3), D = st.in(dist, n, 2), P = st.inout(proj, n, 4);
+    const auto IF = st.in(in_flags, n), Ds = st.in(desc, n, 32), IV = st.out(inview, n);
+    // the descriptors are compacted whenever there are descriptors, wanted on the host or not
+    const auto CD = desc ? st.out_or_scratch(compact_desc, n, 32) : Staged<uint8_t>{};
+    const auto C = st.out(compact, n), N = st.inout(counts, 2);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = plvi_frustum_lines_batch(1, st.dev(Par), st.dev(S), st.dev(Nr), st.dev(D), st.dev(IF), st.dev(Ds), dN,
+                                          n, st.dev(IV), st.dev(P), st.dev(A), st.dev(C), st.dev(CD), dN + 1, nullptr))
+        return rc;
+    // the count first: compact / compact_desc come back up to it
+    if (int rc = st.fetch_one(N)) return rc;
+    st.trim(C, counts[1]);
+    st.trim(CD, counts[1], 32);
+    if (int rc = st.fetch()) return rc;
+    return counts[1];
 }
 
 extern "C" int plvi_local_lines_filter_batch(int n_frames, const plvi_frustum_params* d_params, int* d_matches_12,

@@ -289,31 +289,24 @@ extern "C" int plvi_fuse_points(const plvi_fuse_params* p, const plvi_keypoint* 
         return 0;
     }
     const int kc = n_kp, pc = n_pt;
+    int counts[3] = {n_kp, n_pt, 0};  // [2]: nfused
     HostStage st;
-    const size_t oK = st.put(sizeof(plvi_keypoint) * kc), oD = st.put(32 * (size_t)kc), oU = st.put(4 * (size_t)kc);
-    const size_t oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)kc), oF = st.put(pc);
-    const size_t oX = st.put(12 * (size_t)pc), oS = st.put(12 * (size_t)pc), oT = st.put(8 * (size_t)pc);
-    const size_t oL = st.put(4 * (size_t)pc), oMD = st.put(32 * (size_t)pc), oI = st.put(4 * (size_t)pc);
-    const size_t oDi = st.put(4 * (size_t)pc), oN = st.put(16);
-    if (st.alloc()) return PLVI_E_HIP;
-    const int counts[2] = {n_kp, n_pt};
-    if (st.up(oK, kps, sizeof(plvi_keypoint) * kc) | st.up(oD, desc, 32 * (size_t)kc) |
-        st.up(oU, uright, 4 * (size_t)kc) | st.up(oF, flags, n_pt) | st.up(oX, x3dc, 12 * (size_t)n_pt) |
-        st.up(oS, dist, 12 * (size_t)n_pt) | st.up(oT, dot, 8 * (size_t)n_pt) | st.up(oL, level, 4 * (size_t)n_pt) |
-        st.up(oMD, mp_desc, 32 * (size_t)n_pt) | st.up(oN, counts, sizeof counts))
-        return PLVI_E_HIP;
-    int* dN = st.at<int>(oN);
+    const auto K = st.in(kps, kc);
+    const auto D = st.in(desc, kc, 32), F = st.in(flags, pc), MD = st.in(mp_desc, pc, 32);
+    const auto U = st.in(uright, kc), X = st.in(x3dc, pc, 3), S = st.in(dist, pc, 3);
+    const auto T = st.in(dot, pc);
+    const auto CO = st.scratch<int>(kGridCells + 1), CI = st.scratch<int>(kc), L = st.in(level, pc);
+    const auto I = st.out(fuse_idx, pc), Di = st.out(fuse_dist, pc), N = st.inout(counts, 3);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
     const plvi_grid_params gp{p->min_x, p->min_y, p->inv_w, p->inv_h};
-    if (int rc = plvi_assign_grid_batch(st.at<plvi_keypoint>(oK), dN, kc, 1, &gp, st.at<int>(oCO), st.at<int>(oCI),
-                                        nullptr))
+    if (int rc = plvi_assign_grid_batch(st.dev(K), dN, kc, 1, &gp, st.dev(CO), st.dev(CI), nullptr)) return rc;
+    if (int rc = plvi_fuse_points_batch(1, p, st.dev(K), st.dev(D), dN, kc, st.dev(U), st.dev(CO), st.dev(CI),
+                                        st.dev(F), st.dev(X), st.dev(S), st.dev(T), st.dev(L), st.dev(MD), dN + 1, pc,
+                                        st.dev(I), st.dev(Di), dN + 2, nullptr))
         return rc;
-    if (int rc = plvi_fuse_points_batch(1, p, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, kc,
-                                        uright ? st.at<float>(oU) : nullptr, st.at<int>(oCO), st.at<int>(oCI),
-                                        st.at<uint8_t>(oF), st.at<float>(oX), st.at<float>(oS), st.at<double>(oT),
-                                        st.at<int>(oL), st.at<uint8_t>(oMD), dN + 1, pc, st.at<int>(oI),
-                                        st.at<int>(oDi), dN + 2, nullptr))
-        return rc;
-    return st.finish(dN + 2, fuse_idx, oI, n_pt, fuse_dist, oDi, n_pt);
+    if (int rc = st.fetch()) return rc;
+    return counts[2];
 }
 
 extern "C" int plvi_fuse_lines(const plvi_fuse_line_params* p, const plvi_keyline* kl, const uint8_t* kl_desc,
@@ -330,23 +323,19 @@ extern "C" int plvi_fuse_lines(const plvi_fuse_line_params* p, const plvi_keylin
         return 0;
     }
     const int kc = n_kl, pc = n_ml;
+    int counts[3] = {n_kl, n_ml, 0};  // [2]: nfused
     HostStage st;
-    const size_t oK = st.put(sizeof(plvi_keyline) * kc), oD = st.put(32 * (size_t)kc), oF = st.put(pc);
-    const size_t oA = st.put(12 * (size_t)pc), oB = st.put(12 * (size_t)pc), oS = st.put(12 * (size_t)pc);
-    const size_t oT = st.put(8 * (size_t)pc), oL = st.put(4 * (size_t)pc), oMD = st.put(32 * (size_t)pc);
-    const size_t oI = st.put(4 * (size_t)pc), oDi = st.put(4 * (size_t)pc), oN = st.put(16);
-    if (st.alloc()) return PLVI_E_HIP;
-    const int counts[2] = {n_kl, n_ml};
-    if (st.up(oK, kl, sizeof(plvi_keyline) * kc) | st.up(oD, kl_desc, 32 * (size_t)kc) | st.up(oF, flags, n_ml) |
-        st.up(oA, spc, 12 * (size_t)n_ml) | st.up(oB, epc, 12 * (size_t)n_ml) | st.up(oS, dist, 12 * (size_t)n_ml) |
-        st.up(oT, dot, 8 * (size_t)n_ml) | st.up(oL, level, 4 * (size_t)n_ml) |
-        st.up(oMD, ml_desc, 32 * (size_t)n_ml) | st.up(oN, counts, sizeof counts))
-        return PLVI_E_HIP;
-    int* dN = st.at<int>(oN);
-    if (int rc = plvi_fuse_lines_batch(1, p, st.at<plvi_keyline>(oK), st.at<uint8_t>(oD), dN, kc, st.at<uint8_t>(oF),
-                                       st.at<float>(oA), st.at<float>(oB), st.at<float>(oS), st.at<double>(oT),
-                                       st.at<int>(oL), st.at<uint8_t>(oMD), dN + 1, pc, st.at<int>(oI),
-                                       st.at<int>(oDi), dN + 2, nullptr))
+    const auto K = st.in(kl, kc);
+    const auto D = st.in(kl_desc, kc, 32), F = st.in(flags, pc), MD = st.in(ml_desc, pc, 32);
+    const auto A = st.in(spc, pc, 3), B = st.in(epc, pc, 3), S = st.in(dist, pc, 3);
+    const auto T = st.in(dot, pc);
+    const auto L = st.in(level, pc), I = st.out(fuse_idx, pc), Di = st.out(fuse_dist, pc), N = st.inout(counts, 3);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = plvi_fuse_lines_batch(1, p, st.dev(K), st.dev(D), dN, kc, st.dev(F), st.dev(A), st.dev(B), st.dev(S),
+                                       st.dev(T), st.dev(L), st.dev(MD), dN + 1, pc, st.dev(I), st.dev(Di), dN + 2,
+                                       nullptr))
         return rc;
-    return st.finish(dN + 2, fuse_idx, oI, n_ml, fuse_dist, oDi, n_ml);
+    if (int rc = st.fetch()) return rc;
+    return counts[2];
 }

@@ -312,29 +312,21 @@ extern "C" int plvi_line_search_projection(const plvi_line_proj_params* p, const
     if (n_cur == 0) return 0;
     const int ncell = p->grid_cols * p->grid_rows;
     const int nidx = std::max(cell_off[ncell], 1), lc = std::max(n_last, 1);
+    int counts[4] = {n_cur, n_last, 0, 0};  // [2]: nmatches, [3]: the kernel's error flags
     HostStage st;
-    const size_t oA = st.put(4 * (size_t)n_cur), oD = st.put(32 * (size_t)n_cur), oB = st.put(n_cur);
-    const size_t oCO = st.put(4 * (size_t)(ncell + 1)), oCI = st.put(4 * (size_t)nidx), oF = st.put(lc);
-    const size_t oX = st.put(24 * (size_t)lc), oO = st.put(4 * (size_t)lc), oMD = st.put(32 * (size_t)lc);
-    const size_t oM = st.put(4 * (size_t)n_cur), oN = st.put(32);
-    if (st.alloc()) return PLVI_E_HIP;
-    const int counts[4] = {n_cur, n_last, 0, 0};  // [3]: the kernel's error flags
-    if (st.up(oA, cur_angle, 4 * (size_t)n_cur) | st.up(oD, cur_desc, 32 * (size_t)n_cur) |
-        st.up(oCO, cell_off, 4 * (size_t)(ncell + 1)) | st.up(oCI, cell_idx, 4 * (size_t)cell_off[ncell]) |
-        st.up_or_zero(oB, cur_blocked, n_cur) | st.up(oF, last_flags, n_last) | st.up(oX, x3dc, 24 * (size_t)n_last) |
-        st.up(oO, last_octave, 4 * (size_t)n_last) | st.up(oMD, ml_desc, 32 * (size_t)n_last) |
-        st.up(oN, counts, sizeof counts))
-        return PLVI_E_HIP;
-    int* dN = st.at<int>(oN);
-    if (int rc = plvi_line_search_projection_batch(1, p, st.at<float>(oA), st.at<uint8_t>(oD), st.at<uint8_t>(oB), dN,
-                                                   n_cur, st.at<int>(oCO), st.at<int>(oCI), nidx, st.at<uint8_t>(oF),
-                                                   st.at<float>(oX), st.at<int>(oO), st.at<uint8_t>(oMD), dN + 1, lc,
-                                                   st.at<int>(oM), dN + 2, dN + 3, nullptr))
+    const auto A = st.in(cur_angle, n_cur), X = st.in_or_zero(x3dc, n_last, 6);
+    const auto D = st.in(cur_desc, n_cur, 32), B = st.in_or_zero(cur_blocked, n_cur);
+    const auto F = st.in_or_zero(last_flags, n_last), MD = st.in_or_zero(ml_desc, n_last, 32);
+    const auto CO = st.in(cell_off, ncell + 1), CI = st.in_or_zero(cell_idx, std::max(cell_off[ncell], 0), 1, nidx);
+    const auto O = st.in_or_zero(last_octave, n_last), M = st.out(match, n_cur), N = st.inout(counts, 4);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = plvi_line_search_projection_batch(1, p, st.dev(A), st.dev(D), st.dev(B), dN, n_cur, st.dev(CO),
+                                                   st.dev(CI), nidx, st.dev(F), st.dev(X), st.dev(O), st.dev(MD),
+                                                   dN + 1, lc, st.dev(M), dN + 2, dN + 3, nullptr))
         return rc;
-    const int nm = st.finish(dN + 2, match, oM, n_cur);
-    int err = 0;
-    if (nm >= 0) PLVI_CHECK(hipMemcpy(&err, dN + 3, 4, hipMemcpyDeviceToHost));
-    return err ? PLVI_E_CAPACITY : nm;
+    if (int rc = st.fetch()) return rc;
+    return counts[3] ? PLVI_E_CAPACITY : counts[2];
 }
 
 extern "C" int plvi_line_match_grid_batch(int n_pairs, const int* d_lines1, const uint8_t* d_desc1, const int* d_n1,
@@ -364,40 +356,18 @@ extern "C" int plvi_line_match_grid(const int* lines1, const uint8_t* desc1, int
     const int ncell = grid_cols * grid_rows;
     const int nidx = std::max(cell_off[ncell], 1);
     const int cap2 = std::max(n2, 1);
-    // [desc1 | desc2 | dirs2 (f64) | ints: lines1, cell_off, cell_idx, n1, n2, out, nm, err]
-    const size_t bD1 = (size_t)n1 * 32, bD2 = (size_t)cap2 * 32, bV = (size_t)cap2 * 16;
-    const size_t oV = (bD1 + bD2 + 15) / 16 * 16, oI = oV + bV;
-    const size_t nInts = (size_t)n1 * 4 + (ncell + 1) + nidx + 2 + n1 + 2;
-    DevBuf d;
-    if (d.alloc(oI + nInts * 4)) return PLVI_E_HIP;
-    uint8_t* base = d.as<uint8_t>();
-    int* I = reinterpret_cast<int*>(base + oI);
-    int* dL1 = I;
-    int* dCO = dL1 + 4 * n1;
-    int* dCI = dCO + ncell + 1;
-    int* dN = dCI + nidx;
-    int* dOut = dN + 2;
-    int* dNm = dOut + n1;
-    int* dErr = dNm + 1;
-    const int counts[2] = {n1, n2};
-    PLVI_CHECK(hipMemcpy(base, desc1, bD1, hipMemcpyHostToDevice));
-    if (n2) {
-        PLVI_CHECK(hipMemcpy(base + bD1, desc2, (size_t)n2 * 32, hipMemcpyHostToDevice));
-        PLVI_CHECK(hipMemcpy(base + oV, directions2, (size_t)n2 * 16, hipMemcpyHostToDevice));
-    }
-    PLVI_CHECK(hipMemcpy(dL1, lines1, (size_t)n1 * 16, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(dCO, cell_off, (size_t)(ncell + 1) * 4, hipMemcpyHostToDevice));
-    if (cell_off[ncell] > 0) PLVI_CHECK(hipMemcpy(dCI, cell_idx, (size_t)cell_off[ncell] * 4, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(dN, counts, 8, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemset(dErr, 0, 4));
-    int rc = plvi_line_match_grid_batch(1, dL1, base, dN, n1, grid_cols, grid_rows, dCO, dCI, nidx, base + bD1,
-                                        reinterpret_cast<const double*>(base + oV), dN + 1, cap2, win_w0, win_w1,
-                                        win_h0, win_h1, libstdcxx_range_hint, dOut, dNm, dErr, nullptr);
-    if (rc) return rc;
-    int nm = 0, er = 0;
-    PLVI_CHECK(hipMemcpy(matches_12, dOut, (size_t)n1 * 4, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(&nm, dNm, 4, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(&er, dErr, 4, hipMemcpyDeviceToHost));
-    if (er) return PLVI_E_CAPACITY;
-    return nm;
+    int counts[4] = {n1, n2, 0, 0};  // [2]: nmatches, [3]: the kernel's error flags
+    HostStage st;
+    const auto D1 = st.in_or_zero(desc1, n1, 32), D2 = st.in_or_zero(desc2, n2, 32);
+    const auto V2 = st.in_or_zero(directions2, n2, 2);
+    const auto CO = st.in(cell_off, ncell + 1), CI = st.in_or_zero(cell_idx, std::max(cell_off[ncell], 0), 1, nidx);
+    const auto L1 = st.in_or_zero(lines1, n1, 4), M = st.out_or_scratch(matches_12, n1), N = st.inout(counts, 4);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = plvi_line_match_grid_batch(1, st.dev(L1), st.dev(D1), dN, n1, grid_cols, grid_rows, st.dev(CO),
+                                            st.dev(CI), nidx, st.dev(D2), st.dev(V2), dN + 1, cap2, win_w0, win_w1,
+                                            win_h0, win_h1, libstdcxx_range_hint, st.dev(M), dN + 2, dN + 3, nullptr))
+        return rc;
+    if (int rc = st.fetch()) return rc;
+    return counts[3] ? PLVI_E_CAPACITY : counts[2];
 }

@@ -743,15 +743,12 @@ extern "C" int plvi_kfdb_add(plvi_kf_database* h, int slot, int map_id, const un
     if (slot < 0 || slot >= h->slot_cap || h->occupied[slot]) return PLVI_E_BADARG;
     PLVI_CHECK(hipSetDevice(h->device));
     HostStage hs;
-    const size_t iw = hs.put(4 * (size_t)n + 4), iv = hs.put(8 * (size_t)n + 8), in = hs.put(4);
-    if (int rc = hs.alloc()) return rc;
-    if (int rc = hs.up(iw, word, 4 * (size_t)n)) return rc;
-    if (int rc = hs.up(iv, value, 8 * (size_t)n)) return rc;
-    if (int rc = hs.up(in, &n, 4)) return rc;
+    const auto W = hs.in_or_zero(word, n);
+    const auto V = hs.in_or_zero(value, n);
+    const auto N = hs.in(&n, 1);
+    if (int rc = hs.commit()) return rc;
     const int entry[3] = {0, slot, map_id};
-    if (int rc = plvi_kfdb_add_batch(h, 1, entry, hs.at<unsigned>(iw), hs.at<double>(iv), hs.at<int>(in), n > 0 ? n : 1,
-                                     nullptr))
-        return rc;
+    if (int rc = plvi_kfdb_add_batch(h, 1, entry, hs.dev(W), hs.dev(V), hs.dev(N), n > 0 ? n : 1, nullptr)) return rc;
     return plvi_kfdb_errors(h, nullptr, nullptr);
 }
 
@@ -870,40 +867,31 @@ extern "C" int plvi_kfdb_query(plvi_kf_database* h, const unsigned* q_word, cons
     if (q_n > PLVI_KFDB_MAX_WORDS) return PLVI_E_CAPACITY;
     PLVI_CHECK(hipSetDevice(h->device));
     const int q_cap = q_n > 0 ? q_n : 1, nb = n_best > 0 ? n_best : 1, cc = cand_cap > 0 ? cand_cap : 1;
-    const int conn_off[2] = {0, n_conn};
+    // q_n, q_map, conn_off[2]; then the counts that come back: ncand, nloop, nmerge
+    int c[7] = {q_n, q_map, 0, n_conn, 0, 0, 0};
     HostStage hs;
-    const size_t iw = hs.put(4 * (size_t)q_cap), iv = hs.put(8 * (size_t)q_cap), in = hs.put(4), im = hs.put(4),
-                 ico = hs.put(8), ics = hs.put(4 * (size_t)n_conn + 4),
-                 icv = hs.put(covis ? 4 * (size_t)h->slot_cap * kNeigh : 4), ib = hs.put((size_t)n_maps + 4),
-                 oc = hs.put(4 * (size_t)cc), onc = hs.put(4), ol = hs.put(4 * (size_t)nb), onl = hs.put(4),
-                 om = hs.put(4 * (size_t)nb), onm = hs.put(4);
-    if (int rc = hs.alloc(true)) return rc;
-    if (int rc = hs.up(iw, q_word, 4 * (size_t)q_n)) return rc;
-    if (int rc = hs.up(iv, q_value, 8 * (size_t)q_n)) return rc;
-    if (int rc = hs.up(in, &q_n, 4)) return rc;
-    if (int rc = hs.up(im, &q_map, 4)) return rc;
-    if (int rc = hs.up(ico, conn_off, 8)) return rc;
-    if (int rc = hs.up(ics, conn, 4 * (size_t)n_conn)) return rc;
-    if (int rc = hs.up(icv, covis, 4 * (size_t)h->slot_cap * kNeigh)) return rc;
-    if (int rc = hs.up(ib, map_bad, (size_t)n_maps)) return rc;
-    if (int rc = plvi_kfdb_query_batch(h, 1, hs.at<unsigned>(iw), hs.at<double>(iv), hs.at<int>(in), q_cap,
-                                       hs.at<int>(im), mode, n_best, hs.at<int>(ico), hs.at<int>(ics),
-                                       covis ? hs.at<int>(icv) : nullptr, map_bad ? hs.at<uint8_t>(ib) : nullptr,
-                                       n_maps, nullptr, nullptr, nullptr, nullptr, hs.at<int>(oc), cand_cap,
-                                       hs.at<int>(onc), hs.at<int>(ol), hs.at<int>(onl), hs.at<int>(om),
-                                       hs.at<int>(onm), nullptr))
+    const auto W = hs.in_or_zero(q_word, q_n);
+    const auto V = hs.in_or_zero(q_value, q_n);
+    const auto Bad = hs.in(map_bad, n_maps);
+    const auto Conn = hs.in_or_zero(conn, n_conn), Cov = hs.in(covis, h->slot_cap, kNeigh), C = hs.inout(c, 7);
+    const auto Cand = hs.out_or_scratch(mode == 0 ? cand : nullptr, cc);
+    const auto Loop = hs.out_or_scratch(mode == 1 ? loop : nullptr, nb);
+    const auto Merge = hs.out_or_scratch(mode == 1 ? merge : nullptr, nb);
+    if (int rc = hs.commit()) return rc;
+    int* dC = hs.dev(C);
+    if (int rc = plvi_kfdb_query_batch(h, 1, hs.dev(W), hs.dev(V), dC, q_cap, dC + 1, mode, n_best, dC + 2,
+                                       hs.dev(Conn), hs.dev(Cov), hs.dev(Bad), n_maps, nullptr, nullptr, nullptr,
+                                       nullptr, hs.dev(Cand), cand_cap, dC + 4, hs.dev(Loop), dC + 5, hs.dev(Merge),
+                                       dC + 6, nullptr))
         return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    if (mode == 0) {
-        int n = 0;
-        PLVI_CHECK(hipMemcpy(&n, hs.at<void>(onc), 4, hipMemcpyDeviceToHost));
-        const int w = n < cand_cap ? n : cand_cap;
-        if (w > 0) PLVI_CHECK(hipMemcpy(cand, hs.at<void>(oc), 4 * (size_t)w, hipMemcpyDeviceToHost));
-        return n;
-    }
-    PLVI_CHECK(hipMemcpy(n_loop, hs.at<void>(onl), 4, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(n_merge, hs.at<void>(onm), 4, hipMemcpyDeviceToHost));
-    if (*n_loop > 0) PLVI_CHECK(hipMemcpy(loop, hs.at<void>(ol), 4 * (size_t)*n_loop, hipMemcpyDeviceToHost));
-    if (*n_merge > 0) PLVI_CHECK(hipMemcpy(merge, hs.at<void>(om), 4 * (size_t)*n_merge, hipMemcpyDeviceToHost));
-    return *n_loop + *n_merge;
+    // counts first: the lists come back up to them
+    if (int rc = hs.fetch_one(C)) return rc;
+    hs.trim(Cand, std::min(c[4], cand_cap));
+    hs.trim(Loop, c[5]);
+    hs.trim(Merge, c[6]);
+    if (int rc = hs.fetch()) return rc;
+    if (mode == 0) return c[4];
+    *n_loop = c[5];
+    *n_merge = c[6];
+    return c[5] + c[6];
 }

@@ -27,8 +27,8 @@
 #include <climits>
 #include <cstring>
 
-#include "host_stage.h"
 #include "kf_vote.h"
+#include "map_pool.h"
 #include "plvi_common.h"
 
 namespace plvi {
@@ -370,8 +370,6 @@ __global__ __launch_bounds__(kListThreads) void lm_write_kernel(LmArgs a) {
     }
 }
 
-static size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
-
 // the scratch block: [first tables | cleared tables | uncleared tables]
 struct LmLayout {
     size_t first[2], first_bytes;                  // filled with 0x7f
@@ -423,10 +421,6 @@ using namespace plvi;
 extern "C" size_t plvi_local_map_scratch_bytes(int n_frames, int kf_cap, int mp_n, int ml_n) {
     if (n_frames < 0 || kf_cap < 0 || mp_n < 0 || ml_n < 0) return 0;
     return lm_layout(n_frames, kf_cap, mp_n, ml_n).total;
-}
-
-static bool pool_ok(const plvi_local_map_pool* p) {
-    return p->n >= 0 && (p->n == 0 || (p->bad && p->obs_off && p->obs_kf));
 }
 
 // The argument checks of both forms, made before any table is read (the host form reads
@@ -564,144 +558,81 @@ extern "C" int plvi_local_map(const plvi_local_map_keyframes* kf, const plvi_loc
     if (int rc = lm_validate(1, kf, mp, ml, fr, out)) return rc;
     const bool with_lines = kf->ml != nullptr;
     const size_t K = (size_t)kf->kf_cap;
+    const size_t n_child = kf->child_off && K && kf->child_off[K] > 0 ? (size_t)kf->child_off[K] : 0;
+    // copies of the caller's structs: commit() turns their host pointers into device pointers
     plvi_local_map_keyframes dk = *kf;
-    plvi_local_map_pool dp[2] = {*mp, ml ? *ml : *mp};
+    plvi_local_map_pool dmp = *mp, dml = ml ? *ml : plvi_local_map_pool{};
     plvi_local_map_frames df = *fr;
     plvi_local_map_outputs dout = *out;
     HostStage hs;
-    struct Copy {
-        size_t slot;
-        const void* src;
-        void* back;
-        size_t bytes;
-    };
-    std::vector<Copy> cp;
-    // in: upload; back: download after the call (bytes fixed up once the counts are known)
-    auto stage = [&](const void* src, size_t bytes, void* back = nullptr) {
-        cp.push_back({hs.put(bytes + 4), src, back, bytes});
-        return cp.size() - 1;
-    };
-    const size_t none = (size_t)-1;
-    auto in = [&](const void* src, size_t bytes) { return src ? stage(src, bytes) : none; };
-    auto ob = [&](void* dst, size_t bytes) { return dst ? stage(nullptr, bytes, dst) : none; };
-    const size_t n_child = kf->child_off && K ? (size_t)(kf->child_off[K] > 0 ? kf->child_off[K] : 0) : 0;
-    const size_t i_bad = in(kf->bad, K), i_ord = in(kf->order, 4 * (size_t)kf->n_order), i_cov = in(kf->covis, 40 * K),
-                 i_co = in(kf->child_off, 4 * (K + 1)), i_ch = in(kf->child, 4 * n_child), i_par = in(kf->parent, 4 * K),
-                 i_prev = in(kf->prev_kf, 4 * K), i_kmp = in(kf->mp, 4 * K * kf->kp_cap), i_nmp = in(kf->nmp, 4 * K),
-                 i_kml = in(kf->ml, 4 * K * kf->kl_cap), i_nml = in(kf->nml, 4 * K);
-    size_t i_p[2][7];
-    for (int k = 0; k < 2; ++k) {
-        const plvi_local_map_pool& p = dp[k];
-        const bool on = k == 0 || ml;
-        const size_t n = (size_t)p.n;
-        const size_t n_obs = on && p.obs_off && n ? (size_t)(p.obs_off[n] > 0 ? p.obs_off[n] : 0) : 0;
-        i_p[k][0] = on ? in(p.bad, n) : none;
-        i_p[k][1] = on ? in(p.obs_off, 4 * (n + 1)) : none;
-        i_p[k][2] = on ? in(p.obs_kf, 4 * n_obs) : none;
-        i_p[k][3] = on ? (k ? in(p.sep, 48 * n) : in(p.pos, 12 * n)) : none;
-        i_p[k][4] = on ? in(p.normal, 12 * n) : none;
-        i_p[k][5] = on ? in(p.dist, 8 * n) : none;
-        i_p[k][6] = on ? in(p.desc, 32 * n) : none;
-    }
-    // the vote tables are in/out
-    const size_t i_vmp = fr->vote_mp ? stage(fr->vote_mp, 4 * (size_t)fr->vote_mp_cap, fr->vote_mp) : none,
-                 i_nvmp = in(fr->n_vote_mp, 4),
-                 i_vml = fr->vote_ml ? stage(fr->vote_ml, 4 * (size_t)fr->vote_ml_cap, fr->vote_ml) : none,
-                 i_nvml = in(fr->n_vote_ml, 4), i_smp = in(fr->seen_mp, 4 * (size_t)fr->seen_mp_cap),
-                 i_nsmp = in(fr->n_seen_mp, 4), i_sml = in(fr->seen_ml, 4 * (size_t)fr->seen_ml_cap),
-                 i_nsml = in(fr->n_seen_ml, 4), i_last = in(fr->last_kf, 4);
+    const HostStage::Dir In = HostStage::In, InOut = HostStage::InOut, Out = HostStage::Out;
+    hs.field(dk.bad, In, K);
+    hs.field(dk.order, In, kf->n_order);
+    hs.field(dk.covis, In, K, PLVI_KFDB_NEIGHBOURS);
+    hs.field(dk.child_off, In, K + 1);
+    hs.field(dk.child, In, n_child);
+    hs.field(dk.parent, In, K);
+    hs.field(dk.prev_kf, In, K);
+    hs.field(dk.mp, In, K, kf->kp_cap);
+    hs.field(dk.nmp, In, K);
+    hs.field(dk.ml, In, K, kf->kl_cap);
+    hs.field(dk.nml, In, K);
+    stage_pool(hs, dmp, kPoolPoints);
+    if (ml) stage_pool(hs, dml, kPoolLines);
+    hs.field(df.vote_mp, InOut, fr->vote_mp_cap);  // the vote tables are in/out
+    hs.field(df.n_vote_mp, In, 1);
+    hs.field(df.vote_ml, InOut, fr->vote_ml_cap);
+    hs.field(df.n_vote_ml, In, 1);
+    hs.field(df.seen_mp, In, fr->seen_mp_cap);
+    hs.field(df.n_seen_mp, In, 1);
+    hs.field(df.seen_ml, In, fr->seen_ml_cap);
+    hs.field(df.n_seen_ml, In, 1);
+    hs.field(df.last_kf, In, 1);
     const size_t ckf = (size_t)out->lkf_cap, cmp = (size_t)out->lmp_cap, cml = (size_t)out->lml_cap;
-    const size_t o_lkf = ob(out->local_kf, 4 * ckf), o_nkf = ob(out->n_local_kf, 4), o_ref = ob(out->ref_kf, 4),
-                 o_lmp = ob(out->local_mp, 4 * cmp), o_nmp = ob(out->n_local_mp, 4), o_lml = ob(out->local_ml, 4 * cml),
-                 o_nml = ob(out->n_local_ml, 4), o_ppos = ob(out->mp_pos, 12 * cmp), o_pnor = ob(out->mp_normal, 12 * cmp),
-                 o_pdis = ob(out->mp_dist, 8 * cmp), o_pfl = ob(out->mp_in_flags, cmp), o_pde = ob(out->mp_desc, 32 * cmp),
-                 o_lsep = ob(out->ml_sep, 48 * cml), o_lnor = ob(out->ml_normal, 12 * cml),
-                 o_ldis = ob(out->ml_dist, 8 * cml), o_lfl = ob(out->ml_in_flags, cml), o_lde = ob(out->ml_desc, 32 * cml),
-                 o_err = ob(out->err, 4);
+    const auto lkf = hs.field(dout.local_kf, Out, ckf);
+    const auto nkf = hs.field(dout.n_local_kf, Out, 1);
+    const auto lmp = hs.field(dout.local_mp, Out, cmp);
+    const auto nmp = hs.field(dout.n_local_mp, Out, 1);
+    const auto lml = hs.field(dout.local_ml, Out, cml);
+    const auto nml = hs.field(dout.n_local_ml, Out, 1);
+    const auto ppos = hs.field(dout.mp_pos, Out, cmp, 3);
+    const auto pnor = hs.field(dout.mp_normal, Out, cmp, 3);
+    const auto pdis = hs.field(dout.mp_dist, Out, cmp, 2);
+    const auto pfl = hs.field(dout.mp_in_flags, Out, cmp);
+    const auto pde = hs.field(dout.mp_desc, Out, cmp, 32);
+    const auto lsep = hs.field(dout.ml_sep, Out, cml, 6);
+    const auto lnor = hs.field(dout.ml_normal, Out, cml, 3);
+    const auto ldis = hs.field(dout.ml_dist, Out, cml, 2);
+    const auto lfl = hs.field(dout.ml_in_flags, Out, cml);
+    const auto lde = hs.field(dout.ml_desc, Out, cml, 32);
+    hs.field(dout.ref_kf, Out, 1);
+    const auto err = hs.field(dout.err, Out, 1);
     const size_t sb = plvi_local_map_scratch_bytes(1, kf->kf_cap, mp->n, ml ? ml->n : 0);
-    const size_t i_scr = hs.put(sb);
-    if (int rc = hs.alloc()) return rc;
-    for (const Copy& c : cp)
-        if (int rc = hs.up(c.slot, c.src, c.bytes)) return rc;
-    auto dev = [&](size_t i) -> void* { return i == none ? nullptr : hs.at<void>(cp[i].slot); };
-    dk.bad = (const uint8_t*)dev(i_bad);
-    dk.order = (const int*)dev(i_ord);
-    dk.covis = (const int*)dev(i_cov);
-    dk.child_off = (const int*)dev(i_co);
-    dk.child = (const int*)dev(i_ch);
-    dk.parent = (const int*)dev(i_par);
-    dk.prev_kf = (const int*)dev(i_prev);
-    dk.mp = (const int*)dev(i_kmp);
-    dk.nmp = (const int*)dev(i_nmp);
-    dk.ml = (const int*)dev(i_kml);
-    dk.nml = (const int*)dev(i_nml);
-    for (int k = 0; k < 2; ++k) {
-        dp[k].bad = (const uint8_t*)dev(i_p[k][0]);
-        dp[k].obs_off = (const int*)dev(i_p[k][1]);
-        dp[k].obs_kf = (const int*)dev(i_p[k][2]);
-        dp[k].pos = k ? nullptr : (const float*)dev(i_p[k][3]);
-        dp[k].sep = k ? (const double*)dev(i_p[k][3]) : nullptr;
-        dp[k].normal = (const float*)dev(i_p[k][4]);
-        dp[k].dist = (const float*)dev(i_p[k][5]);
-        dp[k].desc = (const uint8_t*)dev(i_p[k][6]);
-    }
-    df.vote_mp = (int*)dev(i_vmp);
-    df.n_vote_mp = (const int*)dev(i_nvmp);
-    df.vote_ml = (int*)dev(i_vml);
-    df.n_vote_ml = (const int*)dev(i_nvml);
-    df.seen_mp = (const int*)dev(i_smp);
-    df.n_seen_mp = (const int*)dev(i_nsmp);
-    df.seen_ml = (const int*)dev(i_sml);
-    df.n_seen_ml = (const int*)dev(i_nsml);
-    df.last_kf = (const int*)dev(i_last);
-    dout.local_kf = (int*)dev(o_lkf);
-    dout.n_local_kf = (int*)dev(o_nkf);
-    dout.ref_kf = (int*)dev(o_ref);
-    dout.local_mp = (int*)dev(o_lmp);
-    dout.n_local_mp = (int*)dev(o_nmp);
-    dout.local_ml = (int*)dev(o_lml);
-    dout.n_local_ml = (int*)dev(o_nml);
-    dout.mp_pos = (float*)dev(o_ppos);
-    dout.mp_normal = (float*)dev(o_pnor);
-    dout.mp_dist = (float*)dev(o_pdis);
-    dout.mp_in_flags = (uint8_t*)dev(o_pfl);
-    dout.mp_desc = (uint8_t*)dev(o_pde);
-    dout.ml_sep = (double*)dev(o_lsep);
-    dout.ml_normal = (float*)dev(o_lnor);
-    dout.ml_dist = (float*)dev(o_ldis);
-    dout.ml_in_flags = (uint8_t*)dev(o_lfl);
-    dout.ml_desc = (uint8_t*)dev(o_lde);
-    dout.err = (int*)dev(o_err);
-    if (int rc = plvi_local_map_batch(1, &dk, &dp[0], ml ? &dp[1] : nullptr, &df, &dout, hs.at<void>(i_scr), sb, nullptr))
+    const auto scr = hs.scratch<uint8_t>(sb);
+    if (int rc = hs.commit()) return rc;
+    if (int rc = plvi_local_map_batch(1, &dk, &dmp, ml ? &dml : nullptr, &df, &dout, hs.dev(scr), sb, nullptr))
         return rc;
-    PLVI_CHECK(hipDeviceSynchronize());
-    // counts first: list and gathered rows come back up to min(count, capacity)
-    int nkf = 0, nmp = 0, nml = 0, err = 0;
-    PLVI_CHECK(hipMemcpy(&nkf, dout.n_local_kf, 4, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(&nmp, dout.n_local_mp, 4, hipMemcpyDeviceToHost));
-    if (with_lines) PLVI_CHECK(hipMemcpy(&nml, dout.n_local_ml, 4, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(&err, dout.err, 4, hipMemcpyDeviceToHost));
-    const size_t wkf = (size_t)(nkf < out->lkf_cap ? nkf : out->lkf_cap), wmp = (size_t)(nmp < out->lmp_cap ? nmp : out->lmp_cap),
-                 wml = (size_t)(nml < out->lml_cap ? nml : out->lml_cap);
-    auto rows = [&](size_t i, size_t bytes) {
-        if (i != none) cp[i].bytes = bytes;
-    };
-    rows(o_lkf, 4 * wkf);
-    rows(o_lmp, 4 * wmp);
-    rows(o_ppos, 12 * wmp);
-    rows(o_pnor, 12 * wmp);
-    rows(o_pdis, 8 * wmp);
-    rows(o_pfl, wmp);
-    rows(o_pde, 32 * wmp);
-    rows(o_lml, 4 * wml);
-    rows(o_lsep, 48 * wml);
-    rows(o_lnor, 12 * wml);
-    rows(o_ldis, 8 * wml);
-    rows(o_lfl, wml);
-    rows(o_lde, 32 * wml);
-    if (!with_lines) rows(o_nml, 0);
-    for (const Copy& c : cp)
-        if (c.back && c.bytes)
-            PLVI_CHECK(hipMemcpy(c.back, hs.at<void>(c.slot), c.bytes, hipMemcpyDeviceToHost));
-    return err ? PLVI_E_CAPACITY : PLVI_OK;
+    // counts first: list and gathered rows come back up to min(count, capacity);
+    // n_local_ml is not written without lines
+    if (!with_lines) hs.trim(nml, 0);
+    for (const Staged<int> count : {nkf, nmp, nml, err})
+        if (int rc = hs.fetch_one(count)) return rc;
+    const size_t wkf = (size_t)std::min(*out->n_local_kf, out->lkf_cap);
+    const size_t wmp = (size_t)std::min(*out->n_local_mp, out->lmp_cap);
+    const size_t wml = with_lines ? (size_t)std::min(*out->n_local_ml, out->lml_cap) : 0;
+    hs.trim(lkf, wkf);
+    hs.trim(lmp, wmp);
+    hs.trim(ppos, wmp, 3);
+    hs.trim(pnor, wmp, 3);
+    hs.trim(pdis, wmp, 2);
+    hs.trim(pfl, wmp);
+    hs.trim(pde, wmp, 32);
+    hs.trim(lml, wml);
+    hs.trim(lsep, wml, 6);
+    hs.trim(lnor, wml, 3);
+    hs.trim(ldis, wml, 2);
+    hs.trim(lfl, wml);
+    hs.trim(lde, wml, 32);
+    if (int rc = hs.fetch()) return rc;
+    return *out->err ? PLVI_E_CAPACITY : PLVI_OK;
 }

@@ -819,14 +819,25 @@ extern "C" int plvi_assign_grid_batch(const plvi_keypoint* d_kps, const int* d_c
     return PLVI_OK;
 }
 
-// The grid of one staged image (keypoints in slot oK, count at d_n) into the
-// slots oCO / oCI, with the matcher's own image bounds.
+// One staged image: keypoints, descriptors, the blocked flags (NULL: none) and
+// the slots of its grid.
+struct StagedImage {
+    Staged<plvi_keypoint> k;
+    Staged<uint8_t> d, b;
+    Staged<int> co, ci;
+};
+
+static StagedImage stage_image(HostStage& st, const plvi_keypoint* kps, const uint8_t* desc, const uint8_t* blocked,
+                               int n, int cap) {
+    return {st.in_or_zero(kps, n), st.in_or_zero(desc, n, 32), st.in_or_zero(blocked, n),
+            st.scratch<int>(kGridCells + 1), st.scratch<int>(cap)};
+}
+
+// The grid of a staged image (count at d_n), with the matcher's own image bounds.
 template <class Params>
-static int stage_grid(const HostStage& st, const Params* p, size_t oK, const int* d_n, int cap, size_t oCO,
-                      size_t oCI) {
+static int stage_grid(const HostStage& st, const Params* p, const StagedImage& im, const int* d_n, int cap) {
     const plvi_grid_params gp{p->min_x, p->min_y, p->inv_w, p->inv_h};
-    return plvi_assign_grid_batch(st.at<const plvi_keypoint>(oK), d_n, cap, 1, &gp, st.at<int>(oCO), st.at<int>(oCI),
-                                  nullptr);
+    return plvi_assign_grid_batch(st.dev(im.k), d_n, cap, 1, &gp, st.dev(im.co), st.dev(im.ci), nullptr);
 }
 
 extern "C" int plvi_search_by_projection_batch(int n_pairs, const plvi_proj_params* p, const plvi_keypoint* d_cur_kps,
@@ -857,28 +868,21 @@ extern "C" int plvi_search_by_projection(const plvi_proj_params* p, const plvi_k
     if (!p || n_cur < 0 || n_last < 0 || (n_cur > 0 && (!cur_kps || !cur_desc || !match))) return PLVI_E_BADARG;
     if (n_cur == 0) return 0;
     const int cc = n_cur, lc = std::max(n_last, 1);
+    int counts[3] = {n_cur, n_last, 0};  // [2]: nmatches
     HostStage st;
-    const size_t oK = st.put(sizeof(plvi_keypoint) * cc), oD = st.put(32 * (size_t)cc), oB = st.put(cc);
-    const size_t oU = st.put(4 * (size_t)cc), oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)cc);
-    const size_t oX = st.put(12 * (size_t)lc), oLO = st.put(4 * (size_t)lc), oLA = st.put(4 * (size_t)lc);
-    const size_t oMD = st.put(32 * (size_t)lc), oLF = st.put(lc), oM = st.put(4 * (size_t)cc), oN = st.put(16);
-    if (st.alloc()) return PLVI_E_HIP;
-    const int counts[2] = {n_cur, n_last};
-    if (st.up(oK, cur_kps, sizeof(plvi_keypoint) * cc) | st.up(oD, cur_desc, 32 * (size_t)cc) |
-        st.up_or_zero(oB, cur_blocked, cc) | st.up(oU, cur_uright, 4 * (size_t)cc) |
-        st.up(oX, x3dc, 12 * (size_t)n_last) | st.up(oLO, last_octave, 4 * (size_t)n_last) |
-        st.up(oLA, last_angle, 4 * (size_t)n_last) | st.up(oMD, mp_desc, 32 * (size_t)n_last) |
-        st.up(oLF, last_flags, n_last) | st.up(oN, counts, sizeof counts))
-        return PLVI_E_HIP;
-    int* dN = st.at<int>(oN);
-    if (int rc = stage_grid(st, p, oK, dN, cc, oCO, oCI)) return rc;
-    if (int rc = plvi_search_by_projection_batch(
-            1, p, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, cc, st.at<uint8_t>(oB),
-            cur_uright ? st.at<float>(oU) : nullptr, st.at<int>(oCO), st.at<int>(oCI), st.at<float>(oX),
-            st.at<int>(oLO), st.at<float>(oLA), st.at<uint8_t>(oMD), st.at<uint8_t>(oLF), dN + 1, lc, st.at<int>(oM),
-            dN + 2, nullptr))
+    const StagedImage im = stage_image(st, cur_kps, cur_desc, cur_blocked, n_cur, cc);
+    const auto U = st.in(cur_uright, cc), X = st.in_or_zero(x3dc, n_last, 3), LA = st.in_or_zero(last_angle, n_last);
+    const auto MD = st.in_or_zero(mp_desc, n_last, 32), LF = st.in_or_zero(last_flags, n_last);
+    const auto LO = st.in_or_zero(last_octave, n_last), M = st.out(match, cc), N = st.inout(counts, 3);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = stage_grid(st, p, im, dN, cc)) return rc;
+    if (int rc = plvi_search_by_projection_batch(1, p, st.dev(im.k), st.dev(im.d), dN, cc, st.dev(im.b), st.dev(U),
+                                                 st.dev(im.co), st.dev(im.ci), st.dev(X), st.dev(LO), st.dev(LA),
+                                                 st.dev(MD), st.dev(LF), dN + 1, lc, st.dev(M), dN + 2, nullptr))
         return rc;
-    return st.finish(dN + 2, match, oM, n_cur);
+    if (int rc = st.fetch()) return rc;
+    return counts[2];
 }
 
 extern "C" int plvi_search_reloc_batch(int n_pairs, const plvi_reloc_params* p, const plvi_keypoint* d_cur_kps,
@@ -907,28 +911,21 @@ extern "C" int plvi_search_reloc(const plvi_reloc_params* p, const plvi_keypoint
     if (p->nlevels < 1 || p->nlevels > 16 || p->orb_dist < 0 || p->orb_dist > 255) return PLVI_E_BADARG;
     if (n_cur == 0) return 0;
     const int cc = n_cur, kc = std::max(n_kf, 1);
+    int counts[3] = {n_cur, n_kf, 0};  // [2]: nmatches
     HostStage st;
-    const size_t oK = st.put(sizeof(plvi_keypoint) * cc), oD = st.put(32 * (size_t)cc), oB = st.put(cc);
-    const size_t oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)cc), oF = st.put(kc);
-    const size_t oX = st.put(12 * (size_t)kc), oS = st.put(12 * (size_t)kc), oL = st.put(4 * (size_t)kc);
-    const size_t oA = st.put(4 * (size_t)kc), oMD = st.put(32 * (size_t)kc), oM = st.put(4 * (size_t)cc);
-    const size_t oN = st.put(16);
-    if (st.alloc()) return PLVI_E_HIP;
-    const int counts[2] = {n_cur, n_kf};
-    if (st.up(oK, cur_kps, sizeof(plvi_keypoint) * cc) | st.up(oD, cur_desc, 32 * (size_t)cc) |
-        st.up_or_zero(oB, cur_blocked, cc) | st.up(oF, kf_flags, n_kf) | st.up(oX, x3dc, 12 * (size_t)n_kf) |
-        st.up(oS, dist, 12 * (size_t)n_kf) | st.up(oL, level, 4 * (size_t)n_kf) |
-        st.up(oA, kf_angle, 4 * (size_t)n_kf) | st.up(oMD, mp_desc, 32 * (size_t)n_kf) |
-        st.up(oN, counts, sizeof counts))
-        return PLVI_E_HIP;
-    int* dN = st.at<int>(oN);
-    if (int rc = stage_grid(st, p, oK, dN, cc, oCO, oCI)) return rc;
-    if (int rc = plvi_search_reloc_batch(1, p, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, cc,
-                                         st.at<uint8_t>(oB), st.at<int>(oCO), st.at<int>(oCI), st.at<uint8_t>(oF),
-                                         st.at<float>(oX), st.at<float>(oS), st.at<int>(oL), st.at<float>(oA),
-                                         st.at<uint8_t>(oMD), dN + 1, kc, st.at<int>(oM), dN + 2, nullptr))
+    const StagedImage im = stage_image(st, cur_kps, cur_desc, cur_blocked, n_cur, cc);
+    const auto X = st.in_or_zero(x3dc, n_kf, 3), S = st.in_or_zero(dist, n_kf, 3), A = st.in_or_zero(kf_angle, n_kf);
+    const auto F = st.in_or_zero(kf_flags, n_kf), MD = st.in_or_zero(mp_desc, n_kf, 32);
+    const auto L = st.in_or_zero(level, n_kf), M = st.out(match, cc), N = st.inout(counts, 3);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = stage_grid(st, p, im, dN, cc)) return rc;
+    if (int rc = plvi_search_reloc_batch(1, p, st.dev(im.k), st.dev(im.d), dN, cc, st.dev(im.b), st.dev(im.co),
+                                         st.dev(im.ci), st.dev(F), st.dev(X), st.dev(S), st.dev(L), st.dev(A),
+                                         st.dev(MD), dN + 1, kc, st.dev(M), dN + 2, nullptr))
         return rc;
-    return st.finish(dN + 2, match, oM, n_cur);
+    if (int rc = st.fetch()) return rc;
+    return counts[2];
 }
 
 // 50 * ratioHamming >= 256 would accept the bestDist = 256 of a search without
@@ -965,28 +962,23 @@ extern "C" int plvi_search_sim3_projection(const plvi_sim3_proj_params* p, const
     if (n_pt > 0 && (!flags || !x3dc || !dist || !dot || !level || !mp_desc)) return PLVI_E_BADARG;
     if (n_kp == 0) return 0;
     const int kc = n_kp, pc = std::max(n_pt, 1);
+    int counts[3] = {n_kp, n_pt, 0};  // [2]: nmatches
     HostStage st;
-    const size_t oK = st.put(sizeof(plvi_keypoint) * kc), oD = st.put(32 * (size_t)kc), oB = st.put(kc);
-    const size_t oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)kc), oF = st.put(pc);
-    const size_t oX = st.put(12 * (size_t)pc), oS = st.put(12 * (size_t)pc), oT = st.put(8 * (size_t)pc);
-    const size_t oL = st.put(4 * (size_t)pc), oMD = st.put(32 * (size_t)pc), oM = st.put(4 * (size_t)kc);
-    const size_t oN = st.put(16);
-    if (st.alloc()) return PLVI_E_HIP;
-    const int counts[2] = {n_kp, n_pt};
-    if (st.up(oK, kps, sizeof(plvi_keypoint) * kc) | st.up(oD, desc, 32 * (size_t)kc) |
-        st.up_or_zero(oB, matched, kc) | st.up(oF, flags, n_pt) | st.up(oX, x3dc, 12 * (size_t)n_pt) |
-        st.up(oS, dist, 12 * (size_t)n_pt) | st.up(oT, dot, 8 * (size_t)n_pt) | st.up(oL, level, 4 * (size_t)n_pt) |
-        st.up(oMD, mp_desc, 32 * (size_t)n_pt) | st.up(oN, counts, sizeof counts))
-        return PLVI_E_HIP;
-    int* dN = st.at<int>(oN);
-    if (int rc = stage_grid(st, p, oK, dN, kc, oCO, oCI)) return rc;
-    if (int rc = plvi_search_sim3_projection_batch(1, p, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, kc,
-                                                   st.at<uint8_t>(oB), st.at<int>(oCO), st.at<int>(oCI),
-                                                   st.at<uint8_t>(oF), st.at<float>(oX), st.at<float>(oS),
-                                                   st.at<double>(oT), st.at<int>(oL), st.at<uint8_t>(oMD), dN + 1, pc,
-                                                   st.at<int>(oM), dN + 2, nullptr))
+    const StagedImage im = stage_image(st, kps, desc, matched, n_kp, kc);
+    const auto X = st.in_or_zero(x3dc, n_pt, 3), S = st.in_or_zero(dist, n_pt, 3);
+    const auto T = st.in_or_zero(dot, n_pt);
+    const auto F = st.in_or_zero(flags, n_pt), MD = st.in_or_zero(mp_desc, n_pt, 32);
+    const auto L = st.in_or_zero(level, n_pt), M = st.out(match, kc), N = st.inout(counts, 3);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = stage_grid(st, p, im, dN, kc)) return rc;
+    if (int rc = plvi_search_sim3_projection_batch(1, p, st.dev(im.k), st.dev(im.d), dN, kc, st.dev(im.b),
+                                                   st.dev(im.co), st.dev(im.ci), st.dev(F), st.dev(X), st.dev(S),
+                                                   st.dev(T), st.dev(L), st.dev(MD), dN + 1, pc, st.dev(M), dN + 2,
+                                                   nullptr))
         return rc;
-    return st.finish(dN + 2, match, oM, n_kp);
+    if (int rc = st.fetch()) return rc;
+    return counts[2];
 }
 
 extern "C" int plvi_search_local_batch(int n_frames, const plvi_local_params* p, const plvi_keypoint* d_kps,
@@ -1011,26 +1003,21 @@ extern "C" int plvi_search_local(const plvi_local_params* p, const plvi_keypoint
     if (!p || n < 0 || n_mp < 0 || (n > 0 && (!kps || !desc || !match))) return PLVI_E_BADARG;
     if (n == 0) return 0;
     const int cc = n, mc = std::max(n_mp, 1);
+    int counts[3] = {n, n_mp, 0};  // [2]: nmatches
     HostStage st;
-    const size_t oK = st.put(sizeof(plvi_keypoint) * cc), oD = st.put(32 * (size_t)cc), oB = st.put(cc);
-    const size_t oU = st.put(4 * (size_t)cc), oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)cc);
-    const size_t oF = st.put(mc), oP = st.put(16 * (size_t)mc), oL = st.put(4 * (size_t)mc);
-    const size_t oMD = st.put(32 * (size_t)mc), oM = st.put(4 * (size_t)cc), oN = st.put(16);
-    if (st.alloc()) return PLVI_E_HIP;
-    const int counts[2] = {n, n_mp};
-    if (st.up(oK, kps, sizeof(plvi_keypoint) * cc) | st.up(oD, desc, 32 * (size_t)cc) |
-        st.up_or_zero(oB, blocked, cc) | st.up(oU, uright, 4 * (size_t)cc) | st.up(oF, mp_flags, n_mp) |
-        st.up(oP, mp_proj, 16 * (size_t)n_mp) | st.up(oL, mp_level, 4 * (size_t)n_mp) |
-        st.up(oMD, mp_desc, 32 * (size_t)n_mp) | st.up(oN, counts, sizeof counts))
-        return PLVI_E_HIP;
-    int* dN = st.at<int>(oN);
-    if (int rc = stage_grid(st, p, oK, dN, cc, oCO, oCI)) return rc;
-    if (int rc = plvi_search_local_batch(1, p, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, cc,
-                                         st.at<uint8_t>(oB), uright ? st.at<float>(oU) : nullptr, st.at<int>(oCO),
-                                         st.at<int>(oCI), st.at<uint8_t>(oF), st.at<float>(oP), st.at<int>(oL),
-                                         st.at<uint8_t>(oMD), dN + 1, mc, st.at<int>(oM), dN + 2, nullptr))
+    const StagedImage im = stage_image(st, kps, desc, blocked, n, cc);
+    const auto U = st.in(uright, cc), P = st.in_or_zero(mp_proj, n_mp, 4);
+    const auto F = st.in_or_zero(mp_flags, n_mp), MD = st.in_or_zero(mp_desc, n_mp, 32);
+    const auto L = st.in_or_zero(mp_level, n_mp), M = st.out(match, cc), N = st.inout(counts, 3);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = stage_grid(st, p, im, dN, cc)) return rc;
+    if (int rc = plvi_search_local_batch(1, p, st.dev(im.k), st.dev(im.d), dN, cc, st.dev(im.b), st.dev(U),
+                                         st.dev(im.co), st.dev(im.ci), st.dev(F), st.dev(P), st.dev(L), st.dev(MD),
+                                         dN + 1, mc, st.dev(M), dN + 2, nullptr))
         return rc;
-    return st.finish(dN + 2, match, oM, n);
+    if (int rc = st.fetch()) return rc;
+    return counts[2];
 }
 
 extern "C" int plvi_search_local_stereo_batch(
@@ -1065,38 +1052,28 @@ extern "C" int plvi_search_local_stereo(const plvi_local_params* p, const plvi_k
         return PLVI_E_BADARG;
     if (n + n_r == 0) return 0;
     const int cl = std::max(n, 1), cr = std::max(n_r, 1), mc = std::max(n_mp, 1);
-    HostStage st;
-    const size_t oK = st.put(sizeof(plvi_keypoint) * cl), oD = st.put(32 * (size_t)cl), oB = st.put(cl);
-    const size_t oP2 = st.put(4 * (size_t)cl), oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)cl);
-    const size_t oM = st.put(4 * (size_t)cl);
-    const size_t rK = st.put(sizeof(plvi_keypoint) * cr), rD = st.put(32 * (size_t)cr), rB = st.put(cr);
-    const size_t rP2 = st.put(4 * (size_t)cr), rCO = st.put(4 * (size_t)(kGridCells + 1)), rCI = st.put(4 * (size_t)cr);
-    const size_t rM = st.put(4 * (size_t)cr);
-    const size_t oF = st.put(mc), oP = st.put(16 * (size_t)mc), oL = st.put(4 * (size_t)mc);
-    const size_t oPR = st.put(16 * (size_t)mc), oLR = st.put(4 * (size_t)mc), oMD = st.put(32 * (size_t)mc);
-    const size_t oN = st.put(16);
-    if (int rc = st.alloc(true)) return rc;
     const std::vector<int> none(std::max(n, n_r), -1);  // no stereo pairs = every entry -1
-    const int counts[4] = {n, n_r, n_mp, 0};
-    if (st.up(oK, kps, sizeof(plvi_keypoint) * n) | st.up(oD, desc, 32 * (size_t)n) | st.up(oB, blocked, n) |
-        st.up(rK, kps_r, sizeof(plvi_keypoint) * n_r) | st.up(rD, desc_r, 32 * (size_t)n_r) |
-        st.up(rB, blocked_r, n_r) | st.up(oP2, l2r ? l2r : none.data(), 4 * (size_t)n) |
-        st.up(rP2, r2l ? r2l : none.data(), 4 * (size_t)n_r) | st.up(oF, mp_flags, n_mp) |
-        st.up(oP, mp_proj, 16 * (size_t)n_mp) | st.up(oL, mp_level, 4 * (size_t)n_mp) |
-        st.up(oPR, mp_proj_r, 16 * (size_t)n_mp) | st.up(oLR, mp_level_r, 4 * (size_t)n_mp) |
-        st.up(oMD, mp_desc, 32 * (size_t)n_mp) | st.up(oN, counts, sizeof counts))
-        return PLVI_E_HIP;
-    int* dN = st.at<int>(oN);
-    if (int rc = stage_grid(st, p, oK, dN, cl, oCO, oCI)) return rc;
-    if (int rc = stage_grid(st, p, rK, dN + 1, cr, rCO, rCI)) return rc;
+    int counts[4] = {n, n_r, n_mp, 0};                  // [3]: nmatches
+    HostStage st;
+    const StagedImage il = stage_image(st, kps, desc, blocked, n, cl);
+    const StagedImage ir = stage_image(st, kps_r, desc_r, blocked_r, n_r, cr);
+    const auto P2 = st.in_or_zero(l2r ? l2r : none.data(), n), P2R = st.in_or_zero(r2l ? r2l : none.data(), n_r);
+    const auto P = st.in_or_zero(mp_proj, n_mp, 4), PR = st.in_or_zero(mp_proj_r, n_mp, 4);
+    const auto F = st.in_or_zero(mp_flags, n_mp), MD = st.in_or_zero(mp_desc, n_mp, 32);
+    const auto L = st.in_or_zero(mp_level, n_mp), LR = st.in_or_zero(mp_level_r, n_mp);
+    const auto M = st.out_or_scratch(match, n), MR = st.out_or_scratch(match_r, n_r), N = st.inout(counts, 4);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = stage_grid(st, p, il, dN, cl)) return rc;
+    if (int rc = stage_grid(st, p, ir, dN + 1, cr)) return rc;
     if (int rc = plvi_search_local_stereo_batch(
-            1, p, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, cl, st.at<uint8_t>(oB), st.at<int>(oP2),
-            st.at<int>(oCO), st.at<int>(oCI), st.at<plvi_keypoint>(rK), st.at<uint8_t>(rD), dN + 1, cr,
-            st.at<uint8_t>(rB), st.at<int>(rP2), st.at<int>(rCO), st.at<int>(rCI), st.at<uint8_t>(oF),
-            st.at<float>(oP), st.at<int>(oL), st.at<float>(oPR), st.at<int>(oLR), st.at<uint8_t>(oMD), dN + 2, mc,
-            st.at<int>(oM), st.at<int>(rM), dN + 3, nullptr))
+            1, p, st.dev(il.k), st.dev(il.d), dN, cl, st.dev(il.b), st.dev(P2), st.dev(il.co), st.dev(il.ci),
+            st.dev(ir.k), st.dev(ir.d), dN + 1, cr, st.dev(ir.b), st.dev(P2R), st.dev(ir.co), st.dev(ir.ci), st.dev(F),
+            st.dev(P), st.dev(L), st.dev(PR), st.dev(LR), st.dev(MD), dN + 2, mc, st.dev(M), st.dev(MR), dN + 3,
+            nullptr))
         return rc;
-    return st.finish(dN + 3, match, oM, n, match_r, rM, n_r);
+    if (int rc = st.fetch()) return rc;
+    return counts[3];
 }
 
 extern "C" int plvi_search_by_projection_stereo_batch(
@@ -1133,29 +1110,24 @@ extern "C" int plvi_search_by_projection_stereo(const plvi_proj_params* p, const
     if ((n > 0 && (!kps || !desc || !match)) || (n_r > 0 && (!kps_r || !desc_r || !match_r))) return PLVI_E_BADARG;
     if (n_last > 0 && (!x3dc || !x3dr || !last_octave || !last_angle || !mp_desc || !last_flags)) return PLVI_E_BADARG;
     const int cl = std::max(n, 1), cr = std::max(n_r, 1), lc = std::max(n_last, 1);
+    int counts[4] = {n, n_r, n_last, 0};  // [3]: nmatches
     HostStage st;
-    const size_t oK = st.put(sizeof(plvi_keypoint) * cl), oD = st.put(32 * (size_t)cl), oB = st.put(cl);
-    const size_t oCO = st.put(4 * (size_t)(kGridCells + 1)), oCI = st.put(4 * (size_t)cl), oM = st.put(4 * (size_t)cl);
-    const size_t rK = st.put(sizeof(plvi_keypoint) * cr), rD = st.put(32 * (size_t)cr), rB = st.put(cr);
-    const size_t rCO = st.put(4 * (size_t)(kGridCells + 1)), rCI = st.put(4 * (size_t)cr), rM = st.put(4 * (size_t)cr);
-    const size_t oX = st.put(12 * (size_t)lc), oXR = st.put(12 * (size_t)lc), oO = st.put(4 * (size_t)lc);
-    const size_t oA = st.put(4 * (size_t)lc), oMD = st.put(32 * (size_t)lc), oF = st.put(lc), oN = st.put(16);
-    if (int rc = st.alloc(true)) return rc;
-    const int counts[4] = {n, n_r, n_last, 0};
-    if (st.up(oK, kps, sizeof(plvi_keypoint) * n) | st.up(oD, desc, 32 * (size_t)n) | st.up(oB, blocked, n) |
-        st.up(rK, kps_r, sizeof(plvi_keypoint) * n_r) | st.up(rD, desc_r, 32 * (size_t)n_r) |
-        st.up(rB, blocked_r, n_r) | st.up(oX, x3dc, 12 * (size_t)n_last) | st.up(oXR, x3dr, 12 * (size_t)n_last) |
-        st.up(oO, last_octave, 4 * (size_t)n_last) | st.up(oA, last_angle, 4 * (size_t)n_last) |
-        st.up(oMD, mp_desc, 32 * (size_t)n_last) | st.up(oF, last_flags, n_last) | st.up(oN, counts, sizeof counts))
-        return PLVI_E_HIP;
-    int* dN = st.at<int>(oN);
-    if (int rc = stage_grid(st, p, oK, dN, cl, oCO, oCI)) return rc;
-    if (int rc = stage_grid(st, p, rK, dN + 1, cr, rCO, rCI)) return rc;
+    const StagedImage il = stage_image(st, kps, desc, blocked, n, cl);
+    const StagedImage ir = stage_image(st, kps_r, desc_r, blocked_r, n_r, cr);
+    const auto X = st.in_or_zero(x3dc, n_last, 3), XR = st.in_or_zero(x3dr, n_last, 3);
+    const auto A = st.in_or_zero(last_angle, n_last);
+    const auto MD = st.in_or_zero(mp_desc, n_last, 32), F = st.in_or_zero(last_flags, n_last);
+    const auto O = st.in_or_zero(last_octave, n_last);
+    const auto M = st.out_or_scratch(match, n), MR = st.out_or_scratch(match_r, n_r), N = st.inout(counts, 4);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = stage_grid(st, p, il, dN, cl)) return rc;
+    if (int rc = stage_grid(st, p, ir, dN + 1, cr)) return rc;
     if (int rc = plvi_search_by_projection_stereo_batch(
-            1, p, kb8, st.at<plvi_keypoint>(oK), st.at<uint8_t>(oD), dN, cl, st.at<uint8_t>(oB), st.at<int>(oCO),
-            st.at<int>(oCI), st.at<plvi_keypoint>(rK), st.at<uint8_t>(rD), dN + 1, cr, st.at<uint8_t>(rB),
-            st.at<int>(rCO), st.at<int>(rCI), st.at<float>(oX), st.at<float>(oXR), st.at<int>(oO), st.at<float>(oA),
-            st.at<uint8_t>(oMD), st.at<uint8_t>(oF), dN + 2, lc, st.at<int>(oM), st.at<int>(rM), dN + 3, nullptr))
+            1, p, kb8, st.dev(il.k), st.dev(il.d), dN, cl, st.dev(il.b), st.dev(il.co), st.dev(il.ci), st.dev(ir.k),
+            st.dev(ir.d), dN + 1, cr, st.dev(ir.b), st.dev(ir.co), st.dev(ir.ci), st.dev(X), st.dev(XR), st.dev(O),
+            st.dev(A), st.dev(MD), st.dev(F), dN + 2, lc, st.dev(M), st.dev(MR), dN + 3, nullptr))
         return rc;
-    return st.finish(dN + 3, match, oM, n, match_r, rM, n_r);
+    if (int rc = st.fetch()) return rc;
+    return counts[3];
 }

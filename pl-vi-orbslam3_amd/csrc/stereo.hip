@@ -28,6 +28,7 @@
 #include <cmath>
 #include <vector>
 
+#include "host_stage.h"
 #include "plvi_common.h"
 #include "plvi_math.h"
 
@@ -579,38 +580,24 @@ extern "C" int plvi_stereo_match(const plvi_keypoint* kpsL, const uint8_t* descL
         pyrBytes = std::max(pyrBytes, (size_t)lvl_off[l] + (size_t)lvl_w[l] * lvl_h[l]);
     }
     const int capR = std::max(nR, 1);
-    const size_t oKL = 0, oKR = oKL + (size_t)nL * 28, oDL = (oKR + (size_t)capR * 28 + 15) / 16 * 16,
-                 oDR = oDL + (size_t)nL * 32, oPL = oDR + (size_t)capR * 32, oPR = oPL + (pyrBytes + 15) / 16 * 16,
-                 oO = oPR + (pyrBytes + 15) / 16 * 16, oI = oO + (size_t)nL * 8, total = oI + 16;
-    DevBuf d;
-    if (d.alloc(total)) return PLVI_E_HIP;
-    uint8_t* b = d.as<uint8_t>();
-    int* I = reinterpret_cast<int*>(b + oI);  // nL, nR, nstereo, err
-    const int counts[4] = {nL, nR, 0, 0};
-    PLVI_CHECK(hipMemcpy(b + oKL, kpsL, (size_t)nL * 28, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(b + oDL, descL, (size_t)nL * 32, hipMemcpyHostToDevice));
-    if (nR) {
-        PLVI_CHECK(hipMemcpy(b + oKR, kpsR, (size_t)nR * 28, hipMemcpyHostToDevice));
-        PLVI_CHECK(hipMemcpy(b + oDR, descR, (size_t)nR * 32, hipMemcpyHostToDevice));
-    }
-    PLVI_CHECK(hipMemcpy(b + oPL, pyrL, pyrBytes, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(b + oPR, pyrR, pyrBytes, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(I, counts, 16, hipMemcpyHostToDevice));
+    int counts[4] = {nL, nR, 0, 0};  // [2]: nstereo, [3]: err
+    HostStage st;
+    const auto KL = st.in_or_zero(kpsL, nL), KR = st.in_or_zero(kpsR, nR);
+    const auto DL = st.in_or_zero(descL, nL, 32), DR = st.in_or_zero(descR, nR, 32);
+    const auto PL = st.in(pyrL, pyrBytes), PR = st.in(pyrR, pyrBytes);
+    const auto UR = st.out_or_scratch(uright, nL), De = st.out_or_scratch(depth, nL);
+    const auto N = st.inout(counts, 4);
+    if (int rc = st.commit()) return rc;
     for (int l = 0; l < nlevels; ++l) {
-        lv.pl[l] = b + oPL + lvl_off[l];
-        lv.pr[l] = b + oPR + lvl_off[l];
+        lv.pl[l] = st.dev(PL) + lvl_off[l];
+        lv.pr[l] = st.dev(PR) + lvl_off[l];
     }
-    float* ur = reinterpret_cast<float*>(b + oO);
-    int rc = launch_stereo_orb(1, reinterpret_cast<plvi_keypoint*>(b + oKL), b + oDL, I, nL,
-                               reinterpret_cast<plvi_keypoint*>(b + oKR), b + oDR, I + 1, capR, lv,
-                               prm, ur, ur + nL, I + 2, I + 3, nullptr);
-    if (rc) return rc;
-    int out[2];
-    PLVI_CHECK(hipMemcpy(uright, ur, (size_t)nL * 4, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(depth, ur + nL, (size_t)nL * 4, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(out, I + 2, 8, hipMemcpyDeviceToHost));
-    if (out[1]) return PLVI_E_OVERFLOW;
-    return out[0];
+    int* dN = st.dev(N);
+    if (int rc = launch_stereo_orb(1, st.dev(KL), st.dev(DL), dN, nL, st.dev(KR), st.dev(DR), dN + 1, capR, lv, prm,
+                                   st.dev(UR), st.dev(De), dN + 2, dN + 3, nullptr))
+        return rc;
+    if (int rc = st.fetch()) return rc;
+    return counts[3] ? PLVI_E_OVERFLOW : counts[2];
 }
 
 extern "C" size_t plvi_stereo_lines_scratch_bytes(int n_frames, int capL, int capR, int idx_cap) {
@@ -662,37 +649,20 @@ extern "C" int plvi_stereo_lines(const plvi_keyline* klL, const uint8_t* descL, 
     if (nL == 0) return 0;
     const int capL = nL, capR = std::max(nR, 1), idxCap = 65536;
     const size_t sb = plvi_stereo_lines_scratch_bytes(1, capL, capR, idxCap);
-    const size_t oKL = 0, oKR = (size_t)capL * 68, oKU = oKR + (size_t)capR * 68,
-                 oDL = (oKU + (size_t)capL * 68 + 15) / 16 * 16, oDR = oDL + (size_t)capL * 32,
-                 oLE = (oDR + (size_t)capR * 32 + 15) / 16 * 16, oF = oLE + (size_t)capL * 24,
-                 oI = oF + (size_t)capL * 16, oS = (oI + (size_t)capL * 4 + 64 + 15) / 16 * 16, total = oS + sb;
-    DevBuf d;
-    if (d.alloc(total)) return PLVI_E_HIP;
-    uint8_t* b = d.as<uint8_t>();
-    int* I = reinterpret_cast<int*>(b + oI);  // m12[capL] | nL nR nstereo err
-    int* cnt = I + capL;
-    const int counts[4] = {nL, nR, 0, 0};
-    PLVI_CHECK(hipMemcpy(b + oKL, klL, (size_t)nL * 68, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(b + oKU, klUn ? klUn : klL, (size_t)nL * 68, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(b + oDL, descL, (size_t)nL * 32, hipMemcpyHostToDevice));
-    if (nR) {
-        PLVI_CHECK(hipMemcpy(b + oKR, klR, (size_t)nR * 68, hipMemcpyHostToDevice));
-        PLVI_CHECK(hipMemcpy(b + oDR, descR, (size_t)nR * 32, hipMemcpyHostToDevice));
-    }
-    PLVI_CHECK(hipMemcpy(cnt, counts, 16, hipMemcpyHostToDevice));
-    float* F = reinterpret_cast<float*>(b + oF);
-    int rc = plvi_stereo_lines_batch(1, reinterpret_cast<plvi_keyline*>(b + oKL), b + oDL, cnt, capL,
-                                     reinterpret_cast<plvi_keyline*>(b + oKR), b + oDR, cnt + 1, capR,
-                                     reinterpret_cast<plvi_keyline*>(b + oKU), width, height, mbf,
-                                     libstdcxx_range_hint, idxCap, b + oS, sb, I, F, F + 2 * capL,
-                                     reinterpret_cast<double*>(b + oLE), cnt + 2, cnt + 3, nullptr);
-    if (rc) return rc;
-    int out[2];
-    PLVI_CHECK(hipMemcpy(matches_12, I, (size_t)nL * 4, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(disparity, F, (size_t)nL * 8, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(depth, F + 2 * capL, (size_t)nL * 8, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(le, b + oLE, (size_t)nL * 24, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(out, cnt + 2, 8, hipMemcpyDeviceToHost));
-    if (out[1]) return PLVI_E_OVERFLOW;
-    return out[0];
+    int counts[4] = {nL, nR, 0, 0};  // [2]: nstereo, [3]: err
+    HostStage st;
+    const auto KL = st.in_or_zero(klL, nL), KR = st.in_or_zero(klR, nR);
+    const auto KU = st.in_or_zero(klUn ? klUn : klL, nL);  // no undistorted table: the lines as they are
+    const auto DL = st.in_or_zero(descL, nL, 32), DR = st.in_or_zero(descR, nR, 32), S = st.scratch<uint8_t>(sb);
+    const auto Di = st.out_or_scratch(disparity, nL, 2), De = st.out_or_scratch(depth, nL, 2);
+    const auto LE = st.out_or_scratch(le, nL, 3);
+    const auto M = st.out_or_scratch(matches_12, nL), N = st.inout(counts, 4);
+    if (int rc = st.commit()) return rc;
+    int* dN = st.dev(N);
+    if (int rc = plvi_stereo_lines_batch(1, st.dev(KL), st.dev(DL), dN, capL, st.dev(KR), st.dev(DR), dN + 1, capR,
+                                         st.dev(KU), width, height, mbf, libstdcxx_range_hint, idxCap, st.dev(S), sb,
+                                         st.dev(M), st.dev(Di), st.dev(De), st.dev(LE), dN + 2, dN + 3, nullptr))
+        return rc;
+    if (int rc = st.fetch()) return rc;
+    return counts[3] ? PLVI_E_OVERFLOW : counts[2];
 }

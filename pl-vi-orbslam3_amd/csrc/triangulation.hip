@@ -285,40 +285,34 @@ extern "C" int plvi_search_for_triangulation(const plvi_triangulation_pair* pair
     const int cap1 = n1, cap2 = std::max(n2, 1), node_cap = std::max(std::max(nnodes1, nnodes2), 1);
     const int len1 = nnodes1 ? off1[nnodes1] : 0, len2 = nnodes2 ? off2[nnodes2] : 0;
     if (len1 < 0 || len1 > cap1 || len2 < 0 || len2 > cap2) return PLVI_E_BADARG;
+    int counts[5] = {n1, n2, nnodes1, nnodes2, 0};  // [4]: nmatches
     HostStage h;
-    const size_t sP = h.put(sizeof(plvi_triangulation_pair)), sCnt = h.put(5 * sizeof(int));
-    const size_t sK1 = h.put((size_t)cap1 * sizeof(plvi_keypoint)), sD1 = h.put((size_t)cap1 * 32);
-    const size_t sN1 = h.put((size_t)node_cap * 4), sO1 = h.put((size_t)(node_cap + 1) * 4);
-    const size_t sI1 = h.put((size_t)cap1 * 4), sH1 = h.put((size_t)cap1), sU1 = h.put((size_t)cap1 * 4);
-    const size_t sK2 = h.put((size_t)cap2 * sizeof(plvi_keypoint)), sD2 = h.put((size_t)cap2 * 32);
-    const size_t sN2 = h.put((size_t)node_cap * 4), sO2 = h.put((size_t)(node_cap + 1) * 4);
-    const size_t sI2 = h.put((size_t)cap2 * 4), sH2 = h.put((size_t)cap2), sU2 = h.put((size_t)cap2 * 4);
-    const size_t sM = h.put((size_t)cap1 * 4);
-    if (int rc = h.alloc(true)) return rc;
-    const int counts[5] = {n1, n2, nnodes1, nnodes2, 0};
-    int rc = h.up(sP, pair, sizeof(*pair));
-    if (!rc) rc = h.up(sCnt, counts, sizeof(counts));
-    if (!rc) rc = h.up(sK1, kps1, (size_t)n1 * sizeof(plvi_keypoint));
-    if (!rc) rc = h.up(sD1, desc1, (size_t)n1 * 32);
-    if (!rc) rc = h.up(sN1, node1, (size_t)nnodes1 * 4);
-    if (!rc && nnodes1) rc = h.up(sO1, off1, (size_t)(nnodes1 + 1) * 4);
-    if (!rc) rc = h.up(sI1, idx1, (size_t)len1 * 4);
-    if (!rc) rc = h.up(sH1, has_point1, (size_t)n1);
-    if (!rc) rc = h.up(sU1, uright1, (size_t)n1 * 4);
-    if (!rc) rc = h.up(sK2, kps2, (size_t)n2 * sizeof(plvi_keypoint));
-    if (!rc) rc = h.up(sD2, desc2, (size_t)n2 * 32);
-    if (!rc) rc = h.up(sN2, node2, (size_t)nnodes2 * 4);
-    if (!rc && nnodes2) rc = h.up(sO2, off2, (size_t)(nnodes2 + 1) * 4);
-    if (!rc) rc = h.up(sI2, idx2, (size_t)len2 * 4);
-    if (!rc) rc = h.up(sH2, has_point2, (size_t)n2);
-    if (!rc) rc = h.up(sU2, uright2, (size_t)n2 * 4);
-    if (rc) return rc;
-    int* cnt = h.at<int>(sCnt);
-    rc = plvi_search_for_triangulation_batch(
-        1, h.at<plvi_triangulation_pair>(sP), cap1, cap2, node_cap, h.at<plvi_keypoint>(sK1), h.at<uint8_t>(sD1), cnt,
-        h.at<int>(sN1), h.at<int>(sO1), cnt + 2, h.at<int>(sI1), h.at<uint8_t>(sH1), h.at<float>(sU1),
-        h.at<plvi_keypoint>(sK2), h.at<uint8_t>(sD2), cnt + 1, h.at<int>(sN2), h.at<int>(sO2), cnt + 3,
-        h.at<int>(sI2), h.at<uint8_t>(sH2), h.at<float>(sU2), h.at<int>(sM), cnt + 4, nullptr);
-    if (rc) return rc;
-    return h.finish(cnt + 4, matches12, sM, n1);
+    const auto P = h.in(pair, 1);
+    const auto Cnt = h.inout(counts, 5);
+    // one side: keypoints, descriptors, the feature vector (node, off, idx), has_point and uright
+    struct Side {
+        Staged<plvi_keypoint> k;
+        Staged<uint8_t> d;
+        Staged<int> node, off, idx;
+        Staged<uint8_t> has;
+        Staged<float> ur;
+    };
+    auto side = [&](const plvi_keypoint* kps, const uint8_t* desc, int n, const int* node, const int* off, int nnodes,
+                    const int* idx, int len, const uint8_t* has_point, const float* uright) -> Side {
+        return {h.in_or_zero(kps, n), h.in_or_zero(desc, n, 32), h.in_or_zero(node, nnodes, 1, node_cap),
+                h.in_or_zero(off, nnodes ? nnodes + 1 : 0, 1, node_cap + 1), h.in_or_zero(idx, len, 1, n),
+                h.in_or_zero(has_point, n), h.in_or_zero(uright, n)};
+    };
+    const Side a = side(kps1, desc1, n1, node1, off1, nnodes1, idx1, len1, has_point1, uright1);
+    const Side b = side(kps2, desc2, n2, node2, off2, nnodes2, idx2, len2, has_point2, uright2);
+    const auto M = h.out_or_scratch(matches12, n1);
+    if (int rc = h.commit()) return rc;
+    int* cnt = h.dev(Cnt);
+    if (int rc = plvi_search_for_triangulation_batch(
+            1, h.dev(P), cap1, cap2, node_cap, h.dev(a.k), h.dev(a.d), cnt, h.dev(a.node), h.dev(a.off), cnt + 2,
+            h.dev(a.idx), h.dev(a.has), h.dev(a.ur), h.dev(b.k), h.dev(b.d), cnt + 1, h.dev(b.node), h.dev(b.off),
+            cnt + 3, h.dev(b.idx), h.dev(b.has), h.dev(b.ur), h.dev(M), cnt + 4, nullptr))
+        return rc;
+    if (int rc = h.fetch()) return rc;
+    return counts[4];
 }

@@ -8,6 +8,7 @@
 // operation order (-ffp-contract=off).  Element-wise: one thread per point.
 #include <hip/hip_runtime.h>
 
+#include "host_stage.h"
 #include "plvi_common.h"
 
 namespace plvi {
@@ -128,13 +129,13 @@ extern "C" int plvi_image_bounds(const plvi_camera* cam, int cols, int rows, flo
         return PLVI_OK;
     }
     const float in[8] = {0.0f, 0.0f, (float)cols, 0.0f, 0.0f, (float)rows, (float)cols, (float)rows};
-    DevBuf d;
-    if (d.alloc(64)) return PLVI_E_HIP;
-    PLVI_CHECK(hipMemcpy(d.p, in, sizeof(in), hipMemcpyHostToDevice));
-    int rc = plvi_undistort_points(cam, d.as<float>(), 4, d.as<float>() + 8, nullptr);
-    if (rc) return rc;
     float p[8];
-    PLVI_CHECK(hipMemcpy(p, d.as<float>() + 8, sizeof(p), hipMemcpyDeviceToHost));
+    HostStage st;
+    const auto In = st.in(in, 4, 2);
+    const auto Out = st.out(p, 4, 2);
+    if (int rc = st.commit()) return rc;
+    if (int rc = plvi_undistort_points(cam, st.dev(In), 4, st.dev(Out), nullptr)) return rc;
+    if (int rc = st.fetch()) return rc;
     bounds[0] = std::min(p[0], p[4]);  // mnMinX = min(mat(0,0), mat(2,0))
     bounds[1] = std::max(p[2], p[6]);  // mnMaxX = max(mat(1,0), mat(3,0))
     bounds[2] = std::min(p[1], p[3]);  // mnMinY = min(mat(0,1), mat(1,1))

@@ -30,6 +30,7 @@
 #include <memory>
 #include <vector>
 
+#include "host_stage.h"
 #include "plvi_common.h"
 
 namespace plvi {
@@ -534,37 +535,39 @@ extern "C" int plvi_vocab_transform(plvi_vocabulary* h, const uint8_t* desc, int
     if (n == 0 || v.nWords == 0) return PLVI_OK;
     PLVI_CHECK(hipSetDevice(v.device));
     const int cap = n;
-    DevBuf d;
-    const size_t oD = 0, oC = (size_t)32 * cap, oBW = oC + 16, oBV = oBW + ((4 * (size_t)cap + 15) & ~size_t(15));
-    const size_t oBN = oBV + 8 * (size_t)cap, oFN = oBN + 16, oFO = oFN + ((4 * (size_t)cap + 15) & ~size_t(15));
-    const size_t oFI = oFO + ((4 * (size_t)(cap + 1) + 15) & ~size_t(15)), oFC = oFI + ((4 * (size_t)cap + 15) & ~size_t(15));
-    if (d.alloc(oFC + 16)) return PLVI_E_HIP;
-    uint8_t* B = d.as<uint8_t>();
-    PLVI_CHECK(hipMemcpy(B + oD, desc, (size_t)32 * n, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(B + oC, &n, sizeof(int), hipMemcpyHostToDevice));
-    int rc = plvi_vocab_transform_batch(h, B + oD, (const int*)(B + oC), cap, 1, levelsup, (unsigned*)(B + oBW),
-                                        (double*)(B + oBV), (int*)(B + oBN), (unsigned*)(B + oFN), (int*)(B + oFO),
-                                        (unsigned*)(B + oFI), (int*)(B + oFC), nullptr, nullptr, v.stream);
-    if (rc) return rc;
+    int counts[3] = {n, 0, 0};  // [1]: bow_n, [2]: fv_n
+    std::vector<int> off_host(fv_off ? 0 : cap + 1);  // the offsets give fv_idx its length, wanted or not
+    int* off = fv_off ? fv_off : off_host.data();
+    HostStage st;
+    const auto D = st.in(desc, n, 32);
+    const auto BV = st.out_or_scratch(bow_value, cap);
+    const auto BW = st.out_or_scratch(bow_word, cap), FN = st.out_or_scratch(fv_node, cap);
+    const auto FI = st.out_or_scratch(fv_idx, cap);
+    const auto FO = st.out(off, cap + 1), C = st.inout(counts, 3);
+    if (int rc = st.commit()) return rc;
+    int* dC = st.dev(C);
+    if (int rc = plvi_vocab_transform_batch(h, st.dev(D), dC, cap, 1, levelsup, st.dev(BW), st.dev(BV), dC + 1,
+                                            st.dev(FN), st.dev(FO), st.dev(FI), dC + 2, nullptr, nullptr, v.stream))
+        return rc;
     PLVI_CHECK(hipStreamSynchronize(v.stream));
-    int errv = 0, nb = 0, nf = 0;
+    int errv = 0;
     PLVI_CHECK(hipMemcpy(&errv, v.err.p, sizeof(int), hipMemcpyDeviceToHost));
     if (errv) {
         PLVI_CHECK(hipMemset(v.err.p, 0, sizeof(int)));
         return PLVI_E_OVERFLOW;
     }
-    PLVI_CHECK(hipMemcpy(&nb, B + oBN, sizeof(int), hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(&nf, B + oFC, sizeof(int), hipMemcpyDeviceToHost));
+    // counts, then the offsets: every list comes back up to its length
+    if (int rc = st.fetch_one(C, v.stream)) return rc;
+    const int nb = counts[1], nf = counts[2];
+    st.trim(BW, nb);
+    st.trim(BV, nb);
+    st.trim(FN, nf);
+    st.trim(FO, nf + 1);
+    if (int rc = st.fetch_one(FO, v.stream)) return rc;
+    st.trim(FI, off[nf]);
+    if (int rc = st.fetch(v.stream)) return rc;
     *bow_n = nb;
     *fv_n = nf;
-    if (bow_word) PLVI_CHECK(hipMemcpy(bow_word, B + oBW, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-    if (bow_value) PLVI_CHECK(hipMemcpy(bow_value, B + oBV, 8 * (size_t)nb, hipMemcpyDeviceToHost));
-    if (fv_node) PLVI_CHECK(hipMemcpy(fv_node, B + oFN, 4 * (size_t)nf, hipMemcpyDeviceToHost));
-    if (fv_off) PLVI_CHECK(hipMemcpy(fv_off, B + oFO, 4 * (size_t)(nf + 1), hipMemcpyDeviceToHost));
-    int m = 0;
-    if (fv_off) m = fv_off[nf];
-    else PLVI_CHECK(hipMemcpy(&m, B + oFO + 4 * (size_t)nf, sizeof(int), hipMemcpyDeviceToHost));
-    if (fv_idx) PLVI_CHECK(hipMemcpy(fv_idx, B + oFI, 4 * (size_t)m, hipMemcpyDeviceToHost));
     return PLVI_OK;
 }
 
@@ -576,26 +579,18 @@ extern "C" int plvi_vocab_transform_features(plvi_vocabulary* h, const uint8_t* 
     if (n == 0) return PLVI_OK;
     const Vocab& v = h->v;
     PLVI_CHECK(hipSetDevice(v.device));
-    const size_t c4 = ((4 * (size_t)n + 15) & ~size_t(15));
-    DevBuf d;
-    if (d.alloc((size_t)32 * n + 16 + c4 * 7 + 8 * (size_t)n + 64)) return PLVI_E_HIP;
-    uint8_t* B = d.as<uint8_t>();
-    uint8_t* dd = B;
-    int* dc = (int*)(B + (size_t)32 * n);
-    unsigned* w = (unsigned*)(B + (size_t)32 * n + 16);
-    unsigned* ni = (unsigned*)((uint8_t*)w + c4);
-    unsigned* bw = (unsigned*)((uint8_t*)ni + c4);
-    unsigned* fn = (unsigned*)((uint8_t*)bw + c4);
-    unsigned* fi = (unsigned*)((uint8_t*)fn + c4);
-    int* fo = (int*)((uint8_t*)fi + c4);
-    int* cnts = (int*)((uint8_t*)fo + c4 + 16);
-    double* bv = (double*)((uint8_t*)cnts + 16);
-    PLVI_CHECK(hipMemcpy(dd, desc, (size_t)32 * n, hipMemcpyHostToDevice));
-    PLVI_CHECK(hipMemcpy(dc, &n, sizeof(int), hipMemcpyHostToDevice));
-    int rc = plvi_vocab_transform_batch(h, dd, dc, n, 1, levelsup, bw, bv, cnts, fn, fo, fi, cnts + 1, w, ni, v.stream);
-    if (rc) return rc;
-    PLVI_CHECK(hipStreamSynchronize(v.stream));
-    PLVI_CHECK(hipMemcpy(word, w, 4 * (size_t)n, hipMemcpyDeviceToHost));
-    PLVI_CHECK(hipMemcpy(nid, ni, 4 * (size_t)n, hipMemcpyDeviceToHost));
-    return PLVI_OK;
+    HostStage st;
+    const auto D = st.in(desc, n, 32);
+    const auto W = st.out(word, n), Ni = st.out(nid, n);
+    // the transform's own outputs are written as well, and dropped
+    const auto BW = st.scratch<unsigned>(n), FN = st.scratch<unsigned>(n), FI = st.scratch<unsigned>(n);
+    const auto BV = st.scratch<double>(n);
+    const auto C = st.in(&n, 1), FO = st.scratch<int>(n + 1), Cnt = st.scratch<int>(2);
+    if (int rc = st.commit()) return rc;
+    int* cnt = st.dev(Cnt);
+    if (int rc = plvi_vocab_transform_batch(h, st.dev(D), st.dev(C), n, 1, levelsup, st.dev(BW), st.dev(BV), cnt,
+                                            st.dev(FN), st.dev(FO), st.dev(FI), cnt + 1, st.dev(W), st.dev(Ni),
+                                            v.stream))
+        return rc;
+    return st.fetch(v.stream);
 }
