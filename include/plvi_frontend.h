@@ -1730,6 +1730,232 @@ int plvi_covis_download(plvi_covis_graph* h, int slot, int* map_kf, int* map_w, 
 int plvi_covis_update(plvi_covis_graph* h, int slot, const plvi_covis_keyframes* kf, const plvi_local_map_pool* mp,
                       const plvi_local_map_pool* ml, const plvi_covis_outputs* out);
 
+/* -------------------------------------------------------- Keyframe culling
+ * LocalMapping::KeyFrameCulling() / KeyFrameCullingWithLines()
+ * (src/LocalMapping.cc:1566-1718 / :1720-1964) after their first two lines,
+ * which are plvi_covis_resort_batch and plvi_covis_rows: the walk over the
+ * current keyframe's covisibles that decides which of them are redundant.  The
+ * walk is sequential -- a culled keyframe's SetBadFlag erases its
+ * observations, which changes Observations() and the observer counts of every
+ * later candidate and can kill features -- and is reproduced as such: every
+ * output equals the reference's, candidate for candidate.  Nothing is applied
+ * to the caller's tables: the call keeps the effects of its own culls in an
+ * overlay and returns them as the changed list, which the caller replays.
+ *
+ * Tables.  Keyframes by slot and the two pools by id, in the layouts of
+ * plvi_local_map_keyframes / plvi_local_map_pool -- of a pool only n, bad,
+ * obs_off and obs_kf are read -- with two additions: one info byte per keyframe-table
+ * entry and, per pool, a plvi_cull_features.  Device pointers for the batch
+ * call, host pointers for plvi_keyframe_culling.
+ *
+ * Precondition (the map's own invariant): every observation (id, K, idx) of a
+ * pool's CSR has mp[K][idx] == id (ml for lines) with idx < nmp[K].  A table
+ * entry without an observation is allowed: EraseObservation then does nothing.
+ * An observation whose slot lies outside [0, kf_cap) or whose idx lies outside
+ * [0, kp_cap) is ignored.  The two-camera branches (NLeft != -1) are not
+ * modelled.
+ *
+ * Semantics of one query (current keyframe q_slot, candidates cand[q_slot]):
+ *   1. Candidates and the break (:1603-1609, :1713).  Candidates are visited
+ *      in list order and `count` is incremented first.  The initial keyframe
+ *      (SKIP_INIT) and a bad one (SKIP_BAD; also a slot outside [0, kf_cap) and
+ *      a keyframe this walk has already erased) are skipped by `continue`.  The
+ *      break test (count > 20 && abort_ba) || count > 100 stands at the bottom
+ *      of the body and every `continue` skips it, the two inertial ones of 6
+ *      included, so the walk can pass 101.
+ *   2. Points (:1616-1672).  Every entry of mp[K] that is not NULL, not bad,
+ *      not dead (5) and, with monocular == 0, not left out by depth (info bit
+ *      6) counts into nMPs; one id twice counts twice.  It is redundant iff its
+ *      live Observations() > 3 (:1630) and at least 4 OTHER observers (slot !=
+ *      K) have an octave <= its own octave + 1 (nObs > thObs, :1661).  In the
+ *      lines function it is counted into nRedundant only with slam_mode == 0
+ *      (:1819); the points function does not read slam_mode.
+ *   3. Lines (:1831-1873).  The same on ml[K] / kl_info, except that 3 other
+ *      observers are enough (nObs >= thObs, :1862); always counted.
+ *   4. The test (:1674, :1877, :1919) is (float)nRedundant > redundant_th *
+ *      (float)n with the product rounded to float, n = nMPs (points function),
+ *      nMPs + nMLs (lines, slam_mode == 0) or nMLs (lines, slam_mode != 0).
+ *      0.9f * 10 rounds up to 9.0f: 9 of 10 is kept.  A candidate that fails
+ *      the test is KEEP.
+ *   5. Non-inertial cull (:1710, :1913): SetBadFlag (points function) or
+ *      SetBadFlagWithLines.  With not_erase set nothing changes (CULLED |
+ *      DEFERRED).  Otherwise every observation by the culled keyframe is
+ *      erased: the feature's live nObs drops by 2 when bit 7 of the erased
+ *      entry's info byte is set and by 1 otherwise, and a feature that had at
+ *      least one erase and ends at nObs <= 2 is dead from then on -- bad, and
+ *      gone from every later candidate's table.  nObs only decreases, so the
+ *      dead set is a function of the set of culled keyframes.
+ *   6. Inertial mode (:1676-1707), in the reference's order: n_kf_in_map <= 21
+ *      -> KEEP_FEW_KF, continue (n_kf_in_map drops by one per keyframe really
+ *      erased); kf_id > kf_id[q_slot] - 2 in unsigned 64-bit -> KEEP_RECENT,
+ *      continue (never for kf_id[q_slot] < 2); prev or next missing ->
+ *      KEEP_NO_CHAIN; t = (float)(timestamp[next] - timestamp[prev]), a double
+ *      subtraction; (imu_init && kf_id < last_ID && t < 3) || t < 0.5 ->
+ *      CULLED_TIME, where last_ID is the id reached by at most 21 prev steps
+ *      from q_slot on the call's own prev_kf table; otherwise inertial_ba2 or
+ *      !(t < 3) -> KEEP_TIME; otherwise the norm decides (7).  A cull relinks
+ *      the chain (next->prev = prev, prev->next = next, own links cleared)
+ *      BEFORE SetBadFlag, so a not_erase keyframe is relinked without being
+ *      erased, and it calls SetBadFlag(), not SetBadFlagWithLines(), from the
+ *      lines function too: the line observations of an inertially culled
+ *      keyframe are NOT erased.
+ *   7. cv::norm stays with the caller.  Where the decision hinges on the norm
+ *      the walk STOPS: the candidate's outcome is NEEDS_NORM, stop is
+ *      PLVI_CULL_STOP_NEEDS_NORM and the candidate stands at position
+ *      n_visited - 1.  The caller evaluates norm < 0.02 and calls again with
+ *      the SAME tables, start = that position, verdict = 0 or 1 and pre_* =
+ *      the changed list of the earlier call as written.  The device rebuilds
+ *      its overlay from that list with the code that applies a cull inside the
+ *      loop; count continues from start; the verdict gives KEEP_NORM or
+ *      CULLED_NORM.  The changed list of a resumed call begins with the pre
+ *      list, so it is fed back whole to the next resume.
+ * The queries of one call are independent: each starts from the call's tables
+ * with its own overlay, and two queries on one map do not see each other's
+ * culls.
+ *
+ * Limits.  The overlay is a list of at most PLVI_CULL_MAX_CHANGED keyframes
+ * in LDS (a walk changes at most 101: a cull does not `continue`), whatever
+ * kf_cap is.  n_queries <= 65535 (PLVI_E_CAPACITY beyond). */
+#define PLVI_CULL_MAX_CHANGED 128
+#define PLVI_CULL_SPEC 101 /* candidates from start whose counts are taken ahead of the walk */
+enum { /* stop[q] */
+  PLVI_CULL_STOP_END = 0,         /* the list ended */
+  PLVI_CULL_STOP_BREAK_ABORT = 1, /* count > 20 && abort_ba */
+  PLVI_CULL_STOP_BREAK_100 = 2,   /* count > 100 */
+  PLVI_CULL_STOP_NEEDS_NORM = 3,
+};
+enum { /* outcome[q][p]: one code per exit of the loop body, | PLVI_CULL_DEFERRED */
+  PLVI_CULL_NOT_VISITED = 0, /* never written; for the caller's fill */
+  PLVI_CULL_SKIP_INIT = 1,
+  PLVI_CULL_SKIP_BAD = 2,
+  PLVI_CULL_KEEP = 3,          /* the test of semantics 4 failed */
+  PLVI_CULL_KEEP_FEW_KF = 4,   /* redundant; KeyFramesInMap() <= 21 */
+  PLVI_CULL_KEEP_RECENT = 5,   /* redundant; mnId > current mnId - 2 */
+  PLVI_CULL_KEEP_NO_CHAIN = 6, /* redundant; mPrevKF or mNextKF missing */
+  PLVI_CULL_KEEP_TIME = 7,     /* redundant; neither time rule culls and the norm cannot */
+  PLVI_CULL_KEEP_NORM = 8,     /* redundant; verdict 0 */
+  PLVI_CULL_CULLED = 9,        /* non-inertial */
+  PLVI_CULL_CULLED_TIME = 10,
+  PLVI_CULL_CULLED_NORM = 11,  /* verdict 1 */
+  PLVI_CULL_NEEDS_NORM = 12,
+  PLVI_CULL_DEFERRED = 0x80,   /* with a CULLED code: mbNotErase, SetBadFlag only set mbToBeErased */
+};
+enum { /* changed_kind, bits */
+  PLVI_CULL_KIND_POINTS = 1,   /* erased: its MapPoint observations are gone, KeyFramesInMap() dropped */
+  PLVI_CULL_KIND_LINES = 2,    /* its MapLine observations are gone too (SetBadFlagWithLines) */
+  PLVI_CULL_KIND_RELINKED = 4, /* taken out of the mPrevKF / mNextKF chain (MergePrevious is due) */
+  PLVI_CULL_KIND_DEFERRED = 8, /* mbToBeErased */
+};
+enum { /* err[q], bits */
+  PLVI_CULL_ERR_OUT = 1,     /* candidates were visited at positions >= out_cap */
+  PLVI_CULL_ERR_CHANGED = 2, /* the changed list is longer than changed_cap (or PLVI_CULL_MAX_CHANGED) */
+  PLVI_CULL_ERR_PRE = 4,     /* pre_n above min(pre_cap, PLVI_CULL_MAX_CHANGED), or an entry with a slot out of
+                                range or unknown kind bits (such an entry is left out) */
+  PLVI_CULL_ERR_QUERY = 8,   /* q_slot outside [0, kf_cap) or start < 0: nothing visited */
+};
+
+/* The keyframe side, by slot. */
+typedef struct plvi_cull_keyframes {
+  int kf_cap;               /* slots */
+  int kp_cap, kl_cap;       /* row lengths of mp / kp_info and ml / kl_info */
+  int cand_stride;          /* row length of cand */
+  const uint8_t* bad;       /* [kf_cap] isBad(); 1 for an empty slot */
+  const uint8_t* init_kf;   /* [kf_cap] mnId == GetMap()->GetInitKFid(); NULL = none */
+  const uint8_t* not_erase; /* [kf_cap] mbNotErase; NULL = none */
+  const int* mp;            /* [kf_cap][kp_cap] GetMapPointMatches() as pool ids, -1 = NULL */
+  const int* nmp;           /* [kf_cap] counts (count contract against kp_cap) */
+  const int* ml;            /* [kf_cap][kl_cap] GetMapLineMatches(); NULL selects KeyFrameCulling() */
+  const int* nml;
+  const uint8_t* kp_info;   /* [kf_cap][kp_cap] bits 0-5 mvKeysUn[i].octave; bit 6 left out by depth: mvDepth[i] >
+                               mThDepth || mvDepth[i] < 0 (read only with monocular == 0); bit 7 erasing this
+                               observation takes 2 off nObs: !mpCamera2 && mvuRight[i] >= 0 (MapPoint.cc:180) */
+  const uint8_t* kl_info;   /* [kf_cap][kl_cap] bits 0-5 mvKeysUn_Line[i].octave; bit 6 the four-way test of :1842;
+                               bit 7 both mvDepth_l[i] >= 0 (MapLine.cc:139) */
+  const int* cand;          /* [kf_cap][cand_stride] GetVectorCovisibleKeyFrames() per slot: the d_ord_kf of */
+  const int* n_cand;        /* [kf_cap]              plvi_covis_rows, read in place (stride conn_cap), and d_ord_n */
+  const unsigned* kf_id;    /* [kf_cap] mnId.  These four are read, and required, with inertial != 0 only */
+  const double* timestamp;  /* [kf_cap] mTimeStamp */
+  const int* prev_kf;       /* [kf_cap] mPrevKF or -1 */
+  const int* next_kf;       /* [kf_cap] mNextKF or -1 */
+} plvi_cull_keyframes;
+
+/* What the walk reads of a pool besides plvi_local_map_pool. */
+typedef struct plvi_cull_features {
+  const int* obs_idx; /* parallel to obs_kf: the feature's index in that keyframe (get<0> of the tuple) */
+  const int* nobs;    /* [n] Observations(): the reference keeps nObs apart from the map (a stereo point counts 2,
+                         MapLine::AddObservation adds 1 where EraseObservation may take 2); NULL = the list length */
+} plvi_cull_features;
+
+/* Host struct, read before the call returns. */
+typedef struct plvi_cull_params {
+  float redundant_th; /* 0.9f or 0.5f as :1576-1582 chooses */
+  int monocular;      /* mbMonocular */
+  int inertial;       /* mbInertial */
+  int slam_mode;      /* mpTracker->SLAM; read by the lines function only */
+} plvi_cull_params;
+
+/* Per query q; arrays of n_queries entries.  start / verdict / pre_* may be
+ * NULL together = every query is fresh. */
+typedef struct plvi_cull_queries {
+  const int* q_slot;       /* mpCurrentKeyFrame: its row of cand is walked */
+  const int* abort_ba;     /* mbAbortBA */
+  const int* n_kf_in_map;  /* mpAtlas->KeyFramesInMap() BEFORE the walk (a resumed call gives it again) */
+  const int* imu_init;     /* mpAtlas->isImuInitialized() */
+  const int* inertial_ba2; /* GetIniertialBA2() */
+  const int* start;        /* first position to visit; 0 for a fresh query */
+  const int* verdict;      /* norm < 0.02 for the candidate at start: 0 or 1; -1 = none */
+  int pre_cap;             /* row length of pre_slot / pre_kind */
+  const int* pre_n;        /* the changed list of the call that stopped at start; 0 for a fresh query */
+  const int* pre_slot;     /* [q][pre_cap] */
+  const int* pre_kind;
+} plvi_cull_queries;
+
+/* Per query q.  Cells at positions < start, >= n_visited or >= out_cap are
+ * never written, nor are changed cells at or past min(n_changed, changed_cap);
+ * n_visited, stop, n_kf_in_map, err and n_changed are always written. */
+typedef struct plvi_cull_outputs {
+  int out_cap, changed_cap;
+  int* n_visited;     /* count: one past the position of the last candidate visited */
+  int* stop;          /* PLVI_CULL_STOP_* */
+  int* n_kf_in_map;   /* KeyFramesInMap() after the walk */
+  int* err;           /* PLVI_CULL_ERR_* */
+  uint8_t* outcome;   /* [q][out_cap] by position in the candidate list */
+  int* n_mps;         /* [q][out_cap] nMPs (0 for a skipped candidate, as the other two) */
+  int* n_mls;         /* [q][out_cap] nMLs; 0 in the points function */
+  int* n_redundant;   /* [q][out_cap] nRedundantObservations */
+  int* n_changed;     /* full length of the changed list */
+  int* changed_slot;  /* [q][changed_cap] every candidate culled, deferred or relinked, in order */
+  int* changed_kind;  /* [q][changed_cap] PLVI_CULL_KIND_* */
+} plvi_cull_outputs;
+
+/* The batch call.  The structs themselves are host memory, read before the
+ * call returns.  ml / fml may be NULL without kf->ml; kf->ml == NULL or ml ==
+ * NULL selects KeyFrameCulling().  PLVI_E_BADARG for a negative size, a
+ * missing required pointer (every pointer not marked optional; fmp->obs_idx
+ * with mp->n > 0) or start / verdict / pre_* given in part; n_queries == 0
+ * returns 0 without a launch.  d_scratch holds at least
+ * plvi_keyframe_culling_scratch_bytes(n_queries) bytes (PLVI_E_BADARG below)
+ * and needs no initialisation; calls that share a scratch block must be
+ * ordered.  Two launches: the counts of the first PLVI_CULL_SPEC candidates of
+ * every query are taken ahead, one workgroup each, against the overlay known
+ * at launch; the walk, one workgroup per query, uses them until it erases a
+ * keyframe and from then on counts each candidate itself under its overlay,
+ * thread 0 doing the gates.  Asynchronous on `stream`, no host read of device
+ * data, no allocation: capturable like the other batch calls. */
+size_t plvi_keyframe_culling_scratch_bytes(int n_queries); /* 256 + 16 * PLVI_CULL_SPEC * n_queries; 0 if negative */
+int plvi_keyframe_culling_batch(int n_queries, const plvi_cull_keyframes* kf, const plvi_local_map_pool* mp,
+                                const plvi_cull_features* fmp, const plvi_local_map_pool* ml,
+                                const plvi_cull_features* fml, const plvi_cull_params* params,
+                                const plvi_cull_queries* queries, const plvi_cull_outputs* out, void* d_scratch,
+                                size_t scratch_bytes, void* stream);
+
+/* One query from host tables, synchronous: the same structs with host
+ * pointers, per-query arrays of one entry.  Returns 0, PLVI_E_CAPACITY when
+ * err[0] != 0 (everything is still written), or another error. */
+int plvi_keyframe_culling(const plvi_cull_keyframes* kf, const plvi_local_map_pool* mp, const plvi_cull_features* fmp,
+                          const plvi_local_map_pool* ml, const plvi_cull_features* fml, const plvi_cull_params* params,
+                          const plvi_cull_queries* queries, const plvi_cull_outputs* out);
+
 /* ---------------------------------------------------------------- Stereo
  * Rectified stereo of the stereo Frame constructors (src/Frame.cc:95-140,
  * :225-300). */

@@ -1872,3 +1872,191 @@ class Covisibility:
               t["ord_w"], ctypes.byref(n[1]), ctypes.byref(n[2]))
         t.update(n_map=n[0].value, n_ord=n[1].value, err=n[2].value)
         return t
+
+
+CULL_MAX_CHANGED = 128  # PLVI_CULL_MAX_CHANGED: keyframes a walk's overlay holds
+CULL_SPEC = 101         # PLVI_CULL_SPEC: candidates whose counts are taken ahead of the walk
+CULL_STOP_END, CULL_STOP_BREAK_ABORT, CULL_STOP_BREAK_100, CULL_STOP_NEEDS_NORM = 0, 1, 2, 3
+(CULL_NOT_VISITED, CULL_SKIP_INIT, CULL_SKIP_BAD, CULL_KEEP, CULL_KEEP_FEW_KF, CULL_KEEP_RECENT, CULL_KEEP_NO_CHAIN,
+ CULL_KEEP_TIME, CULL_KEEP_NORM, CULL_CULLED, CULL_CULLED_TIME, CULL_CULLED_NORM, CULL_NEEDS_NORM) = range(13)
+CULL_DEFERRED = 0x80
+CULL_KIND_POINTS, CULL_KIND_LINES, CULL_KIND_RELINKED, CULL_KIND_DEFERRED = 1, 2, 4, 8
+CULL_ERR_OUT, CULL_ERR_CHANGED, CULL_ERR_PRE, CULL_ERR_QUERY = 1, 2, 4, 8
+
+_CULL_KF = {"bad": np.uint8, "init_kf": np.uint8, "not_erase": np.uint8, "mp": np.int32, "nmp": np.int32,
+            "ml": np.int32, "nml": np.int32, "kp_info": np.uint8, "kl_info": np.uint8, "cand": np.int32,
+            "n_cand": np.int32, "kf_id": np.uint32, "timestamp": np.float64, "prev_kf": np.int32, "next_kf": np.int32}
+_CULL_POOL = {"bad": np.uint8, "obs_off": np.int32, "obs_kf": np.int32, "obs_idx": np.int32, "nobs": np.int32}
+_CULL_Q = ("q_slot", "abort_ba", "n_kf_in_map", "imu_init", "inertial_ba2")
+_CULL_Q_OUT = ("n_visited", "stop", "n_kf_in_map", "err", "n_changed")
+_CULL_CAND_OUT = {"outcome": np.uint8, "n_mps": np.int32, "n_mls": np.int32, "n_redundant": np.int32}
+_CULL_CH_OUT = ("changed_slot", "changed_kind")
+
+
+class CullKeyframes(ctypes.Structure):
+    """plvi_cull_keyframes (include/plvi_frontend.h); pointers as integers, 0 / None = NULL."""
+    _fields_ = [("kf_cap", _LM_I), ("kp_cap", _LM_I), ("kl_cap", _LM_I), ("cand_stride", _LM_I)] + \
+               [(k, _LM_V) for k in _CULL_KF]
+
+
+class CullFeatures(ctypes.Structure):
+    """plvi_cull_features: what the walk reads of a pool besides plvi_local_map_pool."""
+    _fields_ = [("obs_idx", _LM_V), ("nobs", _LM_V)]
+
+
+class CullParams(ctypes.Structure):
+    """plvi_cull_params."""
+    _fields_ = [("redundant_th", ctypes.c_float), ("monocular", _LM_I), ("inertial", _LM_I), ("slam_mode", _LM_I)]
+
+
+class CullQueries(ctypes.Structure):
+    """plvi_cull_queries: per-query arrays."""
+    _fields_ = [(k, _LM_V) for k in _CULL_Q + ("start", "verdict")] + \
+               [("pre_cap", _LM_I), ("pre_n", _LM_V), ("pre_slot", _LM_V), ("pre_kind", _LM_V)]
+
+
+class CullOutputs(ctypes.Structure):
+    """plvi_cull_outputs."""
+    _fields_ = [("out_cap", _LM_I), ("changed_cap", _LM_I)] + \
+               [(k, _LM_V) for k in ("n_visited", "stop", "n_kf_in_map", "err", "outcome", "n_mps", "n_mls",
+                                     "n_redundant", "n_changed", "changed_slot", "changed_kind")]
+
+
+class KeyFrameCulling:
+    """LocalMapping::KeyFrameCulling() / KeyFrameCullingWithLines() (src/LocalMapping.cc:1566-1964) over resident
+    tables (plvi_keyframe_culling[_batch]): the redundancy walk over the covisibles of a current keyframe.
+
+    ``keyframes``: a dict of numpy arrays named as the fields of plvi_cull_keyframes -- bad, mp, nmp, kp_info, cand
+    [kf_cap][cand_stride], n_cand, and optionally init_kf, not_erase, ml / nml / kl_info (ml selects the lines
+    function) and, for inertial, kf_id, timestamp, prev_kf, next_kf.  ``points`` / ``lines``: dicts with bad,
+    obs_off, obs_kf, obs_idx and optionally nobs.  ``rows`` = (d_ord_kf, d_ord_n, conn_cap), the device addresses
+    of Covisibility.rows(), replaces cand / n_cand in the batch form: the graph's rows are walked in place.
+
+    ``cull_batch`` runs on device copies (``self.dev``); ``cull`` runs one query through the host form.  Both return
+    a dict: n_visited, stop, n_kf_in_map, err, n_changed per query, outcome / n_mps / n_mls / n_redundant [q][out_cap]
+    by candidate position, changed_slot / changed_kind [q][changed_cap], sentinel-filled where nothing was written.
+    A walk that stopped for cv::norm is resumed by passing that dict as ``prev`` with ``verdict``."""
+
+    def __init__(self, keyframes, points, lines=None, redundant_th=0.9, monocular=True, inertial=False, slam_mode=0,
+                 rows=None):
+        self._lib = load()
+        self.kf = {k: _table(keyframes[k], dt) for k, dt in _CULL_KF.items() if keyframes.get(k) is not None}
+        pool = lambda p: None if p is None else {  # noqa: E731
+            k: _table(p[k], dt) for k, dt in _CULL_POOL.items() if p.get(k) is not None}
+        self.pools = [pool(points), pool(lines)]
+        self.kf_cap = len(self.kf["bad"])
+        self.params = CullParams(redundant_th, int(monocular), int(inertial), int(slam_mode))
+        self.rows = rows
+        self.dev = None
+
+    def _structs(self, ptr, rows=None):
+        shape = lambda k: self.kf[k].shape[1] if k in self.kf and self.kf[k].ndim == 2 else 0  # noqa: E731
+        kf = CullKeyframes(self.kf_cap, shape("mp"), shape("ml"), rows[2] if rows else shape("cand"))
+        for k in self.kf:
+            setattr(kf, k, ptr("kf", k))
+        if rows:
+            kf.cand, kf.n_cand = rows[0], rows[1]
+        res = [kf]
+        for g, p in zip(("mp", "ml"), self.pools):
+            if p is None:
+                res += [None, None]
+                continue
+            s, f = LocalMapPool(len(p["bad"])), CullFeatures()
+            for k in p:
+                setattr(f if k in ("obs_idx", "nobs") else s, k, ptr(g, k))
+            res += [s, f]
+        return res
+
+    def upload(self):
+        if self.dev is None:
+            tabs = _named_tables(self.kf, self.pools)
+            self.dev = dict(zip(tabs, _to_device(*tabs.values())[0]))
+        return self.dev
+
+    @staticmethod
+    def _host(B, q_slot, abort_ba, n_kf_in_map, imu_init, inertial_ba2, start, verdict, prev, out_cap, changed_cap,
+              fill):
+        """The per-query inputs and the pre-filled outputs as host arrays."""
+        per = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.int32), (B,)))  # noqa: E731
+        qin = dict(zip(_CULL_Q, map(per, (q_slot, abort_ba, n_kf_in_map, imu_init, inertial_ba2))))
+        res = {k: np.full(B + 1, fill, np.int32) for k in _CULL_Q_OUT}  # one cell more than is written
+        for k, dt in _CULL_CAND_OUT.items():
+            res[k] = np.full((B + 1, max(out_cap, 1)), fill & 0x7f if dt == np.uint8 else fill, dt)
+        for k in _CULL_CH_OUT:
+            res[k] = np.full((B + 1, max(changed_cap, 1)), fill, np.int32)
+        if start is not None or verdict is not None or prev is not None:
+            qin["start"] = per(0 if start is None else start)
+            qin["verdict"] = per(-1 if verdict is None else verdict)
+            qin["pre_n"] = per(0)
+            qin["pre_slot"] = np.zeros((B, max(changed_cap, 1)), np.int32)
+            qin["pre_kind"] = np.zeros((B, max(changed_cap, 1)), np.int32)
+            if prev is not None:  # the earlier call's outputs stay where this call does not write
+                for k in _CULL_CAND_OUT:
+                    res[k][:B] = prev[k]
+                qin["pre_n"] = per(prev["n_changed"])
+                qin["pre_slot"][:] = prev["changed_slot"]
+                qin["pre_kind"][:] = prev["changed_kind"]
+                if start is None:
+                    qin["start"] = per(np.maximum(prev["n_visited"] - 1, 0))
+        return qin, res
+
+    def cull_batch(self, q_slot, abort_ba=0, n_kf_in_map=0, imu_init=0, inertial_ba2=0, start=None, verdict=None,
+                   prev=None, out_cap=None, changed_cap=None, fill=-7, stream=None, run=True):
+        """plvi_keyframe_culling_batch of the current keyframes q_slot (the other per-query arguments broadcast).
+        Returns the dict described above plus "past" (the row after the last query of every output: `fill`
+        unless something wrote past the batch) and "rc".  run=False returns (step(stream), fetch()) for capture."""
+        dev = self.upload()
+        structs = self._structs(lambda g, k: dev[(g, k)].ptr, self.rows)
+        B = len(np.atleast_1d(q_slot))
+        out_cap = (self.rows[2] if self.rows else structs[0].cand_stride) if out_cap is None else out_cap
+        changed_cap = CULL_MAX_CHANGED if changed_cap is None else changed_cap
+        qin, res = self._host(B, np.atleast_1d(q_slot), abort_ba, n_kf_in_map, imu_init, inertial_ba2, start, verdict,
+                              prev, out_cap, changed_cap, fill)
+        qbuf = dict(zip(qin, _to_device(*qin.values())[0]))
+        obuf = dict(zip(res, _to_device(*res.values())[0]))
+        qs = CullQueries(pre_cap=max(changed_cap, 1) if "pre_n" in qin else 0)
+        for k, b in qbuf.items():
+            setattr(qs, k, b.ptr)
+        out = CullOutputs(out_cap, changed_cap)
+        for k, b in obuf.items():
+            setattr(out, k, b.ptr)
+
+        sb = load().plvi_keyframe_culling_scratch_bytes(B)
+        scratch = DeviceBuffer(sb)
+
+        def step(s=None):
+            return _status("plvi_keyframe_culling_batch", B, *structs, self.params, qs, out, scratch.ptr, sb,
+                           s or None)
+
+        def fetch(rc=0):
+            _sync()
+            full = {k: obuf[k].download(a) for k, a in res.items()}
+            r = {k: a[:B] for k, a in full.items()}
+            r.update(rc=rc, past={k: a[B].tolist() for k, a in full.items()}, keep=(qbuf, obuf, scratch))
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
+
+    def cull(self, q_slot, abort_ba=0, n_kf_in_map=0, imu_init=0, inertial_ba2=0, start=None, verdict=None,
+             prev=None, out_cap=None, changed_cap=None, fill=-7):
+        """One query through the host form (plvi_keyframe_culling); the same dict with one query, and "rc"
+        (PLVI_E_CAPACITY with an err bit set; any other refusal raises)."""
+        tabs = _named_tables(self.kf, self.pools)
+        structs = self._structs(lambda g, k: tabs[(g, k)].ctypes.data)
+        out_cap = structs[0].cand_stride if out_cap is None else out_cap
+        changed_cap = CULL_MAX_CHANGED if changed_cap is None else changed_cap
+        qin, res = self._host(1, [q_slot], abort_ba, n_kf_in_map, imu_init, inertial_ba2, start, verdict, prev,
+                              out_cap, changed_cap, fill)
+        qs = CullQueries(pre_cap=max(changed_cap, 1) if "pre_n" in qin else 0)
+        for k, a in qin.items():
+            setattr(qs, k, a.ctypes.data)
+        out = CullOutputs(out_cap, changed_cap)
+        for k, a in res.items():
+            setattr(out, k, a.ctypes.data)
+        rc = _status("plvi_keyframe_culling", *structs, self.params, qs, out)
+        if rc < 0 and rc != PLVI_E_CAPACITY:
+            raise PlviError(rc, "plvi_keyframe_culling")
+        r = {k: a[:1] for k, a in res.items()}
+        r.update(rc=rc, past={k: a[1].tolist() for k, a in res.items()})
+        return r
