@@ -22,7 +22,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
 #include "grid_search.h"
@@ -337,17 +336,11 @@ extern "C" int plvi_search_by_bow_stereo_batch(int n_pairs, float nnratio, int c
     if (n_pairs == 0) return PLVI_OK;
     const size_t smem = bow_smem(f_cap, node_cap);
     if (smem > 64 * 1024) return PLVI_E_CAPACITY;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)search_by_bow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  64 * 1024);
-    });
-    hipLaunchKernelGGL(search_by_bow_kernel, dim3(n_pairs), dim3(256), smem, (hipStream_t)stream, nnratio,
-                       check_orientation, kf_cap, f_cap, node_cap, d_kf_desc, d_kf_angle, d_kf_live, d_kf_node,
-                       d_kf_off, d_kf_nnodes, d_kf_idx, d_f_desc, d_f_angle, d_f_n, d_f_node, d_f_off, d_f_nnodes,
-                       d_f_idx, d_f_nleft, d_match_kf, d_nmatches);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    return launch_lds<search_by_bow_kernel>(dim3(n_pairs), dim3(256), smem, (hipStream_t)stream, nnratio,
+                                            check_orientation, kf_cap, f_cap, node_cap, d_kf_desc, d_kf_angle,
+                                            d_kf_live, d_kf_node, d_kf_off, d_kf_nnodes, d_kf_idx, d_f_desc, d_f_angle,
+                                            d_f_n, d_f_node, d_f_off, d_f_nnodes, d_f_idx, d_f_nleft, d_match_kf,
+                                            d_nmatches);
 }
 
 extern "C" int plvi_search_by_bow_batch(int n_pairs, float nnratio, int check_orientation, int kf_cap, int f_cap,
@@ -420,15 +413,10 @@ extern "C" int plvi_search_by_bow_kf_batch(int n_pairs, float nnratio, int check
         !d_angle2 || !d_live2 || !d_n2 || !d_node2 || !d_off2 || !d_nnodes2 || !d_idx2 || !d_matches12 || !d_nmatches)
         return PLVI_E_BADARG;
     const size_t smem = bow_kf_smem(cap1, cap2, node_cap);
-    if (!lds_fits<search_by_bow_kf_kernel>(smem)) return PLVI_E_CAPACITY;
-    PLVI_CHECK(hipFuncSetAttribute((const void*)search_by_bow_kf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)smem));
-    hipLaunchKernelGGL(search_by_bow_kf_kernel, dim3(n_pairs), dim3(256), smem, (hipStream_t)stream, nnratio,
-                       check_orientation, cap1, cap2, node_cap, d_desc1, d_angle1, d_live1, d_n1, d_node1, d_off1,
-                       d_nnodes1, d_idx1, d_desc2, d_angle2, d_live2, d_n2, d_node2, d_off2, d_nnodes2, d_idx2,
-                       d_matches12, d_nmatches);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    return launch_lds<search_by_bow_kf_kernel>(dim3(n_pairs), dim3(256), smem, (hipStream_t)stream, nnratio,
+                                               check_orientation, cap1, cap2, node_cap, d_desc1, d_angle1, d_live1,
+                                               d_n1, d_node1, d_off1, d_nnodes1, d_idx1, d_desc2, d_angle2, d_live2,
+                                               d_n2, d_node2, d_off2, d_nnodes2, d_idx2, d_matches12, d_nmatches);
 }
 
 // Single pair from host memory, synchronous.  Returns nmatches (>= 0) or an error.

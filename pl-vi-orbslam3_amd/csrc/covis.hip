@@ -5,7 +5,7 @@
 //
 // The reference applied to the queries one after another equals a gather: a query's counter
 // depends on observations, bad flags and map ids only, never on connection state, so
-//   covis_count_kernel   one workgroup per query.  The vote of lm_keyframes_kernel (kf_vote.h) as a
+//   covis_count_kernel   one workgroup per query.  The vote of lm_keyframes_kernel (map_pool.h) as a
 //                        histogram over the slots, in LDS up to PLVI_COVIS_LDS_KF and in scratch
 //                        above; an ordered block-scan compaction of `order` gives the counter (the
 //                        query's new weight map, written in place: no other workgroup reads it),
@@ -26,7 +26,7 @@
 #include <cstring>
 #include <vector>
 
-#include "kf_vote.h"
+#include "block_prims.h"
 #include "map_pool.h"
 #include "plvi_common.h"
 

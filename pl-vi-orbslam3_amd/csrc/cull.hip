@@ -26,7 +26,7 @@
 // DESIGN.md section 24).
 #include <cstring>
 
-#include "kf_vote.h"
+#include "block_prims.h"
 #include "map_pool.h"
 #include "plvi_common.h"
 
@@ -185,6 +185,8 @@ __device__ void cull_count(const CullOverlay& ov, const CullPool& p, int K, int 
         ++n_f;
         n_red += live > 3 && hits >= need;
     }
+    // not wave_sum: with the __shfl_xor butterfly the compiler schedules the whole count loop
+    // differently and a count takes 1.8 % longer (profiles/r18/cull.txt); only lane 0 reads the sums
 #pragma unroll
     for (int m = kWave / 2; m > 0; m >>= 1) {
         n_f += __shfl_down(n_f, m, kWave);

@@ -29,6 +29,7 @@
 #include <cstring>
 #include <vector>
 
+#include "block_prims.h"
 #include "host_stage.h"
 #include "plvi_common.h"
 
@@ -47,11 +48,6 @@ constexpr int kPosBits = 11;                              // position field of t
 constexpr int kKeyNone = 0x7f7f7f7f;                      // the memset pattern: above every key
 static_assert(PLVI_DISTINCTIVE_MAX_OBS <= (1 << kPosBits), "the position must fit the key");
 static_assert((256 << kPosBits | ((1 << kPosBits) - 1)) < kKeyNone, "every key is below the preset");
-
-__device__ __forceinline__ int hamming(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1) {
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 __device__ __forceinline__ int list_length(const int* __restrict__ obs_off, int f, int max_obs) {
     return max(min(obs_off[f + 1] - obs_off[f], max_obs), 0);
@@ -93,7 +89,7 @@ __global__ __launch_bounds__(256) void distinctive_small_kernel(
 #pragma unroll
     for (int j = 0; j < S; ++j) {
         const uint4 b0 = sdesc[wv][segbase + j][0], b1 = sdesc[wv][segbase + j][1];
-        d[j] = (segmask >> j) & 1 ? hamming(a0, a1, b0, b1) : 512;
+        d[j] = (segmask >> j) & 1 ? hamming256(a0, a1, b0, b1) : 512;
     }
     // the smallest v in [0, 256] with #{j : d[j] <= v} > k is the k-th smallest (0-based)
     int lo = 0, hi = 256;
@@ -146,12 +142,7 @@ __device__ __forceinline__ int hist_kth(unsigned* __restrict__ h, int k, int lan
     h4[lane] = make_uint4(0, 0, 0, 0);
     if (lane == 0) h[256] = 0;
     const int s = (int)(c.x + c.y + c.z + c.w);
-    int incl = s;
-#pragma unroll
-    for (int m = 1; m < kWave; m <<= 1) {
-        const int up = __shfl_up(incl, m, kWave);
-        if (lane >= m) incl += up;
-    }
+    const int incl = wave_incl_scan(s, lane);
     const unsigned long long above = __ballot(incl > k);
     if (!above) return 256;  // the k-th value lies in bin 256
     const int L = __ffsll((long long)above) - 1;
@@ -214,7 +205,7 @@ __global__ __launch_bounds__(kLargeThreads) void distinctive_large_kernel(
             const bool ok = sok[j] != 0;  // an ignored entry goes to a padding bin that is never read
 #pragma unroll
             for (int r = 0; r < kLargeRows; ++r)
-                atomicAdd(&h[r * kHistPitch + (ok ? hamming(a0[r], a1[r], b0, b1) : kHistDump)], 1u);
+                atomicAdd(&h[r * kHistPitch + (ok ? hamming256(a0[r], a1[r], b0, b1) : kHistDump)], 1u);
         }
         // the wave's own LDS atomics, read back by the same wave
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -263,13 +254,13 @@ extern "C" int plvi_distinctive_descriptors_batch(int n_feat, const uint8_t* d_p
         const int split = (max_obs + kLargeRowsPerGroup - 1) / kLargeRowsPerGroup;
         const int cap = (max_obs + 3) & ~3;
         const size_t smem = large_lds_bytes(cap);
-        if ((long long)n_feat * split > INT_MAX || !lds_fits<distinctive_large_kernel>(smem)) return PLVI_E_CAPACITY;
-        PLVI_CHECK(hipFuncSetAttribute((const void*)distinctive_large_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        if ((long long)n_feat * split > INT_MAX) return PLVI_E_CAPACITY;
+        // (max_obs <= PLVI_DISTINCTIVE_MAX_OBS keeps smem near 90 KB: launch_lds cannot refuse after the memset)
         PLVI_CHECK(hipMemsetAsync(d_best_pos, kKeyNone & 0xff, 4 * (size_t)n_feat, st));
-        hipLaunchKernelGGL(distinctive_large_kernel, dim3(n_feat * split), dim3(kLargeThreads), smem, st, split, d_pool,
-                           pool_rows, d_obs_off, d_obs_row, max_obs, cap, d_best_pos);
-        PLVI_CHECK(hipGetLastError());
+        if (int rc = launch_lds<distinctive_large_kernel>(dim3(n_feat * split), dim3(kLargeThreads), smem, st, split,
+                                                          d_pool, pool_rows, d_obs_off, d_obs_row, max_obs, cap,
+                                                          d_best_pos))
+            return rc;
     }
     if (max_obs <= 8)
         launch_small<8>(n_feat, d_pool, pool_rows, d_obs_off, d_obs_row, max_obs, d_best_pos, d_best_median,

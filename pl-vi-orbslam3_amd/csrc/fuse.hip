@@ -263,15 +263,12 @@ extern "C" int plvi_fuse_lines_batch(int n_pairs, const plvi_fuse_line_params* p
     int nchunks;
     const int blocks = fuse_blocks(n_pairs, ml_cap, nchunks);
     const size_t smem = (size_t)kFuseLineBytes * kl_cap;
+    // (the LDS bound here too: a refusal comes before anything is enqueued)
     if (!blocks || !lds_fits<fuse_lines_kernel>(smem)) return PLVI_E_CAPACITY;
-    PLVI_CHECK(hipFuncSetAttribute((const void*)fuse_lines_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)smem));
     PLVI_CHECK(hipMemsetAsync(d_nfused, 0, 4 * (size_t)n_pairs, (hipStream_t)stream));
-    hipLaunchKernelGGL(fuse_lines_kernel, dim3(blocks), dim3(kFuseChunk), smem, (hipStream_t)stream, *p, nchunks, d_kl,
-                       d_kl_desc, d_kl_n, kl_cap, d_flags, d_spc, d_epc, d_dist, d_dot, d_level, d_ml_desc, d_ml_n,
-                       ml_cap, d_fuse_idx, d_fuse_dist, d_nfused);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    return launch_lds<fuse_lines_kernel>(dim3(blocks), dim3(kFuseChunk), smem, (hipStream_t)stream, *p, nchunks, d_kl,
+                                         d_kl_desc, d_kl_n, kl_cap, d_flags, d_spc, d_epc, d_dist, d_dot, d_level,
+                                         d_ml_desc, d_ml_n, ml_cap, d_fuse_idx, d_fuse_dist, d_nfused);
 }
 
 // One pair from host memory, synchronous (grid built on the device).

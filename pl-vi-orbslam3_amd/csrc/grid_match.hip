@@ -143,7 +143,7 @@ __global__ __launch_bounds__(64) void line_match_grid_kernel(
         }
         M12[i] = i2;
     }
-    for (int s = 32; s > 0; s >>= 1) drop += __shfl_xor(drop, s);
+    drop = wave_sum(drop);
     if (lane == 0) {
         nmatch[p] = matches - drop;
         if (s_overflow && err) atomicOr(err, 1);

@@ -1,7 +1,7 @@
 // grid_search.h — the device pieces every grid-window matcher shares:
 //   Frame::GetFeaturesInArea (src/Frame.cc:1006-1075): the cell-range clamps
 //     (grid_window) and the candidate walk over the CSR grid (grid_walk)
-//   ORBmatcher::DescriptorDistance (hamming256)
+//   ORBmatcher::DescriptorDistance (hamming256, block_prims.h)
 //   ORBmatcher::ComputeThreeMaxima (src/ORBmatcher.cc:2304-2345) and the
 //     rotation-histogram bin (three_maxima, rot_bin)
 //   one image's keypoints and grid in LDS (GridSide, grid_side_load)
@@ -11,19 +11,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "block_prims.h"
 #include "plvi_common.h"
 
 namespace plvi {
 
 constexpr int kGridCols = 64, kGridRows = 48, kGridCells = kGridCols * kGridRows;  // include/Frame.h:47-48
-
-// Hamming distance of the 256-bit descriptor (a0, a1) and the one at b.
-__device__ __forceinline__ int hamming256(const uint4 a0, const uint4 a1, const uint8_t* __restrict__ b) {
-    const uint4* pb = reinterpret_cast<const uint4*>(b);
-    const uint4 b0 = pb[0], b1 = pb[1];
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 // The cell range of GetFeaturesInArea(u, v, radius); false where the
 // reference returns an empty vIndices early (:1013-1037, in its order).

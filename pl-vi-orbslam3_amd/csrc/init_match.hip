@@ -339,14 +339,9 @@ extern "C" int plvi_search_for_initialization_batch(int n_pairs, const plvi_init
     if (n_pairs == 0) return PLVI_OK;
     const size_t smem = init_smem(cap1, cap2);
     // (with the kernel's static __shared__ histogram, kept bins, counters)
-    if (!lds_fits<search_init_kernel>(smem)) return PLVI_E_CAPACITY;
-    PLVI_CHECK(hipFuncSetAttribute((const void*)search_init_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)smem));
-    hipLaunchKernelGGL(search_init_kernel, dim3(n_pairs), dim3(256), smem, (hipStream_t)stream, *p, d_kps1, d_desc1,
-                       d_n1, cap1, d_prev_matched, d_kps2, d_desc2, d_n2, cap2, d_cell_off, d_cell_idx, d_matches12,
-                       d_nmatches);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    return launch_lds<search_init_kernel>(dim3(n_pairs), dim3(256), smem, (hipStream_t)stream, *p, d_kps1, d_desc1,
+                                          d_n1, cap1, d_prev_matched, d_kps2, d_desc2, d_n2, cap2, d_cell_off,
+                                          d_cell_idx, d_matches12, d_nmatches);
 }
 
 static int line_search_select(const uint8_t* d_desc1, const int* d_n1, int cap1, const uint8_t* d_desc2,

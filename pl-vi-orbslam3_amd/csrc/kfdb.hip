@@ -34,6 +34,7 @@
 #include <cstring>
 #include <vector>
 
+#include "block_prims.h"
 #include "host_stage.h"
 #include "plvi_common.h"
 
@@ -66,8 +67,6 @@ struct ChunkArgs {
     int row[kChunk], slot[kChunk], map[kChunk];
     unsigned seq[kChunk];
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // minCommonWords = maxCommonWords * 0.8f (KeyFrameDatabase.cc:673 / :826): int -> float, one
 // float multiply, truncation
@@ -251,11 +250,9 @@ __global__ __launch_bounds__(kCountThreads) void kfdb_count_kernel(
                     f = min(f, w);
                 }
             }
+            c = wave_sum(c);
 #pragma unroll
-            for (int m = kWave / 2; m >= 1; m >>= 1) {
-                c += __shfl_xor(c, m, kWave);
-                f = min(f, (unsigned)__shfl_xor((int)f, m, kWave));
-            }
+            for (int m = kWave / 2; m >= 1; m >>= 1) f = min(f, (unsigned)__shfl_xor((int)f, m, kWave));
             if (kSingle && c > 0) {
                 const double sc = ordered_score(sq, sv, nq, top, kw, kf_value + (size_t)s * word_cap, ns, lane);
                 // the A/B build scores every sharing pair (d_score is the handle's scratch here); the
@@ -335,57 +332,6 @@ __global__ void kfdb_carry_kernel(int n_queries, int slot_cap, const int* __rest
     member[s] = m;
 }
 
-// ascending bitonic sort of n (a power of two) keys, val (nullable) carried along
-__device__ void bitonic_sort(u64* key, int* val, int n, int tid) {
-    for (int k = 2; k <= n; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (n >> 1); t += kSelThreads) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
-                const bool up = (i & k) == 0;
-                const u64 a = key[i], b = key[p];
-                if ((a > b) == up) {
-                    key[i] = b;
-                    key[p] = a;
-                    if (val) {
-                        const int va = val[i];
-                        val[i] = val[p];
-                        val[p] = va;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-}
-
-// exclusive scan of v over the workgroup (every thread calls it); *total = the sum
-__device__ int block_scan(int v, int* s_wave, int tid, int* total) {
-    const int lane = tid & (kWave - 1), wv = tid / kWave;
-    int incl = v;
-#pragma unroll
-    for (int m = 1; m < kWave; m <<= 1) {
-        const int up = __shfl_up(incl, m, kWave);
-        if (lane >= m) incl += up;
-    }
-    __syncthreads();  // s_wave may still be read from the previous call
-    if (lane == kWave - 1) s_wave[wv] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kSelWaves; ++w) {
-        const int x = s_wave[w];
-        if (w < wv) base += x;
-        tot += x;
-    }
-    *total = tot;
-    return base + incl - v;
-}
-
-__device__ __forceinline__ int next_pow2(int n) {
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 struct SelectArgs {
     int slot_cap, sort_cap, mode, n_best, cand_cap, n_maps;
     const int* cnt;
@@ -437,13 +383,13 @@ __global__ __launch_bounds__(kSelThreads) void kfdb_select_kernel(SelectArgs a) 
         }
     __syncthreads();
     const int L = s_len;
-    const int P = next_pow2(L);
+    const int P = pow2_at_least(L, 1);
     for (int i = L + tid; i < P; i += kSelThreads) {
         key[i] = ~0ull;
         val[i] = -1;
     }
     __syncthreads();
-    bitonic_sort(key, val, P, tid);
+    bitonic_sort<kSelThreads>(key, val, P, tid);
     for (int i = tid; i < L; i += kSelThreads) ord[i] = val[i];
     if (tid == 0 && a.norder) a.norder[q] = L;
     __syncthreads();
@@ -455,7 +401,7 @@ __global__ __launch_bounds__(kSelThreads) void kfdb_select_kernel(SelectArgs a) 
         const int s = i < L ? ord[i] : -1;
         const int flag = s >= 0 && cnt[s] > minc;
         int tot;
-        const int pos = block_scan(flag, s_wave, tid, &tot);
+        const int pos = block_scan<kSelWaves>(flag, s_wave, tid, &tot);
         if (flag) val[n_sc + pos] = s;
         n_sc += tot;
     }
@@ -488,7 +434,7 @@ __global__ __launch_bounds__(kSelThreads) void kfdb_select_kernel(SelectArgs a) 
 
     // the processing order: mode 0 the list order, mode 1 list::sort(compFirst) -- stable, descending
     if (a.mode == 1) {
-        const int P2 = next_pow2(n_sc);
+        const int P2 = pow2_at_least(n_sc, 1);
         for (int j = tid; j < P2; j += kSelThreads) {
             u64 k = ~0ull;
             if (j < n_sc) {
@@ -501,7 +447,7 @@ __global__ __launch_bounds__(kSelThreads) void kfdb_select_kernel(SelectArgs a) 
             key[j] = k;
         }
         __syncthreads();
-        bitonic_sort(key, nullptr, P2, tid);
+        bitonic_sort<kSelThreads>(key, P2, tid);
     }
 
     // the first entry of every pBestKF among those that pass
@@ -530,7 +476,7 @@ __global__ __launch_bounds__(kSelThreads) void kfdb_select_kernel(SelectArgs a) 
             }
         }
         int tot;
-        const int pos = block_scan(flag, s_wave, tid, &tot);
+        const int pos = block_scan<kSelWaves>(flag, s_wave, tid, &tot);
         const int p0 = n0 + (pos & 0xffff), p1 = n1 + (pos >> 16);
         if (a.mode == 1) {
             if ((flag & 1) && p0 < a.n_best) a.loop[(size_t)q * a.n_best + p0] = best;
@@ -612,8 +558,7 @@ extern "C" int plvi_kfdb_create(int n_words, int slot_cap, int word_cap, int sco
     h->device = device;
     h->occupied.assign(slot_cap, 0);
     h->map.assign(slot_cap, 0);
-    h->sort_cap = 1;
-    while (h->sort_cap < slot_cap) h->sort_cap <<= 1;
+    h->sort_cap = pow2_at_least(slot_cap, 1);
     const size_t cells = (size_t)slot_cap * word_cap;
     if (h->word.alloc(4 * cells) || h->value.alloc(8 * cells) || h->n.alloc(4 * (size_t)slot_cap) ||
         h->dmap.alloc(4 * (size_t)slot_cap) || h->seq.alloc(4 * (size_t)slot_cap) ||
@@ -793,27 +738,25 @@ extern "C" int plvi_kfdb_query_batch(plvi_kf_database* h, int n_queries, const u
     if (PLVI_KFDB_LANE_PER_SLOT) spb = 64;  // a lane per slot: one wave's worth of slots per workgroup
     const dim3 grid((S + spb - 1) / spb, n_queries);
     const size_t lds_count = (size_t)4 * q_cap + 16, lds_score = (size_t)12 * q_cap + 16;
+    // (the static_assert on PLVI_KFDB_MAX_WORDS keeps the staged query within what launch_lds accepts)
     if (PLVI_KFDB_SINGLE_PASS) {
-        PLVI_CHECK(hipFuncSetAttribute((const void*)kfdb_count_kernel<true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_score));
-        hipLaunchKernelGGL(kfdb_count_kernel<true>, grid, dim3(kCountThreads), lds_score, st, S, h->word_cap, spb,
-                           h->word.as<unsigned>(), h->value.as<double>(), h->n.as<int>(), d_q_word, d_q_value, d_q_n,
-                           q_cap, cnt, h->first.as<unsigned>(), h->maxc.as<int>(), h->all_score.as<double>(),
-                           h->fsc.as<float>());
+        if (int rc = launch_lds<kfdb_count_kernel<true>>(
+                grid, dim3(kCountThreads), lds_score, st, S, h->word_cap, spb, h->word.as<unsigned>(),
+                h->value.as<double>(), h->n.as<int>(), d_q_word, d_q_value, d_q_n, q_cap, cnt, h->first.as<unsigned>(),
+                h->maxc.as<int>(), h->all_score.as<double>(), h->fsc.as<float>()))
+            return rc;
     } else {
-        PLVI_CHECK(hipFuncSetAttribute((const void*)kfdb_count_kernel<false>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_count));
-        hipLaunchKernelGGL(kfdb_count_kernel<false>, grid, dim3(kCountThreads), lds_count, st, S, h->word_cap, spb,
-                           h->word.as<unsigned>(), h->value.as<double>(), h->n.as<int>(), d_q_word, d_q_value, d_q_n,
-                           q_cap, cnt, h->first.as<unsigned>(), h->maxc.as<int>(), d_score, h->fsc.as<float>());
-        PLVI_CHECK(hipGetLastError());
-        PLVI_CHECK(hipFuncSetAttribute((const void*)kfdb_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds_score));
-        hipLaunchKernelGGL(kfdb_score_kernel, grid, dim3(kCountThreads), lds_score, st, S, h->word_cap, spb,
-                           h->word.as<unsigned>(), h->value.as<double>(), h->n.as<int>(), d_q_word, d_q_value, d_q_n,
-                           q_cap, cnt, h->maxc.as<int>(), d_score, h->fsc.as<float>());
+        if (int rc = launch_lds<kfdb_count_kernel<false>>(
+                grid, dim3(kCountThreads), lds_count, st, S, h->word_cap, spb, h->word.as<unsigned>(),
+                h->value.as<double>(), h->n.as<int>(), d_q_word, d_q_value, d_q_n, q_cap, cnt, h->first.as<unsigned>(),
+                h->maxc.as<int>(), d_score, h->fsc.as<float>()))
+            return rc;
+        if (int rc = launch_lds<kfdb_score_kernel>(grid, dim3(kCountThreads), lds_score, st, S, h->word_cap, spb,
+                                                   h->word.as<unsigned>(), h->value.as<double>(), h->n.as<int>(),
+                                                   d_q_word, d_q_value, d_q_n, q_cap, cnt, h->maxc.as<int>(), d_score,
+                                                   h->fsc.as<float>()))
+            return rc;
     }
-    PLVI_CHECK(hipGetLastError());
     hipLaunchKernelGGL(kfdb_carry_kernel, dim3((S + 255) / 256), dim3(256), 0, st, n_queries, S, cnt,
                        h->maxc.as<int>(), h->fsc.as<float>(), member,
                        PLVI_KFDB_SINGLE_PASS ? h->all_score.as<double>() : nullptr, d_score);
@@ -849,11 +792,7 @@ extern "C" int plvi_kfdb_query_batch(plvi_kf_database* h, int n_queries, const u
     a.merge = d_merge;
     a.nmerge = d_nmerge;
     const size_t lds_sel = h->sort_cap <= kSortLds ? (size_t)12 * h->sort_cap : 16;
-    PLVI_CHECK(hipFuncSetAttribute((const void*)kfdb_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds_sel));
-    hipLaunchKernelGGL(kfdb_select_kernel, dim3(n_queries), dim3(kSelThreads), lds_sel, st, a);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    return launch_lds<kfdb_select_kernel>(dim3(n_queries), dim3(kSelThreads), lds_sel, st, a);
 }
 
 extern "C" int plvi_kfdb_query(plvi_kf_database* h, const unsigned* q_word, const double* q_value, int q_n, int q_map,

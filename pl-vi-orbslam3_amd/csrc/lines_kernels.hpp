@@ -5,6 +5,7 @@
 // Compiled with -ffp-contract=off (bit-exact f32/f64 sequences).
 #include <hip/hip_runtime.h>
 
+#include "block_prims.h"
 #include "lines_device.h"
 #include "plvi_common.h"
 #include "plvi_math.h"
@@ -1160,27 +1161,14 @@ __global__ __launch_bounds__(256) void line_assemble_kernel(const LineOctDev* __
         // after them) any sort gives its order: a block-wide bitonic sort of
         // (response desc, index) keys, then a tie check; only a frame with
         // such a tie replays the std::sort restatement on one thread.
-        int P = 256;
-        while (P < n) P <<= 1;
+        const int P = pow2_at_least(n, 256);
         unsigned long long* K = reinterpret_cast<unsigned long long*>(s_items);
         for (int i = threadIdx.x; i < P; i += 256)
             K[i] = i < n ? ((0xFFFFFFFFull - (unsigned long long)__float_as_uint(tmp[i].response)) << 32) |
                                (unsigned)i
                          : ~0ull;
         __syncthreads();
-        for (int k = 2; k <= P; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = threadIdx.x; t < P / 2; t += 256) {
-                    const int i = (t / j) * 2 * j + (t % j), ixj = i + j;
-                    const bool asc = (i & k) == 0;
-                    const unsigned long long x = K[i], y = K[ixj];
-                    if ((x > y) == asc) {
-                        K[i] = y;
-                        K[ixj] = x;
-                    }
-                }
-                __syncthreads();
-            }
+        bitonic_sort<256>(K, P, (int)threadIdx.x);
         bool tie = false;
         for (int i = threadIdx.x; i < nfinal && i + 1 < n; i += 256) tie |= (K[i] >> 32) == (K[i + 1] >> 32);
         if (__syncthreads_or(tie)) {

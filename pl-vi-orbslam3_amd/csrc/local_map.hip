@@ -27,7 +27,7 @@
 #include <climits>
 #include <cstring>
 
-#include "kf_vote.h"
+#include "block_prims.h"
 #include "map_pool.h"
 #include "plvi_common.h"
 
@@ -278,8 +278,7 @@ __global__ __launch_bounds__(kListThreads) void lm_count_kernel(LmArgs a) {
             c += id >= 0 && is_first(S, f, id, p);
         }
     }
-#pragma unroll
-    for (int m = kWave / 2; m >= 1; m >>= 1) c += __shfl_xor(c, m, kWave);
+    c = wave_sum(c);
     if ((tid & (kWave - 1)) == 0 && c) atomicAdd(&s_cnt, c);
     __syncthreads();
     if (tid == 0) S.cnt[(size_t)f * a.G + b] = s_cnt;

@@ -1,6 +1,6 @@
 // map_pool.h — what the local-map update and the covisibility graph share
-// about a plvi_local_map_pool: its argument check and its staging for their
-// host forms.
+// about a plvi_local_map_pool: its argument check, its staging for their
+// host forms, and the keyframe vote over its observation lists.
 #pragma once
 #include "host_stage.h"
 
@@ -32,6 +32,17 @@ inline void stage_pool(HostStage& hs, plvi_local_map_pool& p, PoolRows rows) {
     hs.field(p.normal, HostStage::In, n, 3);
     hs.field(p.dist, HostStage::In, n, 2);
     hs.field(p.desc, HostStage::In, n, 32);
+}
+
+// The keyframe vote of lm_keyframes_kernel (local_map.hip) and covis_count_kernel (covis.hip):
+// the observation list of feature id adds 1 to hist[kf] for each of its keyframes, hist[0, K)
+// a histogram over the keyframe slots (LDS or global); a slot outside is ignored.
+__device__ __forceinline__ void vote_observations(int* hist, int K, const int* obs_off, const int* obs_kf, int id) {
+    const int o1 = obs_off[id + 1];
+    for (int o = obs_off[id]; o < o1; ++o) {
+        const int kf = obs_kf[o];
+        if ((unsigned)kf < (unsigned)K) atomicAdd(hist + kf, 1);
+    }
 }
 
 }  // namespace plvi

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "block_prims.h"
 #include "match_tile.h"
 #include "plvi_common.h"
 
@@ -42,12 +43,8 @@ __global__ __launch_bounds__(256) void hamming_knn2_kernel(const uint8_t* __rest
     const int qi = blockIdx.x * kKnnQ + threadIdx.x;
     if (blockIdx.x * kKnnQ >= nQ) return;
     const bool active = qi < nQ;
-    uint32_t a[8];
-    {
-        const uint4* qp = reinterpret_cast<const uint4*>(q + ((size_t)pair * nq_cap + (active ? qi : 0)) * 32);
-        const uint4 x = qp[0], y = qp[1];
-        a[0] = x.x; a[1] = x.y; a[2] = x.z; a[3] = x.w; a[4] = y.x; a[5] = y.y; a[6] = y.z; a[7] = y.w;
-    }
+    const uint4* qp = reinterpret_cast<const uint4*>(q + ((size_t)pair * nq_cap + (active ? qi : 0)) * 32);
+    const uint4 a0 = qp[0], a1 = qp[1];
     int b0 = INT_MAX, b1 = INT_MAX, j0 = -1, j1 = -1;
     const uint4* tp = reinterpret_cast<const uint4*>(t + (size_t)pair * nt_cap * 32);
     for (int base = 0; base < nT; base += kKnnChunk) {
@@ -56,9 +53,7 @@ __global__ __launch_bounds__(256) void hamming_knn2_kernel(const uint8_t* __rest
         for (int i = threadIdx.x; i < n * 2; i += 256) tr[i] = tp[(size_t)base * 2 + i];
         __syncthreads();
         for (int j = 0; j < n; ++j) {
-            const uint4 x = tr[2 * j], y = tr[2 * j + 1];
-            int d = __popc(a[0] ^ x.x) + __popc(a[1] ^ x.y) + __popc(a[2] ^ x.z) + __popc(a[3] ^ x.w) +
-                    __popc(a[4] ^ y.x) + __popc(a[5] ^ y.y) + __popc(a[6] ^ y.z) + __popc(a[7] ^ y.w);
+            const int d = hamming256(a0, a1, tr[2 * j], tr[2 * j + 1]);
             if (d < b1) {
                 if (d < b0) {
                     b1 = b0; j1 = j0; b0 = d; j0 = base + j;

@@ -722,6 +722,8 @@ __device__ __forceinline__ void orb_nms_cell(const OrbCellDev c, const int f, co
     const unsigned long long keep = __ballot(ka != 0ull) != 0ull ? ka : kb;
     // reserve the cell's block of the list: wave prefix of the per-lane counts
     const int nk = incol ? __popcll(keep) : 0;
+    // (the ladder of wave_incl_scan, block_prims.h, kept as it was written here: the call changes
+    // the schedule of this kernel's tail, and the kernel is 8 % of the headline step)
     int pre = nk;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {

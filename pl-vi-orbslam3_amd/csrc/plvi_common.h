@@ -88,6 +88,19 @@ inline bool lds_fits(size_t dyn) {
     return dyn + static_lds <= 160 * 1024;
 }
 
+// Launches Kernel with `smem` bytes of dynamic LDS: PLVI_E_CAPACITY where that
+// does not fit a CU, else the kernel's dynamic-LDS limit is raised to smem on
+// the current device and the launch is checked.  An entry point that enqueues
+// other work first and must refuse before any of it asks lds_fits itself.
+template <auto Kernel, class... Args>
+inline int launch_lds(dim3 grid, dim3 block, size_t smem, hipStream_t st, const Args&... args) {
+    if (!lds_fits<Kernel>(smem)) return PLVI_E_CAPACITY;
+    PLVI_CHECK(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(Kernel, grid, block, smem, st, args...);
+    PLVI_CHECK(hipGetLastError());
+    return PLVI_OK;
+}
+
 // Read and clear a pipeline's per-frame device error flags (orb_pipeline.hip).
 int read_frame_errors(int* d_err, int nslots, int* frame_flags, int* any, hipStream_t st);
 

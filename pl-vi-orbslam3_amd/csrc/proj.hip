@@ -34,7 +34,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 
 #include "grid_search.h"
 #include "host_stage.h"
@@ -75,19 +74,7 @@ __global__ __launch_bounds__(256) void assign_grid_kernel(const plvi_keypoint* _
     }
     atomicAdd(&s_m, cm);
     __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < P / 2; t += 256) {
-                const int i = (t / j) * 2 * j + (t % j), ixj = i + j;
-                const bool asc = (i & k) == 0;
-                const unsigned x = s_key[i], y = s_key[ixj];
-                if ((x > y) == asc) {
-                    s_key[i] = y;
-                    s_key[ixj] = x;
-                }
-            }
-            __syncthreads();
-        }
+    bitonic_sort<256>(s_key, P, tid);
     const int m = s_m;
     int* CO = cell_off + (size_t)f * (kGridCells + 1);
     int* CI = cell_idx + (size_t)f * cap;
@@ -782,23 +769,6 @@ static size_t proj_smem(int cur_cap, int last_cap) {
 
 static size_t sim3_smem(int kp_cap, int pt_cap) { return side_smem(kp_cap, false) + (size_t)pt_cap * 4 + 64; }
 
-// Launches a matcher kernel, one 256-thread block per pair with `smem` bytes
-// of dynamic LDS; PLVI_E_CAPACITY where that does not fit a CU.
-template <auto Kernel, class... Args>
-static int launch_matcher(int n_blocks, size_t smem, void* stream, const Args&... args) {
-    if (!lds_fits<Kernel>(smem)) return PLVI_E_CAPACITY;
-    PLVI_CHECK(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(Kernel, dim3(n_blocks), dim3(256), smem, (hipStream_t)stream, args...);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
-}
-
-static int grid_pow2(int cap) {
-    int P = 256;
-    while (P < cap) P <<= 1;
-    return P;
-}
-
 }  // namespace plvi
 
 using namespace plvi;
@@ -807,16 +777,10 @@ extern "C" int plvi_assign_grid_batch(const plvi_keypoint* d_kps, const int* d_c
                                       const plvi_grid_params* gp, int* d_cell_off, int* d_cell_idx, void* stream) {
     if (!gp || cap < 1 || cap > (1 << kGridKeyBits) || n_frames < 0) return PLVI_E_BADARG;
     if (n_frames == 0) return PLVI_OK;
-    const int P = grid_pow2(cap);
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)assign_grid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  4 << kGridKeyBits);
-    });
-    hipLaunchKernelGGL(assign_grid_kernel, dim3(n_frames), dim3(256), (size_t)4 * P, (hipStream_t)stream, d_kps,
-                       d_count, cap, P, *gp, d_cell_off, d_cell_idx);
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    const int P = pow2_at_least(cap, 256);
+    return launch_lds<assign_grid_kernel>(
+        dim3(n_frames), dim3(256), (size_t)4 * P, (hipStream_t)stream, d_kps, d_count, cap, P, *gp, d_cell_off,
+        d_cell_idx);
 }
 
 // One staged image: keypoints, descriptors, the blocked flags (NULL: none) and
@@ -851,11 +815,10 @@ extern "C" int plvi_search_by_projection_batch(int n_pairs, const plvi_proj_para
     if (!p || n_pairs < 0 || cur_cap < 1 || last_cap < 1 || cur_cap > 65535 || last_cap > 65535) return PLVI_E_BADARG;
     if (p->nlevels < 1 || p->nlevels > 16) return PLVI_E_BADARG;
     if (n_pairs == 0) return PLVI_OK;
-    return launch_matcher<search_by_projection_kernel>(n_pairs, proj_smem(cur_cap, last_cap), stream, *p, d_cur_kps,
-                                                       d_cur_desc, d_cur_n, cur_cap, d_cur_blocked, d_cur_uright,
-                                                       d_cell_off, d_cell_idx, d_x3dc, d_last_octave, d_last_angle,
-                                                       d_mp_desc, d_last_flags, d_last_n, last_cap, d_match,
-                                                       d_nmatches);
+    return launch_lds<search_by_projection_kernel>(
+        dim3(n_pairs), dim3(256), proj_smem(cur_cap, last_cap), (hipStream_t)stream, *p, d_cur_kps, d_cur_desc,
+        d_cur_n, cur_cap, d_cur_blocked, d_cur_uright, d_cell_off, d_cell_idx, d_x3dc, d_last_octave, d_last_angle,
+        d_mp_desc, d_last_flags, d_last_n, last_cap, d_match, d_nmatches);
 }
 
 // One pair from host memory, synchronous (grid built on the device too).
@@ -895,10 +858,10 @@ extern "C" int plvi_search_reloc_batch(int n_pairs, const plvi_reloc_params* p, 
     if (p->nlevels < 1 || p->nlevels > 16 || p->orb_dist < 0 || p->orb_dist > 255) return PLVI_E_BADARG;
     if (n_pairs == 0) return PLVI_OK;
     // same carve-up as the frame-to-frame matcher
-    return launch_matcher<search_reloc_kernel>(n_pairs, proj_smem(cur_cap, kf_cap), stream, *p, d_cur_kps, d_cur_desc,
-                                               d_cur_n, cur_cap, d_cur_blocked, d_cell_off, d_cell_idx, d_kf_flags,
-                                               d_x3dc, d_dist, d_level, d_kf_angle, d_mp_desc, d_kf_n, kf_cap, d_match,
-                                               d_nmatches);
+    return launch_lds<search_reloc_kernel>(
+        dim3(n_pairs), dim3(256), proj_smem(cur_cap, kf_cap), (hipStream_t)stream, *p, d_cur_kps, d_cur_desc, d_cur_n,
+        cur_cap, d_cur_blocked, d_cell_off, d_cell_idx, d_kf_flags, d_x3dc, d_dist, d_level, d_kf_angle, d_mp_desc,
+        d_kf_n, kf_cap, d_match, d_nmatches);
 }
 
 // One pair from host memory, synchronous (grid built on the device).
@@ -947,10 +910,10 @@ extern "C" int plvi_search_sim3_projection_batch(int n_pairs, const plvi_sim3_pr
     if (!d_kps || !d_desc || !d_kp_n || !d_cell_off || !d_cell_idx || !d_flags || !d_x3dc || !d_dist || !d_dot ||
         !d_level || !d_mp_desc || !d_pt_n || !d_match || !d_nmatches)
         return PLVI_E_BADARG;
-    return launch_matcher<search_sim3_proj_kernel>(n_pairs, sim3_smem(kp_cap, pt_cap), stream, *p, d_kps, d_desc,
-                                                   d_kp_n, kp_cap, d_matched, d_cell_off, d_cell_idx, d_flags, d_x3dc,
-                                                   d_dist, d_dot, d_level, d_mp_desc, d_pt_n, pt_cap, d_match,
-                                                   d_nmatches);
+    return launch_lds<search_sim3_proj_kernel>(
+        dim3(n_pairs), dim3(256), sim3_smem(kp_cap, pt_cap), (hipStream_t)stream, *p, d_kps, d_desc, d_kp_n, kp_cap,
+        d_matched, d_cell_off, d_cell_idx, d_flags, d_x3dc, d_dist, d_dot, d_level, d_mp_desc, d_pt_n, pt_cap,
+        d_match, d_nmatches);
 }
 
 // One pair from host memory, synchronous (grid built on the device).
@@ -990,9 +953,10 @@ extern "C" int plvi_search_local_batch(int n_frames, const plvi_local_params* p,
     if (!p || n_frames < 0 || cap < 1 || mp_cap < 1 || cap > 65535) return PLVI_E_BADARG;
     if (p->nlevels < 1 || p->nlevels > 16) return PLVI_E_BADARG;
     if (n_frames == 0) return PLVI_OK;
-    return launch_matcher<search_local_kernel>(n_frames, local_smem(cap, mp_cap), stream, *p, d_kps, d_desc, d_n, cap,
-                                               d_blocked, d_uright, d_cell_off, d_cell_idx, d_mp_flags, d_mp_proj,
-                                               d_mp_level, d_mp_desc, d_mp_n, mp_cap, d_match, d_nmatches);
+    return launch_lds<search_local_kernel>(
+        dim3(n_frames), dim3(256), local_smem(cap, mp_cap), (hipStream_t)stream, *p, d_kps, d_desc, d_n, cap,
+        d_blocked, d_uright, d_cell_off, d_cell_idx, d_mp_flags, d_mp_proj, d_mp_level, d_mp_desc, d_mp_n, mp_cap,
+        d_match, d_nmatches);
 }
 
 // One frame from host memory, synchronous (grid built on the device).
@@ -1032,11 +996,11 @@ extern "C" int plvi_search_local_stereo_batch(
         return PLVI_E_BADARG;
     if (p->nlevels < 1 || p->nlevels > 16) return PLVI_E_BADARG;
     if (n_frames == 0) return PLVI_OK;
-    return launch_matcher<search_local2_kernel>(n_frames, local2_smem(cap, cap_r, mp_cap), stream, *p, d_kps, d_desc,
-                                                d_n, cap, d_blocked, d_l2r, d_cell_off, d_cell_idx, d_kps_r, d_desc_r,
-                                                d_n_r, cap_r, d_blocked_r, d_r2l, d_cell_off_r, d_cell_idx_r,
-                                                d_mp_flags, d_mp_proj, d_mp_level, d_mp_proj_r, d_mp_level_r, d_mp_desc,
-                                                d_mp_n, mp_cap, d_match, d_match_r, d_nmatches);
+    return launch_lds<search_local2_kernel>(
+        dim3(n_frames), dim3(256), local2_smem(cap, cap_r, mp_cap), (hipStream_t)stream, *p, d_kps, d_desc, d_n, cap,
+        d_blocked, d_l2r, d_cell_off, d_cell_idx, d_kps_r, d_desc_r, d_n_r, cap_r, d_blocked_r, d_r2l, d_cell_off_r,
+        d_cell_idx_r, d_mp_flags, d_mp_proj, d_mp_level, d_mp_proj_r, d_mp_level_r, d_mp_desc, d_mp_n, mp_cap,
+        d_match, d_match_r, d_nmatches);
 }
 
 // One two-camera frame from host memory, synchronous (both grids built on the device).
@@ -1090,12 +1054,11 @@ extern "C" int plvi_search_by_projection_stereo_batch(
     if (n_pairs == 0) return PLVI_OK;
     CamModel cm{0, 0.f, 0.f, 0.f, 0.f};
     if (kb8) cm = CamModel{1, kb8[0], kb8[1], kb8[2], kb8[3]};
-    return launch_matcher<search_by_projection2_kernel>(n_pairs, proj2_smem(cap, cap_r, last_cap), stream, *p, cm,
-                                                        d_kps, d_desc, d_n, cap, d_blocked, d_cell_off, d_cell_idx,
-                                                        d_kps_r, d_desc_r, d_n_r, cap_r, d_blocked_r, d_cell_off_r,
-                                                        d_cell_idx_r, d_x3dc, d_x3dr, d_last_octave, d_last_angle,
-                                                        d_mp_desc, d_last_flags, d_last_n, last_cap, d_match, d_match_r,
-                                                        d_nmatches);
+    return launch_lds<search_by_projection2_kernel>(
+        dim3(n_pairs), dim3(256), proj2_smem(cap, cap_r, last_cap), (hipStream_t)stream, *p, cm, d_kps, d_desc, d_n,
+        cap, d_blocked, d_cell_off, d_cell_idx, d_kps_r, d_desc_r, d_n_r, cap_r, d_blocked_r, d_cell_off_r,
+        d_cell_idx_r, d_x3dc, d_x3dr, d_last_octave, d_last_angle, d_mp_desc, d_last_flags, d_last_n, last_cap,
+        d_match, d_match_r, d_nmatches);
 }
 
 // One pair from host memory, synchronous (both grids built on the device).

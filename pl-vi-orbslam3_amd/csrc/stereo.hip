@@ -28,6 +28,7 @@
 #include <cmath>
 #include <vector>
 
+#include "block_prims.h"
 #include "host_stage.h"
 #include "plvi_common.h"
 #include "plvi_math.h"
@@ -53,42 +54,6 @@ struct StereoPrm {
     int nlevels, rowCap;
     float scale[16], inv[16];
 };
-
-__device__ __forceinline__ int hamming32(const uint4* a, const uint4* b) {
-    const uint4 a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-// Exclusive scan of s[0..n) in place over the 256-thread block; returns the total.
-__device__ int block_scan_excl(int* s, int n, int* s_tmp) {
-    const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int per = (n + kStThreads - 1) / kStThreads, b0 = min(n, t * per), b1 = min(n, b0 + per);
-    int local = 0;
-    for (int i = b0; i < b1; ++i) local += s[i];
-    int x = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) s_tmp[wv] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kStThreads / 64; ++w) {
-        base += w < wv ? s_tmp[w] : 0;
-        tot += s_tmp[w];
-    }
-    int run = base + x - local;
-    for (int i = b0; i < b1; ++i) {
-        const int v = s[i];
-        s[i] = run;
-        run += v;
-    }
-    __syncthreads();
-    return tot;
-}
 
 // ---------------------------------------------------------------------------
 // Frame::ComputeStereoMatches (src/Frame.cc:1228-1406)
@@ -133,7 +98,7 @@ __global__ __launch_bounds__(kStThreads) void stereo_orb_kernel(
         for (int yi = minr; yi <= maxr; ++yi) atomicAdd(&s_row[yi], 1);
     }
     __syncthreads();
-    const int total = block_scan_excl(s_row, nRows + 1, s_tmp);
+    const int total = block_scan_array<kStThreads>(s_row, nRows + 1, s_tmp);
     // never taken: a band holds at most ceil(4*scale) + 2 rows and rowCap allows ceil(4*scale_top) + 3 each
     if (total > prm.rowCap) s_fail = 1;
     __syncthreads();
@@ -174,8 +139,7 @@ __global__ __launch_bounds__(kStThreads) void stereo_orb_kernel(
             if (uR >= minU && uR <= maxU) {
                 const uint4* qr = reinterpret_cast<const uint4*>(DR + (size_t)iR * 32);
                 const uint4 r0 = qr[0], r1 = qr[1];
-                const int d = __popc(q0.x ^ r0.x) + __popc(q0.y ^ r0.y) + __popc(q0.z ^ r0.z) + __popc(q0.w ^ r0.w) +
-                              __popc(q1.x ^ r1.x) + __popc(q1.y ^ r1.y) + __popc(q1.z ^ r1.z) + __popc(q1.w ^ r1.w);
+                const int d = hamming256(q0, q1, r0, r1);
                 const unsigned key = ((unsigned)d << 16) | (unsigned)iR;
                 best = key < best ? key : best;
             }
@@ -318,7 +282,7 @@ __global__ __launch_bounds__(kStThreads) void stereo_orb_kernel(
         uright[(size_t)f * capL + i] = ur;
         depth[(size_t)f * capL + i] = dp;
     }
-    for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);
+    kept = wave_sum(kept);
     if (lane == 0) s_tmp[wv] = kept;
     __syncthreads();
     if (t == 0) nstereo[f] = s_tmp[0] + s_tmp[1] + s_tmp[2] + s_tmp[3];
@@ -383,7 +347,7 @@ __global__ __launch_bounds__(kStThreads) void stereo_line_grid_kernel(
                      });
     }
     __syncthreads();
-    const int total = block_scan_excl(s_cnt, kLGridCells + 1, s_tmp);
+    const int total = block_scan_array<kStThreads>(s_cnt, kLGridCells + 1, s_tmp);
     const bool over = total > idxCap;
     for (int i = t; i <= kLGridCells; i += kStThreads) co[i] = over ? 0 : s_cnt[i];
     if (over) {

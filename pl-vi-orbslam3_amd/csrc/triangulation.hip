@@ -61,8 +61,6 @@ __device__ __forceinline__ TriLds tri_carve(unsigned char* q, int cap2, int node
 
 size_t tri_smem(int cap2, int node_cap) { return (size_t)52 * cap2 + (size_t)16 * node_cap + 8; }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 }  // namespace
 
 __global__ __launch_bounds__(256) void tri_fill_kernel(const int* __restrict__ n1_all, int cap1,
@@ -168,8 +166,7 @@ __global__ __launch_bounds__(kTriThreads) void tri_match_kernel(
             const int tag = s.idx[b];
             if (tag == kTriSkip) continue;
             const uint4 t0 = s.desc[2 * b], t1 = s.desc[2 * b + 1];
-            const int dist = __popc(q0.x ^ t0.x) + __popc(q0.y ^ t0.y) + __popc(q0.z ^ t0.z) + __popc(q0.w ^ t0.w) +
-                             __popc(q1.x ^ t1.x) + __popc(q1.y ^ t1.y) + __popc(q1.z ^ t1.z) + __popc(q1.w ^ t1.w);
+            const int dist = hamming256(q0, q1, t0, t1);
             if (dist > bestDist) continue;  // dist > TH_LOW || dist > bestDist (:1080), bestDist <= TH_LOW
             const float4 g = s.geo[b];
             if (!stereo1 && !(tag & kTriStereoBit)) {  // (:1089-1097)
@@ -254,19 +251,18 @@ extern "C" int plvi_search_for_triangulation_batch(
         !d_has_point2 || !d_uright2 || !d_matches12 || !d_nmatches)
         return PLVI_E_BADARG;
     const size_t smem = tri_smem(cap2, node_cap);
-    if (!lds_fits<tri_match_kernel>(smem)) return PLVI_E_CAPACITY;
-    PLVI_CHECK(hipFuncSetAttribute((const void*)tri_match_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)smem));
+    if (!lds_fits<tri_match_kernel>(smem)) return PLVI_E_CAPACITY;  // before tri_fill_kernel is enqueued
     const hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(tri_fill_kernel, dim3(n_pairs, (cap1 + 255) / 256), dim3(256), 0, st, d_n1, cap1, d_matches12);
     // slices of KF1's list per pair: enough workgroups to cover the chip when
     // the batch alone does not, never more than the list has 512-thread strides
     const int strides = (cap1 + kTriThreads - 1) / kTriThreads;
     const int slices = std::max(1, std::min(strides, (512 + n_pairs - 1) / n_pairs));
-    hipLaunchKernelGGL(tri_match_kernel, dim3(n_pairs, slices), dim3(kTriThreads), smem, st, d_pairs, cap1, cap2,
-                       node_cap, d_kps1, d_desc1, d_n1, d_node1, d_off1, d_nnodes1, d_idx1, d_has_point1, d_uright1,
-                       d_kps2, d_desc2, d_n2, d_node2, d_off2, d_nnodes2, d_idx2, d_has_point2, d_uright2,
-                       d_matches12);
+    if (int rc = launch_lds<tri_match_kernel>(dim3(n_pairs, slices), dim3(kTriThreads), smem, st, d_pairs, cap1, cap2,
+                                              node_cap, d_kps1, d_desc1, d_n1, d_node1, d_off1, d_nnodes1, d_idx1,
+                                              d_has_point1, d_uright1, d_kps2, d_desc2, d_n2, d_node2, d_off2,
+                                              d_nnodes2, d_idx2, d_has_point2, d_uright2, d_matches12))
+        return rc;
     hipLaunchKernelGGL(tri_finish_kernel, dim3(n_pairs), dim3(256), 0, st, d_pairs, cap1, cap2, d_kps1, d_n1, d_kps2,
                        d_matches12, d_nmatches);
     PLVI_CHECK(hipGetLastError());

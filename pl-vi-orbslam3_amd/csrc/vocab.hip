@@ -30,6 +30,7 @@
 #include <memory>
 #include <vector>
 
+#include "block_prims.h"
 #include "host_stage.h"
 #include "plvi_common.h"
 
@@ -47,51 +48,6 @@ constexpr int kBowThreads = 256;
 constexpr int kDescentGroup = 16;
 constexpr int kMaxDepth = 64;
 
-__device__ __forceinline__ int popc256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-// Exclusive scan of one int per thread over the 256-thread block.
-__device__ int block_excl_scan(int v, int* s_tmp, int* total) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) s_tmp[wv] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kBowThreads / 64; ++w) {
-        const int t = s_tmp[w];
-        base += w < wv ? t : 0;
-        tot += t;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
-
-__device__ void bitonic_sort_u64(unsigned long long* a, int P) {
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < P / 2; t += kBowThreads) {
-                const int i = (t / j) * 2 * j + (t % j), ixj = i + j;
-                const bool asc = (i & k) == 0;
-                const unsigned long long x = a[i], y = a[ixj];
-                if ((x > y) == asc) {
-                    a[i] = y;
-                    a[ixj] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
 // Group runs of equal (key >> 32) among the first m sorted keys: returns the
 // number of runs, s_head[r] = index of run r's first key, s_head[runs] = m.
 __device__ int runs_of(const unsigned long long* key, int m, int P, int* s_head, int* s_tmp) {
@@ -100,7 +56,7 @@ __device__ int runs_of(const unsigned long long* key, int m, int P, int* s_head,
     for (int j = j0; j < j0 + E; ++j)
         c += j < m && (j == 0 || (key[j] >> 32) != (key[j - 1] >> 32));
     int total;
-    int pos = block_excl_scan(c, s_tmp, &total);
+    int pos = block_scan<kBowThreads / kWave>(c, s_tmp, threadIdx.x, &total);
     for (int j = j0; j < j0 + E; ++j)
         if (j < m && (j == 0 || (key[j] >> 32) != (key[j - 1] >> 32))) s_head[pos++] = j;
     if (threadIdx.x == 0) s_head[total] = m;
@@ -158,7 +114,7 @@ __global__ __launch_bounds__(kBowThreads) void bow_transform_kernel(
                     if (j < nc) {
                         const uint4* d = V.desc + 2 * (size_t)(c0 + j);
                         r = V.range[c0 + j];
-                        key = ((unsigned)popc256(q0, q1, d[0], d[1]) << 16) | (unsigned)j;
+                        key = ((unsigned)hamming256(q0, q1, d[0], d[1]) << 16) | (unsigned)j;
                     }
                     unsigned k = key;
 #pragma unroll
@@ -198,8 +154,8 @@ __global__ __launch_bounds__(kBowThreads) void bow_transform_kernel(
         cm += live;
     }
     int m;
-    (void)block_excl_scan(cm, s_tmp, &m);
-    bitonic_sort_u64(s_key, P);
+    (void)block_scan<kBowThreads / kWave>(cm, s_tmp, tid, &m);  // its barriers complete s_key too
+    bitonic_sort<kBowThreads>(s_key, P, tid);
     const int nb = runs_of(s_key, m, P, s_head, s_tmp);
     for (int r = tid; r < nb; r += kBowThreads) {
         const int j = s_head[r], c = s_head[r + 1] - j;
@@ -240,7 +196,7 @@ __global__ __launch_bounds__(kBowThreads) void bow_transform_kernel(
         s_key[j] = live ? ((unsigned long long)s_nid[j] << 32) | (unsigned)j : ~0ull;
     }
     __syncthreads();
-    bitonic_sort_u64(s_key, P);
+    bitonic_sort<kBowThreads>(s_key, P, tid);
     const int nf = runs_of(s_key, m, P, s_head, s_tmp);
     int* FO = fv_off + (size_t)f * (cap + 1);
     for (int r = tid; r <= nf; r += kBowThreads) {
@@ -251,11 +207,6 @@ __global__ __launch_bounds__(kBowThreads) void bow_transform_kernel(
     if (tid == 0) fv_n[f] = nf;
 }
 
-static int bow_pow2(int cap) {
-    int P = kBowThreads;
-    while (P < cap) P <<= 1;
-    return P;
-}
 static size_t bow_smem(int P) { return (size_t)P * (8 + 8 + 8 + 4 + 4 + 4) + 16; }
 
 // ---------------------------------------------------------------------------
@@ -508,17 +459,13 @@ extern "C" int plvi_vocab_transform_batch(plvi_vocabulary* h, const uint8_t* d_d
         PLVI_CHECK(hipMemsetAsync(d_fv_off, 0, sizeof(int) * (size_t)n_frames * (cap + 1), st));
         return PLVI_OK;
     }
-    const int P = bow_pow2(cap);
+    const int P = pow2_at_least(cap, kBowThreads);
     const size_t smem = bow_smem(P);
-    if (!lds_fits<bow_transform_kernel>(smem)) return PLVI_E_CAPACITY;
-    PLVI_CHECK(hipFuncSetAttribute((const void*)bow_transform_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)smem));
     const int must = v.scoring != 5, l2 = v.scoring == 1, tf = v.weighting == 0 || v.weighting == 1;
-    hipLaunchKernelGGL(bow_transform_kernel, dim3(n_frames), dim3(kBowThreads), smem, st, v.dev(), v.L, levelsup,
-                       must, l2, tf, d_desc, d_count, cap, P, d_bow_word, d_bow_value, d_bow_n, d_fv_node, d_fv_off,
-                       d_fv_idx, d_fv_n, d_feat_word, d_feat_nid, v.err.as<int>());
-    PLVI_CHECK(hipGetLastError());
-    return PLVI_OK;
+    return launch_lds<bow_transform_kernel>(dim3(n_frames), dim3(kBowThreads), smem, st, v.dev(), v.L, levelsup, must,
+                                            l2, tf, d_desc, d_count, cap, P, d_bow_word, d_bow_value, d_bow_n,
+                                            d_fv_node, d_fv_off, d_fv_idx, d_fv_n, d_feat_word, d_feat_nid,
+                                            v.err.as<int>());
 }
 
 // transform(features, BowVector&, FeatureVector&, levelsup) for one frame
