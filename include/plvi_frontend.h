@@ -279,7 +279,8 @@ int plvi_lines_kernel_timing_read(plvi_line_extractor* h, float* total_ms, int* 
 /* The same timing per kernel kind: 0 = lsd_prep_kernel, 1 = lbd_sobel0_kernel
  * (octave-0 5x5 blur + Sobel), 2 = lbd_sobel1_kernel (pyrDown + Sobel),
  * 3 = lsd_rect_lanes_kernel (region2rect; one launch for all octaves, or one
- * per stream where octave 0 grows beside the others). */
+ * per stream where octave 0 grows beside the others), 4 = lbd_describe_kernel
+ * (one launch per batch). */
 int plvi_lines_kernel_timing_read_kind(plvi_line_extractor* h, int kind, float* total_ms, int* launches);
 
 /* ------------------------------------------------------------------ Hamming

@@ -1457,170 +1457,252 @@ __global__ __launch_bounds__(64) void lbd_sobel1_kernel(const uint8_t* __restric
 
 // ---------------------------------------------------------------------------
 // LB3: BinaryDescriptor::computeLBD (binary_descriptor_custom.cpp:1073-1342)
-// + binaryConversion (:402-414, :663-667).  One wave per keyline: lane h
-// walks support-region row h (63 rows) with the reference's sequential
-// float stepping; lane 0 then accumulates the bands in row order and
-// normalises.  Gaussian coefficient tables come from the host (double exp,
-// cast to float at use, :1189/:1203).
+// + binaryConversion (:402-414, :663-667).  One wave per keyline, kLbdWaves
+// independent waves per workgroup, each taking the lines li, li + stride, ...
+// of one frame (the next line's record is loaded while the current one is
+// described).  Lane h walks support-region row h (63 rows) with the
+// reference's sequential float stepping; lanes (band, k) then accumulate the
+// band sums in row order, and the normalisation sums run in index order.
+// Gaussian coefficient tables come from the host (double exp, cast to float
+// at use, :1189/:1203).  The waves of a workgroup share nothing: every
+// synchronisation below is wave-local.
 // ---------------------------------------------------------------------------
 __constant__ float c_gaussG[63];
 __constant__ float c_gaussL[21];
+__constant__ float c_gaussLL[21];  // c_gaussL[i] * c_gaussL[i], the float product
 __constant__ unsigned char c_comb[64];
 
-__global__ __launch_bounds__(64) void lbd_describe_kernel(const LineOctDev* __restrict__ octs,
-                                                          const short2* __restrict__ g_all,
-                                                          const plvi_keyline* __restrict__ kls,
-                                                          const int* __restrict__ counts, int fcap,
-                                                          uint8_t* __restrict__ desc) {
-    __shared__ float rq[8][64];
-    __shared__ float bs[72];
-    __shared__ float dv[72];
-    const int li = blockIdx.x, f = blockIdx.y;
-    if (li >= counts[f]) return;  // li < fcap by the launch grid: the count needs no clamp
-    const plvi_keyline kl = kls[(size_t)f * fcap + li];
-    const LineOctDev& od = octs[kl.octave];
-    const short2* pg = g_all + od.loff + (size_t)f * od.lplane;  // (dx, dy) interleaved
-    const short realWidth = (short)od.lw;
-    const short imageWidth = realWidth - 1;
-    const short imageHeight = (short)(od.lh - 1);
-    const short lengthOfLSP = (short)kl.numOfPixels;
-    const short halfWidth = (lengthOfLSP - 1) / 2;
-    const short halfHeight = (63 - 1) / 2;
-    const float mX = (float)(0.5 * (double)(kl.sPointInOctaveX + kl.ePointInOctaveX));
-    const float mY = (float)(0.5 * (double)(kl.sPointInOctaveY + kl.ePointInOctaveY));
-    const float dL0 = plvi_cosf(kl.angle), dL1 = plvi_sinf(kl.angle);
-    const float dO0 = -dL1, dO1 = dL0;
-    const int h = threadIdx.x;
-    float pL = 0, nL = 0, pO = 0, nO = 0;
-    // The coordinates are walked per row lane (reference order), but the
-    // gathers are transposed through LDS: one gather instruction then covers
-    // 8 rows x 8 consecutive samples instead of 64 rows at one sample, so its
-    // lanes share cache lines (samples along a row are 1 px apart) and the
-    // vector-memory path is not one cache line per lane
-    // one array: each (row, sample) slot's index is read and its gathered
-    // value written back by the same lane, and row lane h writes / reads only
-    // its own row
-    __shared__ int sidx[64][9];
-    auto& sg = sidx;
-    {
+constexpr int kLbdWaves = 4;                 // waves (lines in flight) per workgroup
+constexpr int kLbdLinesPerWave = 4;          // lines a wave takes in a large batch ...
+constexpr int kLbdSlotsPerLine = 65536;      // ... one more per 8 x the chip's 8192 resident waves of line slots
+constexpr int kLbdChunk = 16;                // samples per row and gather step
+constexpr int kLbdTileStride = kLbdChunk + 1;
+constexpr int kLbdBandRows = 7 + 63 + 7;     // scaled row sums with 7 zero rows either side
+
+struct LbdWaveLds {
+    // the sample tile and, after the sample loop, the row sums rq[row + 7][8]
+    union {
+        int tile[64 * kLbdTileStride];
+        float rq[kLbdBandRows * 8];
+    };
+    alignas(16) float dv[72];
+    alignas(16) float sq[72];
+};
+static_assert(sizeof(plvi_keyline) == 17 * sizeof(int), "keyline record: one dword per lane 0..16");
+static_assert(kLbdBandRows * 8 <= 64 * kLbdTileStride, "row sums alias the sample tile");
+
+// wave-local ordering of LDS traffic between lanes (the wave runs in lockstep)
+__device__ __forceinline__ void lbd_wave_sync() {
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// lane h takes `next` of lane h - 1 (DPP wave_shr:1); lane 0 keeps `own`
+__device__ __forceinline__ float lbd_from_lane_below(float own, float next) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, own), __builtin_bit_cast(int, next),
+                                                                 0x138, 0xf, 0xf, false));
+}
+
+// 8 waves per SIMD (<= 64 VGPRs): the gathers' latency is hidden by the other waves
+__global__ __launch_bounds__(64 * kLbdWaves) __attribute__((amdgpu_waves_per_eu(8, 8))) void lbd_describe_kernel(
+    const LineOctDev* __restrict__ octs, int nOct, const short2* __restrict__ g_all, const plvi_keyline* __restrict__ kls,
+    const int* __restrict__ counts, int fcap, uint8_t* __restrict__ desc) {
+    __shared__ LbdWaveLds lds[kLbdWaves];
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int h = threadIdx.x & 63;
+    const int f = blockIdx.y;
+    const int cnt = min(counts[f], fcap);
+    const int stride = gridDim.x * kLbdWaves;
+    int li = blockIdx.x * kLbdWaves + wv;
+    if (li >= cnt) return;
+    LbdWaveLds& L = lds[wv];
+    // per-wave constants, off every line's chain
+    const float cG = c_gaussG[min(h, 62)];
+    // band coefficient t and its square live in lane t (read back as scalars)
+    const int cLv = __builtin_bit_cast(int, c_gaussL[min(h, 20)]), cLLv = __builtin_bit_cast(int, c_gaussLL[min(h, 20)]);
+    const int combA = 8 * c_comb[(2 * h) & 63], combB = 8 * c_comb[(2 * h + 1) & 63];
+    const LineOctDev& o0 = octs[0];
+    const LineOctDev& o1 = octs[nOct > 1 ? 1 : 0];
+    const int lw0 = o0.lw, lh0 = o0.lh, lw1 = o1.lw, lh1 = o1.lh;
+    const long long loff0 = o0.loff, lpl0 = o0.lplane, loff1 = o1.loff, lpl1 = o1.lplane;
+    // keyline record: lane j < 17 holds dword j
+    const int* recs = reinterpret_cast<const int*>(kls + (size_t)f * fcap);
+    const unsigned recLane = h < 17 ? h : 0;
+    int rec = recs[(unsigned)li * 17u + recLane];
+    // band lanes: lane (b, k) owns the band sums of quantities qs (linear) and qs + 2 (squared)
+    const int bb = h >> 2, bk = h & 3;
+    const int bqs = (bk < 2 ? 0 : 4) + (bk & 1);
+    const float invN = (bb == 0 || bb == 8) ? (float)(1.0 / (7 * 2.0)) : (float)(1.0 / (7 * 3.0));
+    const int kk = h & 7, rr = h >> 3;  // gather lanes: 8 rows x 8 consecutive samples per instruction
+    for (;;) {
+        const float angle = __builtin_bit_cast(float, __builtin_amdgcn_readlane(rec, 0));
+        const int octave = __builtin_amdgcn_readlane(rec, 2);
+        const float sPX = __builtin_bit_cast(float, __builtin_amdgcn_readlane(rec, 11));
+        const float sPY = __builtin_bit_cast(float, __builtin_amdgcn_readlane(rec, 12));
+        const float ePX = __builtin_bit_cast(float, __builtin_amdgcn_readlane(rec, 13));
+        const float ePY = __builtin_bit_cast(float, __builtin_amdgcn_readlane(rec, 14));
+        const int numOfPixels = __builtin_amdgcn_readlane(rec, 16);
+        const int liNext = li + stride;
+        // the next record rides in front of this line's gathers
+        rec = recs[(unsigned)min(liNext, fcap - 1) * 17u + recLane];
+        const bool oc1 = octave != 0;  // octave < nOct <= kLineMaxOct = 2
+        const char* pgb = reinterpret_cast<const char*>(g_all + (oc1 ? loff1 : loff0) + (size_t)f * (oc1 ? lpl1 : lpl0));
+        const short realWidth = (short)(oc1 ? lw1 : lw0);
+        const short imageWidth = realWidth - 1;
+        const short imageHeight = (short)((oc1 ? lh1 : lh0) - 1);
+        const short lengthOfLSP = (short)numOfPixels;
+        const short halfWidth = (lengthOfLSP - 1) / 2;
+        const short halfHeight = (63 - 1) / 2;
+        const float mX = (float)(0.5 * (double)(sPX + ePX));
+        const float mY = (float)(0.5 * (double)(sPY + ePY));
+        const float dL0 = plvi_cosf(angle), dL1 = plvi_sinf(angle);
+        const float dO0 = -dL1, dO1 = dL0;
+        float pL = 0, nL = 0, pO = 0, nO = 0;
+        // The coordinates are walked per row lane (reference order), but the
+        // gathers are transposed through LDS: one gather instruction then covers
+        // 8 rows x 8 consecutive samples instead of 64 rows at one sample, so its
+        // lanes share cache lines (samples along a row are 1 px apart).  Each
+        // (row, sample) slot's byte offset is read and its gathered value written
+        // back by the same gather lane; row lane h writes / reads only its own
+        // row.  Every offset is clamped into the plane, so the gathers need no
+        // branch: a sample past the line's end is loaded and replaced by (0, 0),
+        // which adds +-0 to sums that start at +0 and never go negative.  Lane 63
+        // walks a row that does not exist; its sums are dropped below.
         float sX = -dL0 * halfWidth + dL1 * halfHeight + mX;
         float sY = -dL1 * halfWidth - dL0 * halfHeight + mY;
-        for (int k = 0; k < h; ++k) {
-            sX -= dL1;
-            sY += dL0;
-        }
-        const int* pgi = reinterpret_cast<const int*>(pg);
-        const int kk = h & 7, rr = h >> 3;
-        for (int w0 = 0; w0 < lengthOfLSP; w0 += 8) {  // lengthOfLSP is wave-uniform
+        // row h starts h sequential steps across (the reference's row loop): every
+        // lane steps, then takes its lower neighbour's result; lane 0 keeps its
+        // own, so after step s lanes 0..s hold their final start
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                short t = (short)__builtin_roundf(sX);
-                const short xc = (t < 0) ? 0 : (t > imageWidth) ? imageWidth : t;
-                t = (short)__builtin_roundf(sY);
-                const short yc = (t < 0) ? 0 : (t > imageHeight) ? imageHeight : t;
-                sidx[h][k] = yc * realWidth + xc;
+        for (int k = 0; k < 62; ++k) {
+            sX = lbd_from_lane_below(sX, sX - dL1);
+            sY = lbd_from_lane_below(sY, sY + dL0);
+        }
+        int* trow = L.tile + h * kLbdTileStride;
+        for (int w0 = 0; w0 < lengthOfLSP; w0 += kLbdChunk) {  // lengthOfLSP is wave-uniform
+#pragma unroll
+            for (int k = 0; k < kLbdChunk; ++k) {
+                const int xc = plvi_round_clamp_i16(sX, imageWidth);
+                const int yc = plvi_round_clamp_i16(sY, imageHeight);
+                trow[k] = (yc * realWidth + xc) * 4;
                 sX += dL0;
                 sY += dL1;
+                // a few samples at a time: interleaving all 16 chains buys nothing on
+                // this in-order VALU and costs the registers that keep 8 waves per SIMD
+                if ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);
             }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            int gv[8];
-            const bool okk = w0 + kk < lengthOfLSP;
+            lbd_wave_sync();
+            int gv[2 * 8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int r = 8 * i + rr;
-                gv[i] = (r < 63 && okk) ? pgi[sidx[r][kk]] : 0;
+            for (int i = 0; i < 2 * 8; ++i) {
+                const int r = 8 * (i >> 1) + rr, k = kk + 8 * (i & 1);
+                gv[i] = *reinterpret_cast<const int*>(pgb + (unsigned)L.tile[r * kLbdTileStride + k]);
             }
+            const bool ok0 = w0 + kk < lengthOfLSP, ok1 = w0 + kk + 8 < lengthOfLSP;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) sg[8 * i + rr][kk] = gv[i];
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            if (h < 63) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (w0 + k >= lengthOfLSP) break;
-                    const short2 g = __builtin_bit_cast(short2, sg[h][k]);
-                    const short dx = g.x, dy = g.y;
-                    const float gDL = dx * dL0 + dy * dL1;
-                    const float gDO = dx * dO0 + dy * dO1;
-                    if (gDL > 0) pL += gDL;
-                    else nL -= gDL;
-                    if (gDO > 0) pO += gDO;
-                    else nO -= gDO;
-                }
+            for (int i = 0; i < 2 * 8; ++i) {
+                const int r = 8 * (i >> 1) + rr, k = kk + 8 * (i & 1);
+                L.tile[r * kLbdTileStride + k] = ((i & 1) ? ok1 : ok0) ? gv[i] : 0;
             }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            lbd_wave_sync();
+#pragma unroll
+            for (int k = 0; k < kLbdChunk; ++k) {
+                const short2 g = __builtin_bit_cast(short2, trow[k]);
+                const short dx = g.x, dy = g.y;
+                const float gDL = dx * dL0 + dy * dL1;
+                const float gDO = dx * dO0 + dy * dO1;
+                // the reference's `if (g > 0) p += g; else n -= g;`: adding +-0 to
+                // the other sum leaves it unchanged (both are >= +0, g is finite)
+                pL += __builtin_fmaxf(gDL, 0.f);
+                nL += __builtin_fmaxf(-gDL, 0.f);
+                pO += __builtin_fmaxf(gDO, 0.f);
+                nO += __builtin_fmaxf(-gDO, 0.f);
+                if ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+            }
+            lbd_wave_sync();
         }
-    }
-    // row sums scaled by gaussCoefG_ (:1189-1197), per row lane
-    if (h < 63) {
-        const float c = c_gaussG[h];
-        const float pLr = c * pL, nLr = c * nL, pOr = c * pO, nOr = c * nO;
-        rq[0][h] = pLr; rq[1][h] = nLr; rq[2][h] = pLr * pLr; rq[3][h] = nLr * nLr;
-        rq[4][h] = pOr; rq[5][h] = nOr; rq[6][h] = pOr * pOr; rq[7][h] = nOr * nOr;
-    }
-    __syncthreads();
-    // band sums (:1202-1241): accumulator (band b, quantity q) takes the rows of
-    // bands b-1, b, b+1 in row order, exactly the reference's += sequence for it
-    for (int a = h; a < 72; a += 64) {
-        const int b = a >> 3, q = a & 7;
-        const bool sq = (q & 2) != 0;
-        float acc = 0.f;
-        const int r0 = max(0, 7 * (b - 1)), r1 = min(62, 7 * (b + 2) - 1);
-        for (int r = r0; r <= r1; ++r) {
-            const int j = r / 7, m = r - 7 * j;
-            const float c = j == b ? c_gaussL[m + 7] : j == b + 1 ? c_gaussL[m + 14] : c_gaussL[m];
-            const float x = rq[q][r];
-            acc += sq ? c * c * x : c * x;
+        // row sums scaled by gaussCoefG_ (:1189-1197), per row lane, at rq[h + 7][0..7]
+        if (h < 56) {  // rows -7..-1 and 63..69: zeros, so every band lane runs the same 21 steps
+            L.rq[h] = 0.f;
+            L.rq[(63 + 7) * 8 + h] = 0.f;
         }
-        bs[a] = acc;
-    }
-    __syncthreads();
-    if (h < 36) {  // mean / std per band (:1254-1281)
-        const int b = h >> 2, k = h & 3;
-        const int qs = (k < 2 ? 0 : 4) + (k & 1);
-        const float invN = (b == 0 || b == 8) ? (float)(1.0 / (7 * 2.0)) : (float)(1.0 / (7 * 3.0));
-        const float t = bs[8 * b + qs] * invN;
-        dv[8 * b + k] = t;
-        dv[8 * b + 4 + k] = __builtin_sqrtf(bs[8 * b + qs + 2] * invN - t * t);
-    }
-    __syncthreads();
-    // normalisation (:1283-1330): the three sums stay sequential (lane 0),
-    // the element-wise scaling and the 0.4 clip run on all lanes
-    __shared__ float s_t[3];
-    if (h == 0) {
+        if (h < 63) {
+            const float pLr = cG * pL, nLr = cG * nL, pOr = cG * pO, nOr = cG * nO;
+            float4* q = reinterpret_cast<float4*>(L.rq + (h + 7) * 8);
+            q[0] = make_float4(pLr, nLr, pLr * pLr, nLr * nLr);
+            q[1] = make_float4(pOr, nOr, pOr * pOr, nOr * nOr);
+        }
+        lbd_wave_sync();
+        // band sums (:1202-1241): band b takes rows 7(b-1) + t, t = 0..20, of bands
+        // b-1, b, b+1 with coefficient c_gaussL[t], in row order -- exactly the
+        // reference's += sequence per accumulator (a zero row adds c * 0 = +0 to a
+        // sum that is >= +0).  Then mean / std per band (:1254-1281).
+        float m, sd;
+        {
+            float accL = 0.f, accS = 0.f;
+            const float* x = L.rq + 56 * bb + bqs;  // rq[7(b-1) + 7][qs]
+#pragma unroll
+            for (int t = 0; t < 21; ++t) {
+                const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(cLv, t));
+                const float cc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(cLLv, t));
+                accL += c * x[8 * t];
+                accS += cc * x[8 * t + 2];
+            }
+            m = accL * invN;
+            sd = __builtin_sqrtf(accS * invN - m * m);
+        }
+        // normalisation (:1283-1330): every lane runs the three sums in index
+        // order over the squares its band lanes publish; the element-wise scaling
+        // and the 0.4 clip run on the band lanes
+        const int im = 8 * bb + bk, is = im + 4;
+        lbd_wave_sync();
+        if (h < 36) {
+            L.sq[im] = m * m;
+            L.sq[is] = sd * sd;
+        }
+        lbd_wave_sync();
         float tM = 0, tS = 0;
+#pragma unroll
         for (int b = 0; b < 9; ++b) {
-            const float* v = dv + 8 * b;
-            tM += v[0] * v[0]; tM += v[1] * v[1]; tM += v[2] * v[2]; tM += v[3] * v[3];
-            tS += v[4] * v[4]; tS += v[5] * v[5]; tS += v[6] * v[6]; tS += v[7] * v[7];
+            const float4 vm = *reinterpret_cast<const float4*>(L.sq + 8 * b);
+            const float4 vs = *reinterpret_cast<const float4*>(L.sq + 8 * b + 4);
+            tM += vm.x; tM += vm.y; tM += vm.z; tM += vm.w;
+            tS += vs.x; tS += vs.y; tS += vs.z; tS += vs.w;
         }
-        s_t[0] = 1 / __builtin_sqrtf(tM);
-        s_t[1] = 1 / __builtin_sqrtf(tS);
-    }
-    __syncthreads();
-    for (int i = h; i < 72; i += 64) {
-        float v = dv[i] * ((i & 7) < 4 ? s_t[0] : s_t[1]);
-        if ((double)v > 0.4) v = (float)0.4;
-        dv[i] = v;
-    }
-    __syncthreads();
-    if (h == 0) {
+        m = m * (1 / __builtin_sqrtf(tM));
+        sd = sd * (1 / __builtin_sqrtf(tS));
+        if ((double)m > 0.4) m = (float)0.4;
+        if ((double)sd > 0.4) sd = (float)0.4;
+        lbd_wave_sync();
+        if (h < 36) {
+            L.sq[im] = m * m;
+            L.sq[is] = sd * sd;
+        }
+        lbd_wave_sync();
         float t = 0;
-        for (int i = 0; i < 72; ++i) t += dv[i] * dv[i];
-        s_t[2] = 1 / __builtin_sqrtf(t);
-    }
-    __syncthreads();
-    for (int i = h; i < 72; i += 64) dv[i] = dv[i] * s_t[2];
-    __syncthreads();
-    if (h < 32) {
-        const float* f1 = dv + 8 * c_comb[2 * h];
-        const float* f2 = dv + 8 * c_comb[2 * h + 1];
-        unsigned r = 0;
-        for (int i = 0; i < 8; ++i)
-            if (f1[i] > f2[i]) r += 1u << i;
-        desc[((size_t)f * fcap + li) * 32 + h] = (uint8_t)r;
+#pragma unroll
+        for (int i = 0; i < 72; i += 4) {
+            const float4 v = *reinterpret_cast<const float4*>(L.sq + i);
+            t += v.x; t += v.y; t += v.z; t += v.w;
+        }
+        const float s2 = 1 / __builtin_sqrtf(t);
+        if (h < 36) {
+            L.dv[im] = m * s2;
+            L.dv[is] = sd * s2;
+        }
+        lbd_wave_sync();
+        if (h < 32) {
+            const float* f1 = L.dv + combA;
+            const float* f2 = L.dv + combB;
+            unsigned r = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if (f1[i] > f2[i]) r += 1u << i;
+            (desc + ((size_t)f * fcap + li) * 32)[(unsigned)h] = (uint8_t)r;
+        }
+        li = liNext;
+        if (li >= cnt) break;
+        lbd_wave_sync();  // the next line's tile overwrites rq
     }
 }
 

@@ -102,9 +102,10 @@ struct LinePipeline {
     int kn = 0;
     std::vector<hipEvent_t> kev;
     // and around every LBD Gaussian + Sobel launch ([0] lbd_sobel0_kernel, [1]
-    // lbd_sobel1_kernel) and every region2rect launch ([2] lsd_rect_lanes_kernel)
-    std::vector<hipEvent_t> kevS[3];
-    int knS[3] = {0, 0, 0};
+    // lbd_sobel1_kernel), every region2rect launch ([2] lsd_rect_lanes_kernel)
+    // and every LBD describe launch ([3] lbd_describe_kernel)
+    std::vector<hipEvent_t> kevS[4];
+    int knS[4] = {0, 0, 0, 0};
     int ktiming(int on) {
         if (on && kev.empty()) {
             kev.resize(2 * kKRing);
@@ -115,7 +116,7 @@ struct LinePipeline {
             }
         }
         ktime = on != 0;
-        if (on) kn = knS[0] = knS[1] = knS[2] = 0;
+        if (on) kn = knS[0] = knS[1] = knS[2] = knS[3] = 0;
         return PLVI_OK;
     }
     void ktimeS(int k, int edge, hipStream_t st) {  // edge 0 = before, 1 = after launch k
@@ -125,7 +126,7 @@ struct LinePipeline {
     }
     int ktiming_read_kind(int kind, float* total_ms, int* launches) {
         if (kind == 0) return ktiming_read(total_ms, launches);
-        if (kind < 1 || kind > 3) return PLVI_E_BADARG;
+        if (kind < 1 || kind > 4) return PLVI_E_BADARG;
         const int k = kind - 1;
         float tot = 0.f;
         for (int i = 0; i < knS[k]; ++i) {
@@ -396,7 +397,10 @@ struct LinePipeline {
             static const unsigned char comb[64] = {0, 1, 0, 2, 0, 3, 0, 4, 0, 5, 0, 6, 1, 2, 1, 3, 1, 4, 1, 5, 1, 6,
                                                    2, 3, 2, 4, 2, 5, 2, 6, 2, 7, 2, 8, 3, 4, 3, 5, 3, 6, 3, 7, 3, 8,
                                                    4, 5, 4, 6, 4, 7, 4, 8, 5, 6, 5, 7, 5, 8, 6, 7, 6, 8, 7, 8};
+            float gLL[21];
+            for (int i = 0; i < 21; ++i) gLL[i] = gL[i] * gL[i];
             PLVI_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_gaussL), gL, sizeof(gL)));
+            PLVI_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_gaussLL), gLL, sizeof(gLL)));
             PLVI_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_gaussG), gG, sizeof(gG)));
             PLVI_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_comb), comb, sizeof(comb)));
         }
@@ -659,12 +663,21 @@ struct LinePipeline {
         return PLVI_OK;
     }
 
-    // LB3: LBD descriptors of the assembled keylines.
+    // LB3: LBD descriptors of the assembled keylines.  One line per wave while
+    // the batch's fcap * nf line slots do not fill the chip a few times over
+    // (small batches: a frame's lines spread over as many CUs as before); a
+    // large batch gives every wave kLbdLinesPerWave lines of its frame.  The
+    // grid depends on nf and fcap only.
     void launch_describe(int nf, hipStream_t st) {
-        hipLaunchKernelGGL(lbd_describe_kernel, dim3(fcap, nf), dim3(64), 0, st, d_oct.as<LineOctDev>(),
+        const long long slots = (long long)fcap * nf;
+        const int per = (int)std::min<long long>(kLbdLinesPerWave, std::max<long long>(1, slots / kLbdSlotsPerLine));
+        const int gx = ((fcap + per - 1) / per + kLbdWaves - 1) / kLbdWaves;
+        ktimeS(3, 0, st);
+        hipLaunchKernelGGL(lbd_describe_kernel, dim3(gx, nf), dim3(64 * kLbdWaves), 0, st, d_oct.as<LineOctDev>(), nOct,
                            (const short2*)lbdG.as<short2>(),
                            (const plvi_keyline*)klOut.as<plvi_keyline>(), (const int*)cntOut.as<int>(), fcap,
                            descOut.as<uint8_t>());
+        ktimeS(3, 1, st);
         mark(5, st);
     }
 

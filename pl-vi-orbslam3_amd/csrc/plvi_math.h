@@ -196,6 +196,24 @@ PLVI_HD void plvi_sincosf_pos(float y, float* sp, float* cp) {
     *cp = c;
 }
 
+// ------------------------------------------------------------ LBD sample coordinate
+// The reference's `short t = (short)roundf(v); t < 0 ? 0 : t > hi ? hi : t`
+// (binary_descriptor_custom.cpp:1158-1163, 0 <= hi <= 32767) without the
+// round-half-away expansion and the 16-bit compares: trunc(v), plus one where
+// the (exactly representable) fraction reaches a half.  For v >= 0 that is
+// roundf(v); for v < 0 both forms are <= 0 and clamp to 0; the low 16 bits are
+// then taken as the cast takes them.  Equal to the reference wherever the
+// cast is defined, i.e. roundf(v) in [-32768, 32767] (every float checked,
+// tests/native/lbd_round_check.cpp); a coordinate lies within three image
+// sides of the origin.
+PLVI_HD int plvi_round_clamp_i16(float v, int hi) {
+    const float t = __builtin_truncf(v);
+    int i = (int)t;
+    i += (v - t >= 0.5f) ? 1 : 0;
+    i = (short)i;
+    return i < 0 ? 0 : i > hi ? hi : i;
+}
+
 // ------------------------------------------------------------ fastAtan2
 PLVI_HD float plvi_fast_atan2(float y, float x) {
     const float k = (float)(180 / 3.1415926535897932384626433832795);

@@ -506,7 +506,7 @@ class Lineextractor:
 
     def kernel_timing_read(self, kind=0):
         """(total ms, launches) since kernel_timing(True): kind 0 = lsd_prep_kernel, 1 = lbd_sobel0_kernel,
-        2 = lbd_sobel1_kernel, 3 = lsd_rect_lanes_kernel (region2rect)."""
+        2 = lbd_sobel1_kernel, 3 = lsd_rect_lanes_kernel (region2rect), 4 = lbd_describe_kernel."""
         return _timing_read("plvi_lines_kernel_timing_read_kind", self._h, kind)
 
     def pyramid_level(self, level, frame=0):
