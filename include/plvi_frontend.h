@@ -1957,6 +1957,169 @@ int plvi_keyframe_culling(const plvi_cull_keyframes* kf, const plvi_local_map_po
                           const plvi_local_map_pool* ml, const plvi_cull_features* fml, const plvi_cull_params* params,
                           const plvi_cull_queries* queries, const plvi_cull_outputs* out);
 
+/* ------------------------------------------------------- Local BA window
+ * The set-up of Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap,
+ * num_fixedKF) (src/Optimizer.cc:4851-4960, edge loop :5048-5168),
+ * LocalBundleAdjustmentOnlyLines / ...OnlyLinesAngle / ...OnlyLinesWithAngle
+ * (:6181-6233, :6433-6485, :6689-6741, one text three times; edge loop
+ * :6291-6337, whose condition the two Angle variants share) and
+ * LocalInertialBA (:9185-9307, :9521-9640) for a batch of current keyframes:
+ * the local keyframes, the local features, the fixed cameras and the
+ * (feature, keyframe, index) edge list.  Integers only; every output equals
+ * the reference's.  g2o, the vertex estimates, invSigma2, the inertial edges
+ * and the outlier pass stay with the caller.
+ *
+ * Tables.  The keyframe side is plvi_cull_keyframes, of which mp / nmp / ml /
+ * nml, bad, init_kf, cand / n_cand, kf_id (POINTS), prev_kf (INERTIAL) and bit
+ * 7 of kp_info are read; the pools are plvi_local_map_pool, read for n, bad,
+ * obs_off and obs_kf, with a plvi_ba_features each.  kf_map_id [kf_cap] and
+ * plvi_ba_features.map_id are GetMap() as an integer, NULL = one map:
+ * `GetMap() == pCurrentMap` is map_id == kf_map_id[q_slot].  POINTS and
+ * INERTIAL read mp / fmp, LINES reads kf->ml / ml / fml.  A NULL kp_info
+ * makes every point edge a mono edge.
+ *
+ * The mnBALocalForKF / mnBAFixedForKF stamps are state of one query (each
+ * query is a fresh mnId; mnId == 0 equals the constructors' stamp and is
+ * outside the model), kept as per-slot tables and resolved as "the smallest
+ * traversal position wins".
+ *
+ * Semantics of one query (keyframe q = q_slot, map M = kf_map_id[q]):
+ *   1. Local keyframes, visual modes (:4857-4868): q, then q's cand row in
+ *      order.  Every row entry in [0, kf_cap) is stamped local; it is listed
+ *      iff it is not bad and (POINTS) in map M -- the lines functions have no
+ *      map test (:6195).  q in its own row is listed twice.
+ *   2. Local features (:4874-4896, :6201-6215): the listed keyframes in list
+ *      order, each table in index order; the first occurrence of every id
+ *      that is in range, not bad and (visual modes) in map M.  init_in_local
+ *      = some listed keyframe has init_kf set.
+ *   3. Fixed cameras (:4899-4914): the local features in list order, each
+ *      observation list in CSR order; a keyframe in [0, kf_cap) stamped
+ *      neither local nor fixed is stamped fixed, and listed iff it is not bad
+ *      and in map M.
+ *   4. POINTS only (:4915-4954): num_fixed = n_fixed + init_in_local; below 2
+ *      the selection loop runs over the local list as written -- q and the
+ *      initial keyframe are skipped; mnId < lowerId compares the 64-bit mnId
+ *      with the SIGN-EXTENDED int, unsigned (movslq / cmp / jb in the
+ *      reference's object); the `else if` gives the second candidate only to a
+ *      keyframe that did not take "lowest" -- and pLowerKf, then (still below
+ *      2) pSecondLowerKF, move from the local list (every equal element) to
+ *      the end of the fixed list.  A pointer never assigned moves nothing and
+ *      sets PLVI_BA_ERR_UNDEFINED; num_fixed is incremented all the same.
+ *      The features of 2 are not recomputed.
+ *   5. INERTIAL (:9197-9307): Nd = min(n_kf_in_map - 2, max_opt); the
+ *      optimizable list is q and prev_kf steps while it is shorter than Nd (no
+ *      bad test, no map test), local features from those keyframes as in 2
+ *      WITHOUT the map test (:9229).  If the back's prev_kf exists it is the
+ *      first fixed keyframe; otherwise the back itself is, and is popped from
+ *      the optimizable list (its features stay).  The covisible loop of :9255
+ *      never runs (maxCovKF is 0).  Then, per local feature in order, the
+ *      first observer in CSR order that is in range, unstamped and not bad is
+ *      stamped fixed and listed and the feature's loop breaks (bad unstamped
+ *      observers are stamped and passed); after each feature the walk ends
+ *      once the fixed list holds PLVI_BA_MAX_FIXED_INERTIAL keyframes.
+ *      non_fixed = the fixed list is empty.
+ *   6. Edges: the local features in list order, each observation list in CSR
+ *      order; an observation is an edge iff its keyframe is in range, not bad
+ *      and in map M, (INERTIAL) stamped local or fixed (:9538), and obs_idx is
+ *      inside the keyframe table's row.  Kind: PLVI_BA_EDGE_STEREO where bit 7
+ *      of kp_info[kf][idx] is set, else MONO; LINE in LINES.  vpEdgesMono... are
+ *      the kind-0 subsequence of the merged list, vpEdgesStereo... the kind-1
+ *      one.  edge_feat is the feature's position in local_feat, edge_cam the
+ *      keyframe's first position in local_kf || fixed_kf after the moves of 4
+ *      and the pop of 5; it would be -1 for a keyframe in neither list, which
+ *      no input produces (the argument per mode is in DESIGN.md).  The
+ *      two-camera branches are not modelled.
+ *
+ * Outputs follow the count contract: counts are full lengths, nothing is
+ * written at or past min(count, cap), err[q] has a bit per overflowed list.
+ *
+ * Limits.  n_queries <= 65535 and kf_cap * max(kp_cap, kl_cap) <=
+ * PLVI_LOCAL_MAP_MAX_ENTRIES (PLVI_E_CAPACITY beyond); max_opt <=
+ * PLVI_BA_MAX_OPT (PLVI_E_BADARG beyond).  The per-slot stamp / position
+ * tables are in LDS up to kf_cap = PLVI_BA_LDS_KF and in the scratch block
+ * above.  No other bound on kf_cap, n, cand_stride or the list lengths. */
+#define PLVI_BA_LDS_KF 2048           /* largest kf_cap whose per-slot tables are kept in LDS (24 KB) */
+#define PLVI_BA_MAX_OPT 64            /* largest max_opt */
+#define PLVI_BA_MAX_FIXED_INERTIAL 200 /* maxFixKF of :9284 */
+enum { /* plvi_ba_params.mode */
+  PLVI_BA_POINTS = 0,
+  PLVI_BA_LINES = 1,
+  PLVI_BA_INERTIAL = 2,
+};
+enum { /* edge_kind */
+  PLVI_BA_EDGE_MONO = 0,
+  PLVI_BA_EDGE_STEREO = 1,
+  PLVI_BA_EDGE_LINE = 2,
+};
+enum { /* err[q] */
+  PLVI_BA_ERR_LOCAL_KF = 1,   /* local_kf is longer than lkf_cap */
+  PLVI_BA_ERR_FIXED_KF = 2,   /* fixed_kf is longer than fkf_cap */
+  PLVI_BA_ERR_FEAT = 4,       /* local_feat is longer than feat_cap */
+  PLVI_BA_ERR_EDGE = 8,       /* the edge list is longer than edge_cap */
+  PLVI_BA_ERR_UNDEFINED = 16, /* the reference would push an uninitialised pLowerKf / pSecondLowerKF */
+  PLVI_BA_ERR_QUERY = 32,     /* q_slot outside [0, kf_cap): every count is 0 */
+};
+
+typedef struct plvi_ba_features {
+  const int* obs_idx; /* parallel to obs_kf: get<0> of the tuple for points, the size_t for lines */
+  const int* map_id;  /* [n] GetMap(); NULL = one map */
+} plvi_ba_features;
+
+/* Host struct, read before the call returns. */
+typedef struct plvi_ba_params {
+  int mode;    /* PLVI_BA_* */
+  int max_opt; /* INERTIAL: 10 or 25 as bLarge chooses (:9190-9196) */
+} plvi_ba_params;
+
+typedef struct plvi_ba_queries {
+  const int* q_slot;      /* [q] pKF */
+  const int* n_kf_in_map; /* [q] pCurrentMap->KeyFramesInMap(); INERTIAL only, NULL otherwise */
+} plvi_ba_queries;
+
+typedef struct plvi_ba_outputs {
+  int lkf_cap, fkf_cap, feat_cap, edge_cap;
+  int* local_kf;      /* [q][lkf_cap] lLocalKeyFrames / vpOptimizableKFs as slots */
+  int* n_local_kf;
+  int* fixed_kf;      /* [q][fkf_cap] lFixedCameras / lFixedKeyFrames */
+  int* n_fixed_kf;
+  int* num_fixed;     /* POINTS: num_fixedKF as the reference leaves it; otherwise n_fixed_kf */
+  int* init_in_local;
+  int* non_fixed;     /* n_fixed_kf == 0 (bNonFixed) */
+  int* local_feat;    /* [q][feat_cap] lLocalMapPoints / lLocalMapLines as pool ids */
+  int* n_local_feat;
+  int* edge_feat;     /* [q][edge_cap] position in local_feat */
+  int* edge_kf;       /* [q][edge_cap] slot */
+  int* edge_idx;      /* [q][edge_cap] */
+  int* edge_cam;      /* [q][edge_cap] position in local_kf || fixed_kf, or -1 */
+  uint8_t* edge_kind; /* [q][edge_cap] PLVI_BA_EDGE_* */
+  int* n_mono;        /* the edge list is n_mono + n_stereo + n_line long */
+  int* n_stereo;
+  int* n_line;
+  int* err;           /* PLVI_BA_ERR_* */
+} plvi_ba_outputs;
+
+/* The batch call: one workgroup per query, one launch.  The structs are host
+ * memory, read before the call returns; their pointers are device pointers.
+ * The pool of the mode (mp / fmp, or ml / fml for LINES) is required, the other
+ * may be NULL.  PLVI_E_BADARG for a negative size, an unknown mode or a
+ * missing required pointer; n_queries == 0 returns 0 without a launch.
+ * d_scratch holds at least plvi_ba_window_scratch_bytes(...) bytes, needs no
+ * initialisation, and calls that share it must be ordered.  Asynchronous on
+ * `stream`, no host read of device data, no allocation: capturable. */
+size_t plvi_ba_window_scratch_bytes(int n_queries, int kf_cap, int mp_n, int ml_n);
+int plvi_ba_window_batch(int n_queries, const plvi_cull_keyframes* kf, const int* kf_map_id,
+                         const plvi_local_map_pool* mp, const plvi_ba_features* fmp, const plvi_local_map_pool* ml,
+                         const plvi_ba_features* fml, const plvi_ba_params* params, const plvi_ba_queries* queries,
+                         const plvi_ba_outputs* out, void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* One query from host tables, synchronous: the same structs with host
+ * pointers, per-query arrays of one entry.  Returns 0, PLVI_E_CAPACITY when
+ * err[0] has an overflow bit or PLVI_BA_ERR_QUERY (everything is still
+ * written), or another error. */
+int plvi_ba_window(const plvi_cull_keyframes* kf, const int* kf_map_id, const plvi_local_map_pool* mp,
+                   const plvi_ba_features* fmp, const plvi_local_map_pool* ml, const plvi_ba_features* fml,
+                   const plvi_ba_params* params, const plvi_ba_queries* queries, const plvi_ba_outputs* out);
+
 /* ---------------------------------------------------------------- Stereo
  * Rectified stereo of the stereo Frame constructors (src/Frame.cc:95-140,
  * :225-300). */

@@ -2060,3 +2060,182 @@ class KeyFrameCulling:
         r = {k: a[:1] for k, a in res.items()}
         r.update(rc=rc, past={k: a[1].tolist() for k, a in res.items()})
         return r
+
+
+BA_LDS_KF = 2048              # PLVI_BA_LDS_KF: largest kf_cap whose per-slot tables are kept in LDS
+BA_MAX_OPT = 64               # PLVI_BA_MAX_OPT
+BA_MAX_FIXED_INERTIAL = 200   # PLVI_BA_MAX_FIXED_INERTIAL
+BA_POINTS, BA_LINES, BA_INERTIAL = range(3)
+BA_EDGE_MONO, BA_EDGE_STEREO, BA_EDGE_LINE = range(3)
+BA_ERR_LOCAL_KF, BA_ERR_FIXED_KF, BA_ERR_FEAT, BA_ERR_EDGE, BA_ERR_UNDEFINED, BA_ERR_QUERY = 1, 2, 4, 8, 16, 32
+
+_BA_POOL = {"bad": np.uint8, "obs_off": np.int32, "obs_kf": np.int32, "obs_idx": np.int32, "map_id": np.int32}
+_BA_Q_OUT = ("n_local_kf", "n_fixed_kf", "num_fixed", "init_in_local", "non_fixed", "n_local_feat", "n_mono",
+             "n_stereo", "n_line", "err")
+_BA_LISTS = {"local_kf": "lkf_cap", "fixed_kf": "fkf_cap", "local_feat": "feat_cap", "edge_feat": "edge_cap",
+             "edge_kf": "edge_cap", "edge_idx": "edge_cap", "edge_cam": "edge_cap", "edge_kind": "edge_cap"}
+
+
+class BAFeatures(ctypes.Structure):
+    """plvi_ba_features."""
+    _fields_ = [("obs_idx", _LM_V), ("map_id", _LM_V)]
+
+
+class BAParams(ctypes.Structure):
+    """plvi_ba_params."""
+    _fields_ = [("mode", _LM_I), ("max_opt", _LM_I)]
+
+
+class BAQueries(ctypes.Structure):
+    """plvi_ba_queries."""
+    _fields_ = [("q_slot", _LM_V), ("n_kf_in_map", _LM_V)]
+
+
+class BAOutputs(ctypes.Structure):
+    """plvi_ba_outputs."""
+    _fields_ = [(k, _LM_I) for k in ("lkf_cap", "fkf_cap", "feat_cap", "edge_cap")] + \
+               [(k, _LM_V) for k in ("local_kf", "n_local_kf", "fixed_kf", "n_fixed_kf", "num_fixed", "init_in_local",
+                                     "non_fixed", "local_feat", "n_local_feat", "edge_feat", "edge_kf", "edge_idx",
+                                     "edge_cam", "edge_kind", "n_mono", "n_stereo", "n_line", "err")]
+
+
+class LocalBAWindow:
+    """The set-up of Optimizer::LocalBundleAdjustment / LocalBundleAdjustmentOnlyLines[Angle|WithAngle] /
+    LocalInertialBA (src/Optimizer.cc:4851-4960, :6181-6233, :9185-9307 and their edge loops) over resident tables
+    (plvi_ba_window[_batch]): local keyframes, local features, fixed cameras and the edge list of a current keyframe.
+
+    ``keyframes``: a dict of numpy arrays named as the fields of plvi_cull_keyframes -- bad, mp / nmp / kp_info
+    (POINTS, INERTIAL) or ml / nml (LINES), cand / n_cand (visual modes), kf_id (POINTS), prev_kf (INERTIAL) and
+    optionally init_kf.  ``points`` / ``lines``: dicts with bad, obs_off, obs_kf, obs_idx and optionally map_id.
+    ``kf_map_id`` [kf_cap] is GetMap() per slot, None = one map.  ``rows`` as in KeyFrameCulling.
+
+    ``batch`` runs on device copies (``self.dev``), ``host`` runs one query through the host form.  Both return a
+    dict: the per-query counts and flags, local_kf / fixed_kf / local_feat and the edge_* arrays [q][cap],
+    sentinel-filled where nothing was written."""
+
+    def __init__(self, keyframes, points=None, lines=None, mode=BA_POINTS, max_opt=10, kf_map_id=None, rows=None):
+        self._lib = load()
+        self.kf = {k: _table(keyframes[k], dt) for k, dt in _CULL_KF.items() if keyframes.get(k) is not None}
+        if kf_map_id is not None:
+            self.kf["map_id"] = _table(kf_map_id, np.int32)
+        pool = lambda p: None if p is None else {  # noqa: E731
+            k: _table(p[k], dt) for k, dt in _BA_POOL.items() if p.get(k) is not None}
+        self.pools = [pool(points), pool(lines)]
+        self.kf_cap = len(self.kf["bad"])
+        self.mode = int(mode)
+        self.params = BAParams(self.mode, int(max_opt))
+        self.rows = rows
+        self.dev = None
+
+    def _pool(self):
+        return self.pools[1 if self.mode == BA_LINES else 0]
+
+    def _check_tables(self):
+        """Every companion array has the length its table gives it: refused here, before the library reads them."""
+        _same_len(self.kf_cap, **{"keyframes." + k: a for k, a in self.kf.items()})
+        for g, p in zip(("points", "lines"), self.pools):
+            if p is None:
+                continue
+            n = len(p["bad"])
+            _same_len(n + 1, **{g + ".obs_off": p["obs_off"]})
+            _same_len(n, **{g + ".map_id": p.get("map_id")})
+            n_obs = int(p["obs_off"][n]) if n else 0
+            if len(p["obs_kf"]) < n_obs:
+                raise ValueError(f"{g}.obs_kf has {len(p['obs_kf'])} records, obs_off names {n_obs}")
+            _same_len(len(p["obs_kf"]), **{g + ".obs_idx": p.get("obs_idx")})
+        if self._pool() is None:
+            raise ValueError("the mode's pool is missing")
+
+    def _structs(self, ptr, rows=None):
+        shape = lambda k: self.kf[k].shape[1] if k in self.kf and self.kf[k].ndim == 2 else 0  # noqa: E731
+        kf = CullKeyframes(self.kf_cap, shape("mp"), shape("ml"), rows[2] if rows else shape("cand"))
+        for k in self.kf:
+            if k != "map_id":
+                setattr(kf, k, ptr("kf", k))
+        if rows:
+            kf.cand, kf.n_cand = rows[0], rows[1]
+        res = [kf, ptr("kf", "map_id") if "map_id" in self.kf else None]
+        for g, p in zip(("mp", "ml"), self.pools):
+            if p is None:
+                res += [None, None]
+                continue
+            s, f = LocalMapPool(len(p["bad"])), BAFeatures()
+            for k in p:
+                setattr(f if k in ("obs_idx", "map_id") else s, k, ptr(g, k))
+            res += [s, f]
+        return res
+
+    def upload(self):
+        if self.dev is None:
+            tabs = _named_tables(self.kf, self.pools)
+            self.dev = dict(zip(tabs, _to_device(*tabs.values())[0]))
+        return self.dev
+
+    def _caps(self, stride, lkf_cap, fkf_cap, feat_cap, edge_cap):
+        p = self._pool()
+        d = (max(stride, self.params.max_opt) + 1, self.kf_cap + 2, len(p["bad"]), len(p["obs_kf"]))
+        return {k: d[i] if v is None else v
+                for i, (k, v) in enumerate(zip(("lkf_cap", "fkf_cap", "feat_cap", "edge_cap"),
+                                               (lkf_cap, fkf_cap, feat_cap, edge_cap)))}
+
+    @staticmethod
+    def _host(B, q_slot, n_kf_in_map, caps, fill):
+        per = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.int32), (B,)))  # noqa: E731
+        qin = {"q_slot": per(q_slot), "n_kf_in_map": per(n_kf_in_map)}
+        res = {k: np.full(B + 1, fill, np.int32) for k in _BA_Q_OUT}  # one row more than is written
+        for k, c in _BA_LISTS.items():
+            dt = np.uint8 if k == "edge_kind" else np.int32
+            res[k] = np.full((B + 1, max(caps[c], 1)), fill & 0x7f if dt == np.uint8 else fill, dt)
+        return qin, res
+
+    def batch(self, q_slot, n_kf_in_map=0, lkf_cap=None, fkf_cap=None, feat_cap=None, edge_cap=None, fill=-7,
+              stream=None, run=True):
+        """plvi_ba_window_batch of the current keyframes q_slot.  Returns the dict described above plus "past" (the
+        row after the last query of every output) and "rc".  run=False returns (step(stream), fetch()) for capture."""
+        self._check_tables()
+        dev = self.upload()
+        structs = self._structs(lambda g, k: dev[(g, k)].ptr, self.rows)
+        B = len(np.atleast_1d(q_slot))
+        caps = self._caps(structs[0].cand_stride, lkf_cap, fkf_cap, feat_cap, edge_cap)
+        qin, res = self._host(B, np.atleast_1d(q_slot), n_kf_in_map, caps, fill)
+        qbuf = dict(zip(qin, _to_device(*qin.values())[0]))
+        obuf = dict(zip(res, _to_device(*res.values())[0]))
+        qs = BAQueries(**{k: b.ptr for k, b in qbuf.items()})
+        out = BAOutputs(**caps)
+        for k, b in obuf.items():
+            setattr(out, k, b.ptr)
+        n = [0 if p is None else len(p["bad"]) for p in self.pools]
+        sb = load().plvi_ba_window_scratch_bytes(B, self.kf_cap, n[0], n[1])
+        scratch = DeviceBuffer(sb)
+
+        def step(s=None):
+            return _status("plvi_ba_window_batch", B, *structs, self.params, qs, out, scratch.ptr, sb, s or None)
+
+        def fetch(rc=0):
+            _sync()
+            full = {k: obuf[k].download(a) for k, a in res.items()}
+            r = {k: a[:B] for k, a in full.items()}
+            r.update(rc=rc, past={k: a[B].tolist() for k, a in full.items()}, keep=(qbuf, obuf, scratch))
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
+
+    def host(self, q_slot, n_kf_in_map=0, lkf_cap=None, fkf_cap=None, feat_cap=None, edge_cap=None, fill=-7):
+        """One query through the host form (plvi_ba_window); the same dict with one query, and "rc"
+        (PLVI_E_CAPACITY with an overflow bit set; any other refusal raises)."""
+        self._check_tables()
+        tabs = _named_tables(self.kf, self.pools)
+        structs = self._structs(lambda g, k: tabs[(g, k)].ctypes.data)
+        caps = self._caps(structs[0].cand_stride, lkf_cap, fkf_cap, feat_cap, edge_cap)
+        qin, res = self._host(1, [q_slot], n_kf_in_map, caps, fill)
+        qs = BAQueries(**{k: a.ctypes.data for k, a in qin.items()})
+        out = BAOutputs(**caps)
+        for k, a in res.items():
+            setattr(out, k, a.ctypes.data)
+        rc = _status("plvi_ba_window", *structs, self.params, qs, out)
+        if rc < 0 and rc != PLVI_E_CAPACITY:
+            raise PlviError(rc, "plvi_ba_window")
+        r = {k: a[:1] for k, a in res.items()}
+        r.update(rc=rc, past={k: a[1].tolist() for k, a in res.items()})
+        return r
