@@ -2120,6 +2120,161 @@ int plvi_ba_window(const plvi_cull_keyframes* kf, const int* kf_map_id, const pl
                    const plvi_ba_features* fmp, const plvi_local_map_pool* ml, const plvi_ba_features* fml,
                    const plvi_ba_params* params, const plvi_ba_queries* queries, const plvi_ba_outputs* out);
 
+/* ------------------------------------------------- Loop-detection windows
+ * The integer work of LoopClosing::NewDetectCommonRegions between its device
+ * calls (src/LoopClosing.cc): the six-keyframe window around a BoW candidate
+ * and its abort by proximity (DetectCommonRegionsFromBoW, :797-804 and
+ * :833-840), the first-come merge of the six SearchByBoW results into one
+ * match table (:818-858), the covisible window of :893-915 with its point
+ * cloud and owners (vpPoints / vpPointsKFs of
+ * plvi_search_sim3_projection_batch) and the window and point cloud of
+ * FindMatchesByProjection (:1162-1199).  Integers only; every output equals
+ * the reference's.  Sim3Solver, OptimizeSim3, every g2o::Sim3 / cv::Mat
+ * product, the per-point inputs of the projection search, the thresholds and
+ * SetNotErase / SetErase stay with the caller.
+ *
+ * Tables.  The keyframe side is plvi_cull_keyframes, of which kf_cap, kp_cap,
+ * bad, mp / nmp (nmp under the count contract against kp_cap) and cand /
+ * n_cand / cand_stride are read: the rows of plvi_covis_rows in place.  The
+ * pool is plvi_local_map_pool, read for n and bad, and for pos / normal / dist
+ * / desc where a gather is asked for.  cov5(s) below is
+ * GetBestCovisibilityKeyFrames(5) (KeyFrame.cc:255-263): the first
+ * min(PLVI_LOOP_COVISIBLES, n_cand[s]) entries of row s as stored, with no
+ * isBad() test.  An entry outside [0, kf_cap) is listed in the window as
+ * stored and contributes neither a table nor (LAST) a row of its own.
+ *
+ * Semantics of one query, by kind:
+ *   BOW (candidate i = kf_slot, current keyframe cur_slot).  A bad candidate
+ *      is skipped (:797): n_win = 0, abort_at = -1.  Otherwise the window is
+ *      cov5(i), push_back(front), [0] = i (:802-804): i, c1, c2, c3, c4, c0 --
+ *      i, c0 with one covisible.  With none the reference indexes an empty
+ *      vector; the window is i alone and PLVI_LOOP_ERR_UNDEFINED is set.
+ *      abort_at = the first window position whose keyframe is in the connected
+ *      set of the query (:833-840; a bad member is tested like any other), -1
+ *      without one.  It depends on nothing SearchByBoW produces, so it is
+ *      known before the six searches.  n_pts = 0.
+ *   PROJ (around m = kf_slot; pMostBoWMatchesKF is never reassigned after
+ *      :811, so m is always the candidate).  The window is cov5(m) followed by
+ *      m (:893-895).  The tables of the window are walked in that order, each
+ *      in index order; the first occurrence of every id that is in range and
+ *      not bad is listed in pts, with the keyframe where it occurred in pts_kf
+ *      (:901-915).  No isBad() test on the window's members.
+ *   LAST (around m).  cov5(m), m, then for each of the first |cov5(m)| members
+ *      in order ALL of its cov5 (:1167-1182; the nInserted loop writes a set
+ *      that nothing reads): at most 5 + 1 + 25 entries, repeats and m itself
+ *      included.  A repeated keyframe contributes nothing the second time.
+ *      pts as for PROJ; pts_kf is not written.  The window depends on m
+ *      alone: one query serves every call of FindMatchesByProjection against
+ *      the same pMatchedKFw.
+ *
+ * Merge (:842-857), one per BOW query.  Members j < min(n_win, abort_at if >=
+ * 0) that are in range and not bad (a bad member was not searched, :820) are
+ * read in order, each for k ascending over [0, n1): p = mp[win[j]][m] with m =
+ * matches12[q][j][k], skipped when m is outside the member's table or p is
+ * NULL, out of range or bad.  A p not seen before is inserted: num is
+ * incremented, matched_mp[k] = p, matched_kf[k] = win[j].  A later member can
+ * overwrite cell k with another new point, so num counts distinct points and
+ * can exceed the number of cells that are not -1.  nIndexMostBoWMatchesKF is
+ * computed by the reference and never read; it has no counterpart here.
+ *
+ * Outputs follow the count contract: n_win and n_pts are full lengths,
+ * nothing is written at or past a capacity, err[q] is written by every call.
+ *
+ * Limits.  n_queries <= 65535, max(kf_cap, PLVI_LOOP_WIN_MAX) * kp_cap and
+ * PLVI_LOOP_BOW_WIN * cap1 <= PLVI_LOCAL_MAP_MAX_ENTRIES (a walk position is
+ * an unsigned int; PLVI_E_CAPACITY beyond).  No bound on the pool. */
+#define PLVI_LOOP_COVISIBLES 5 /* nNumCovisibles */
+#define PLVI_LOOP_BOW_WIN 6    /* longest BOW window */
+#define PLVI_LOOP_WIN_MAX 31   /* longest LAST window; row length of win */
+enum { /* plvi_loop_queries.kind */
+  PLVI_LOOP_WIN_BOW = 0,
+  PLVI_LOOP_WIN_PROJ = 1,
+  PLVI_LOOP_WIN_LAST = 2,
+};
+enum { /* err[q], bits */
+  PLVI_LOOP_ERR_PTS = 1,       /* the point list is longer than pt_cap */
+  PLVI_LOOP_ERR_UNDEFINED = 2, /* a BOW candidate has no covisible: the reference reads vpCovKFi[0] of an empty vector */
+  PLVI_LOOP_ERR_QUERY = 4,     /* kf_slot (or a given cur_slot, BOW) outside [0, kf_cap), or an unknown kind:
+                                  n_win = n_pts = 0, abort_at = -1 */
+};
+
+/* Per query q; arrays of n_queries entries. */
+typedef struct plvi_loop_queries {
+  const int* kind;      /* PLVI_LOOP_WIN_* */
+  const int* kf_slot;   /* i for BOW, m for PROJ and LAST */
+  const int* cur_slot;  /* BOW: mpCurrentKF, the keyframe whose connected set row q of the CSR below holds.  It is
+                           checked against [0, kf_cap) and not otherwise read (the set never holds the keyframe
+                           itself); NULL = not checked */
+  const int* conn_off;  /* [q + 1] CSR of GetConnectedKeyFrames() per query, the layout of plvi_kfdb_query_batch; */
+  const int* conn_slot; /*         both NULL = no keyframe is connected; a slot outside [0, kf_cap) is ignored */
+} plvi_loop_queries;
+
+/* Per query q.  The gathered rows have the layouts of plvi_local_map_outputs
+ * (pos [q][pt_cap][3], normal [q][pt_cap][3], dist [q][pt_cap][2], desc
+ * [q][pt_cap][32], moved as dwords: 4-byte aligned), row stride pt_cap; each
+ * may be NULL (no gather) and needs its row of the pool. */
+typedef struct plvi_loop_outputs {
+  int pt_cap;
+  int* win;      /* [q][PLVI_LOOP_WIN_MAX] the window as slots */
+  int* n_win;    /* [q] */
+  int* abort_at; /* [q] BOW: the window position that aborts by proximity or -1; -1 for the other kinds */
+  int* pts;      /* [q][pt_cap] vpMapPoints as pool ids (PROJ, LAST) */
+  int* pts_kf;   /* [q][pt_cap] vpKeyFrames: the slot where the point occurred first; written by PROJ; may be NULL */
+  int* n_pts;    /* [q] full length; 0 for BOW */
+  float* pos;
+  float* normal;
+  float* dist;
+  uint8_t* desc;
+  int* err;      /* [q] PLVI_LOOP_ERR_* */
+} plvi_loop_outputs;
+
+/* Bytes of the scratch block of both batch calls: 256 + 4 * mp_n per query (a
+ * first-occurrence table by pool id).  0 for a negative argument. */
+size_t plvi_loop_window_scratch_bytes(int n_queries, int mp_n);
+
+/* The window call: one workgroup per query, plus one launch of (pt_cap / 256
+ * chunks, queries) when a gather is asked for.  The structs are host memory,
+ * read before the call returns; their pointers are device pointers.
+ * PLVI_E_BADARG for a negative size, a missing required pointer (everything
+ * not marked optional; pts with pt_cap > 0), conn_off / conn_slot given in
+ * part, or a gather without its pool row; n_queries == 0 returns 0 without a
+ * launch.  d_scratch holds at least plvi_loop_window_scratch_bytes(n_queries,
+ * mp->n) bytes (PLVI_E_BADARG below), needs no initialisation, and calls that
+ * share it must be ordered.  Asynchronous on `stream`, no host read of device
+ * data, no allocation: capturable. */
+int plvi_loop_window_batch(int n_queries, const plvi_cull_keyframes* kf, const plvi_local_map_pool* mp,
+                           const plvi_loop_queries* queries, const plvi_loop_outputs* out, void* d_scratch,
+                           size_t scratch_bytes, void* stream);
+
+/* The merge call, one workgroup per query.  d_win [q][PLVI_LOOP_WIN_MAX],
+ * d_n_win [q] and d_abort_at [q] as plvi_loop_window_batch wrote them for BOW
+ * queries; d_matches12 [q][PLVI_LOOP_BOW_WIN][cap1] is the output of
+ * plvi_search_by_bow_kf_batch with n_pairs = 6 * n_queries and pair p = 6 * q
+ * + j; d_n1 [q] follows the count contract against cap1.  Rows of bad members
+ * and of members at or past abort_at or n_win are not read.  Outputs
+ * d_matched_mp / d_matched_kf [q][cap1] (pool id / slot, or -1; rows [0, n1)
+ * are fully written, nothing past them) and d_num [q].  kf is read for kf_cap,
+ * kp_cap, bad, mp and nmp, mp for n and bad.  Scratch, errors and
+ * capturability as above. */
+int plvi_loop_bow_merge_batch(int n_queries, const plvi_cull_keyframes* kf, const plvi_local_map_pool* mp,
+                              const int* d_win, const int* d_n_win, const int* d_abort_at, const int* d_matches12,
+                              const int* d_n1, int cap1, int* d_matched_mp, int* d_matched_kf, int* d_num,
+                              void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* One query from host tables, synchronous: the same structs with host
+ * pointers, per-query arrays of one entry (conn_off of two).  Returns 0,
+ * PLVI_E_CAPACITY when err[0] has PLVI_LOOP_ERR_PTS or PLVI_LOOP_ERR_QUERY
+ * (everything is still written), or another error. */
+int plvi_loop_window(const plvi_cull_keyframes* kf, const plvi_local_map_pool* mp, const plvi_loop_queries* queries,
+                     const plvi_loop_outputs* out);
+
+/* One merge from host memory, synchronous: win [PLVI_LOOP_WIN_MAX], matches12
+ * [PLVI_LOOP_BOW_WIN][cap1], matched_mp / matched_kf [cap1], the rest one int
+ * each. */
+int plvi_loop_bow_merge(const plvi_cull_keyframes* kf, const plvi_local_map_pool* mp, const int* win,
+                        const int* n_win, const int* abort_at, const int* matches12, const int* n1, int cap1,
+                        int* matched_mp, int* matched_kf, int* num);
+
 /* ---------------------------------------------------------------- Stereo
  * Rectified stereo of the stereo Frame constructors (src/Frame.cc:95-140,
  * :225-300). */

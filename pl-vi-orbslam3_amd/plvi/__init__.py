@@ -2239,3 +2239,221 @@ class LocalBAWindow:
         r = {k: a[:1] for k, a in res.items()}
         r.update(rc=rc, past={k: a[1].tolist() for k, a in res.items()})
         return r
+
+
+LOOP_COVISIBLES = 5   # PLVI_LOOP_COVISIBLES: nNumCovisibles
+LOOP_BOW_WIN = 6      # PLVI_LOOP_BOW_WIN: longest BOW window
+LOOP_WIN_MAX = 31     # PLVI_LOOP_WIN_MAX: longest LAST window, row length of win
+LOOP_WIN_BOW, LOOP_WIN_PROJ, LOOP_WIN_LAST = range(3)
+LOOP_ERR_PTS, LOOP_ERR_UNDEFINED, LOOP_ERR_QUERY = 1, 2, 4
+
+_LOOP_KF = {"bad": np.uint8, "mp": np.int32, "nmp": np.int32, "cand": np.int32, "n_cand": np.int32}
+_LOOP_ROWS = {k: _LM_ROWS[k] for k in ("pos", "normal", "dist", "desc")}
+_LOOP_Q_OUT = ("n_win", "abort_at", "n_pts", "err")
+_LOOP_MERGE_OUT = ("matched_mp", "matched_kf")
+
+
+class LoopQueries(ctypes.Structure):
+    """plvi_loop_queries."""
+    _fields_ = [(k, _LM_V) for k in ("kind", "kf_slot", "cur_slot", "conn_off", "conn_slot")]
+
+
+class LoopOutputs(ctypes.Structure):
+    """plvi_loop_outputs."""
+    _fields_ = [("pt_cap", _LM_I)] + \
+               [(k, _LM_V) for k in ("win", "n_win", "abort_at", "pts", "pts_kf", "n_pts", "pos", "normal", "dist",
+                                     "desc", "err")]
+
+
+class LoopWindow:
+    """The keyframe windows, the BoW merge and the point clouds of LoopClosing::NewDetectCommonRegions
+    (src/LoopClosing.cc:797-858, :893-915, :1162-1199) over resident tables (plvi_loop_window[_batch],
+    plvi_loop_bow_merge[_batch]).
+
+    ``keyframes``: a dict of numpy arrays named as the fields of plvi_cull_keyframes -- bad, mp / nmp, cand / n_cand.
+    ``points``: a dict with bad and optionally pos, normal, dist, desc (the rows a gather reads).  ``rows`` as in
+    KeyFrameCulling: the graph's rows replace cand / n_cand in the batch forms.
+
+    ``batch`` runs on device copies (``self.dev``), ``host`` runs one query through the host form.  Both return a
+    dict: n_win, abort_at, n_pts, err per query, win [q][31], pts / pts_kf [q][pt_cap] and the gathered rows asked
+    for by ``gather``, sentinel-filled where nothing was written.  ``connected`` is one sequence of slots per query
+    (GetConnectedKeyFrames() of the current keyframe), None = no keyframe is connected.  ``merge_batch`` /
+    ``merge_host`` take the BOW windows and the six SearchByBoW tables per query."""
+
+    def __init__(self, keyframes, points, rows=None):
+        self._lib = load()
+        self.kf = {k: _table(keyframes[k], dt) for k, dt in _LOOP_KF.items() if keyframes.get(k) is not None}
+        p = {"bad": _table(points["bad"], np.uint8)}
+        for k, (dt, w) in _LOOP_ROWS.items():
+            if points.get(k) is not None:
+                p[k] = _table(points[k], dt, w)
+        self.pools = [p, None]
+        self.kf_cap = len(self.kf["bad"])
+        self.rows = rows
+        self.dev = None
+
+    def _check_tables(self):
+        """Every companion array has the length its table gives it: refused here, before the library reads them."""
+        _same_len(self.kf_cap, **{"keyframes." + k: a for k, a in self.kf.items()})
+        p = self.pools[0]
+        _same_len(len(p["bad"]), **{"points." + k: a for k, a in p.items()})
+
+    def _structs(self, ptr, rows=None):
+        shape = lambda k: self.kf[k].shape[1] if k in self.kf and self.kf[k].ndim == 2 else 0  # noqa: E731
+        kf = CullKeyframes(self.kf_cap, shape("mp"), 0, rows[2] if rows else shape("cand"))
+        for k in self.kf:
+            setattr(kf, k, ptr("kf", k))
+        if rows:
+            kf.cand, kf.n_cand = rows[0], rows[1]
+        return kf, _pool_structs(self.pools, ptr)[0]
+
+    def upload(self):
+        if self.dev is None:
+            tabs = _named_tables(self.kf, self.pools)
+            self.dev = dict(zip(tabs, _to_device(*tabs.values())[0]))
+        return self.dev
+
+    def _pt_cap(self, pt_cap):
+        return max(len(self.pools[0]["bad"]), 1) if pt_cap is None else pt_cap
+
+    def _host(self, B, kind, kf_slot, cur_slot, connected, pt_cap, gather, owners, fill):
+        """The per-query inputs and the pre-filled outputs as host arrays."""
+        per = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.int32), (B,)))  # noqa: E731
+        qin = {"kind": per(kind), "kf_slot": per(kf_slot)}
+        if cur_slot is not None:
+            qin["cur_slot"] = per(cur_slot)
+        if connected is not None:
+            if len(connected) != B:
+                raise ValueError(f"connected has {len(connected)} rows, expected {B}")
+            off = np.zeros(B + 1, np.int32)
+            off[1:] = np.cumsum([len(c) for c in connected])
+            qin["conn_off"] = off
+            qin["conn_slot"] = np.array([s for c in connected for s in c], np.int32).reshape(-1)
+        for k in gather:
+            if k not in self.pools[0]:
+                raise ValueError(f"gather of {k}: points has no such row")
+        res = {k: np.full(B + 1, fill, np.int32) for k in _LOOP_Q_OUT}  # one row more than is written
+        res["win"] = np.full((B + 1, LOOP_WIN_MAX), fill, np.int32)
+        c = max(pt_cap, 1)
+        for k in ("pts", "pts_kf") if owners else ("pts",):
+            res[k] = np.full((B + 1, c), fill, np.int32)
+        for k in gather:
+            dt, w = _LOOP_ROWS[k]
+            res[k] = np.full((B + 1, c, w), fill & 0x7f if dt == np.uint8 else fill, dt)
+        return qin, res
+
+    def batch(self, kind, kf_slot, cur_slot=None, connected=None, pt_cap=None, gather=(), owners=True, fill=-7,
+              stream=None, run=True):
+        """plvi_loop_window_batch of the queries (kind, kf_slot), which broadcast against each other.  Returns the
+        dict described above plus "past" (the row after the last query of every output), "dev" (the device address
+        of every output, for the calls that follow) and "rc".  run=False returns (step(stream), fetch())."""
+        self._check_tables()
+        B = np.broadcast(np.atleast_1d(kind), np.atleast_1d(kf_slot)).shape[0]
+        pt_cap = self._pt_cap(pt_cap)
+        qin, res = self._host(B, kind, kf_slot, cur_slot, connected, pt_cap, gather, owners, fill)
+        dev = self.upload()
+        structs = self._structs(lambda g, k: dev[(g, k)].ptr, self.rows)
+        qbuf = dict(zip(qin, _to_device(*qin.values())[0]))
+        obuf = dict(zip(res, _to_device(*res.values())[0]))
+        qs = LoopQueries(**{k: b.ptr for k, b in qbuf.items()})
+        out = LoopOutputs(pt_cap, **{k: b.ptr for k, b in obuf.items()})
+        sb = load().plvi_loop_window_scratch_bytes(B, len(self.pools[0]["bad"]))
+        scratch = DeviceBuffer(sb)
+
+        def step(s=None):
+            return _status("plvi_loop_window_batch", B, *structs, qs, out, scratch.ptr, sb, s or None)
+
+        def fetch(rc=0):
+            _sync()
+            full = {k: obuf[k].download(a) for k, a in res.items()}
+            r = {k: a[:B] for k, a in full.items()}
+            r.update(rc=rc, past={k: a[B].tolist() for k, a in full.items()}, keep=(qbuf, obuf, scratch),
+                     dev={k: b.ptr for k, b in obuf.items()})
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
+
+    def host(self, kind, kf_slot, cur_slot=None, connected=None, pt_cap=None, gather=(), owners=True, fill=-7):
+        """One query through the host form (plvi_loop_window); the same dict with one query, and "rc"
+        (PLVI_E_CAPACITY with PTS or QUERY set; any other refusal raises).  connected: the slots of this query."""
+        self._check_tables()
+        tabs = _named_tables(self.kf, self.pools)
+        structs = self._structs(lambda g, k: tabs[(g, k)].ctypes.data)
+        pt_cap = self._pt_cap(pt_cap)
+        qin, res = self._host(1, [kind], [kf_slot], None if cur_slot is None else [cur_slot],
+                              None if connected is None else [connected], pt_cap, gather, owners, fill)
+        qs = LoopQueries(**{k: a.ctypes.data for k, a in qin.items()})
+        out = LoopOutputs(pt_cap, **{k: a.ctypes.data for k, a in res.items()})
+        rc = _status("plvi_loop_window", *structs, qs, out)
+        if rc < 0 and rc != PLVI_E_CAPACITY:
+            raise PlviError(rc, "plvi_loop_window")
+        r = {k: a[:1] for k, a in res.items()}
+        r.update(rc=rc, past={k: a[1].tolist() for k, a in res.items()})
+        return r
+
+    def merge_batch(self, win, n_win, abort_at, matches12, n1, n_queries=None, cap1=None, fill=-7, stream=None,
+                    run=True):
+        """plvi_loop_bow_merge_batch.  win [q][31], n_win [q], abort_at [q], matches12 [q][6][cap1] and n1 [q] are
+        numpy arrays (uploaded) or device addresses (then n_queries and cap1 are given).  Returns matched_mp /
+        matched_kf [q][cap1] and num [q], sentinel-filled, plus "past", "dev" and "rc"."""
+        self._check_tables()
+        dev = self.upload()
+        structs = self._structs(lambda g, k: dev[(g, k)].ptr)
+        B = len(n1) if n_queries is None else n_queries
+        cap1 = np.shape(matches12)[2] if cap1 is None else cap1
+        shapes = {"win": (B, LOOP_WIN_MAX), "n_win": (B,), "abort_at": (B,), "matches12": (B, LOOP_BOW_WIN, cap1),
+                  "n1": (B,)}
+        ins, keep = {}, []
+        for k, v in zip(shapes, (win, n_win, abort_at, matches12, n1)):
+            if isinstance(v, (int, np.integer)):
+                ins[k] = int(v)
+                continue
+            a = np.ascontiguousarray(v, np.int32)
+            if a.shape != shapes[k]:
+                raise ValueError(f"{k} has shape {a.shape}, expected {shapes[k]}")
+            keep.append(_to_device(a)[0][0])
+            ins[k] = keep[-1].ptr
+        res = {k: np.full((B + 1, max(cap1, 1)), fill, np.int32) for k in _LOOP_MERGE_OUT}
+        res["num"] = np.full(B + 1, fill, np.int32)
+        obuf = dict(zip(res, _to_device(*res.values())[0]))
+        sb = load().plvi_loop_window_scratch_bytes(B, len(self.pools[0]["bad"]))
+        scratch = DeviceBuffer(sb)
+
+        def step(s=None):
+            return _status("plvi_loop_bow_merge_batch", B, *structs, ins["win"], ins["n_win"], ins["abort_at"],
+                           ins["matches12"], ins["n1"], cap1, obuf["matched_mp"].ptr, obuf["matched_kf"].ptr,
+                           obuf["num"].ptr, scratch.ptr, sb, s or None)
+
+        def fetch(rc=0):
+            _sync()
+            full = {k: obuf[k].download(a) for k, a in res.items()}
+            r = {k: a[:B] for k, a in full.items()}
+            r.update(rc=rc, past={k: a[B].tolist() for k, a in full.items()}, keep=(keep, obuf, scratch),
+                     dev={k: b.ptr for k, b in obuf.items()})
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
+
+    def merge_host(self, win, n_win, abort_at, matches12, n1, fill=-7):
+        """One merge through the host form (plvi_loop_bow_merge): win [31], matches12 [6][cap1]."""
+        self._check_tables()
+        win, m12 = _table(win, np.int32), _table(matches12, np.int32)
+        if win.shape != (LOOP_WIN_MAX,):
+            raise ValueError(f"win has shape {win.shape}, expected ({LOOP_WIN_MAX},)")
+        if m12.ndim != 2 or m12.shape[0] != LOOP_BOW_WIN:
+            raise ValueError(f"matches12 has shape {m12.shape}, expected ({LOOP_BOW_WIN}, cap1)")
+        cap1 = m12.shape[1]
+        tabs = _named_tables(self.kf, self.pools)
+        structs = self._structs(lambda g, k: tabs[(g, k)].ctypes.data)
+        one = lambda v: np.array([v], np.int32)  # noqa: E731
+        res = {k: np.full((2, max(cap1, 1)), fill, np.int32) for k in _LOOP_MERGE_OUT}
+        res["num"] = np.full(2, fill, np.int32)
+        rc = _status("plvi_loop_bow_merge", *structs, win, one(n_win), one(abort_at), m12, one(n1), cap1,
+                     res["matched_mp"], res["matched_kf"], res["num"])
+        if rc < 0:
+            raise PlviError(rc, "plvi_loop_bow_merge")
+        r = {k: a[:1] for k, a in res.items()}
+        r.update(rc=rc, past={k: a[1].tolist() for k, a in res.items()})
+        return r
