@@ -4,13 +4,11 @@
 // :6291-6337) and LocalInertialBA (:9185-9307, edges :9521-9640).  Integers only.
 //
 // The reference's mnBALocalForKF / mnBAFixedForKF stamps make "first come" decisions along a
-// fixed traversal; here every such decision is "the smallest traversal position wins":
+// fixed traversal; here every such decision is "the smallest traversal position wins" (first_walk.h):
 //   local keyframes  cam[slot] = atomicMin of the row position (q is 0, row entry p is 1 + p); a
 //                    row entry that is stamped but not listed leaves kBaLocal.  dl[] is the list
 //                    without its repeats, which is all the feature walk needs.
-//   local features   first[id] = atomicMin of r * cap + i over dl[r]'s table, then an ordered
-//                    compaction of the entries that hold their id's minimum: the rows laid end to
-//                    end, kBaPer consecutive positions a thread, one block scan per 8192 positions.
+//   local features   the first-occurrence walk over the rows of dl[], first[n] cleared per query.
 //   fixed cameras    keys[slot] = atomicMin of (feature position << 32 | observation offset) over
 //                    the observers that are not stamped local; the keys of the slots that pass the
 //                    bad / map test are sorted, and a key names its slot through obs_kf.
@@ -26,17 +24,16 @@
 // One workgroup per query and one launch; keys[] and cam[] are LDS up to PLVI_BA_LDS_KF slots.
 #include <cstring>
 
-#include "block_prims.h"
+#include "first_walk.h"
 #include "map_pool.h"
 #include "plvi_common.h"
 
 namespace plvi {
 
 constexpr int kBaThreads = 1024;
-constexpr int kBaPer = 8;  // positions a thread takes per block scan of the feature compaction
 constexpr int kBaWaves = kBaThreads / kWave;
 constexpr int kBaMaxFix = PLVI_BA_MAX_FIXED_INERTIAL;
-constexpr unsigned kBaNone = 0xffffffffu, kBaLocal = 0xfffffffeu, kBaFixed = 0xfffffffdu;
+constexpr unsigned kBaLocal = kNoPos - 1, kBaFixed = kNoPos - 2;  // cam[] stamps above every position
 
 typedef unsigned long long u64;
 constexpr u64 kBaNoKey = ~0ull;
@@ -79,9 +76,8 @@ __device__ __forceinline__ bool ba_listed(const BaArgs& a, int s, int M) {
     return !a.kf_bad[s] && (a.mode == PLVI_BA_LINES || !a.kf_map || a.kf_map[s] == M);
 }
 
-// :4886 / :6208 / :9229
-__device__ __forceinline__ bool ba_feature(const BaArgs& a, int id, int M) {
-    if ((unsigned)id >= (unsigned)a.n || a.f_bad[id]) return false;
+// :4886 / :6208 / :9229 for a feature that is in range and not bad
+__device__ __forceinline__ bool ba_in_map(const BaArgs& a, int id, int M) {
     return a.mode == PLVI_BA_INERTIAL || !a.f_map || a.f_map[id] == M;
 }
 
@@ -91,7 +87,7 @@ __device__ int ba_choice(const BaArgs& a, const unsigned* cam, int id) {
     const int o1 = a.obs_off[id + 1];
     for (int o = a.obs_off[id]; o < o1; ++o) {
         const int kf = a.obs_kf[o];
-        if ((unsigned)kf < (unsigned)a.K && ba_load(cam + kf) == kBaNone && !a.kf_bad[kf]) return kf;
+        if ((unsigned)kf < (unsigned)a.K && ba_load(cam + kf) == kNoPos && !a.kf_bad[kf]) return kf;
     }
     return -1;
 }
@@ -100,7 +96,7 @@ __device__ int ba_choice(const BaArgs& a, const unsigned* cam, int id) {
 __device__ __forceinline__ bool ba_edge(const BaArgs& a, const unsigned* cam, int o, int M) {
     const int kf = a.obs_kf[o];
     if ((unsigned)kf >= (unsigned)a.K || a.kf_bad[kf] || (a.kf_map && a.kf_map[kf] != M)) return false;
-    if (a.mode == PLVI_BA_INERTIAL && cam[kf] == kBaNone) return false;
+    if (a.mode == PLVI_BA_INERTIAL && cam[kf] == kNoPos) return false;
     return (unsigned)a.obs_idx[o] < (unsigned)a.cap;
 }
 
@@ -137,9 +133,9 @@ __global__ __launch_bounds__(kBaThreads) void ba_window_kernel(BaArgs a) {
     const int n_row = inertial ? 0 : clampi(a.n_cand[cur], 0, a.cand_stride);
     const int* row = a.cand + (size_t)cur * a.cand_stride;
 
-    for (int s = tid; s < a.K; s += kBaThreads) cam[s] = kBaNone;
+    for (int s = tid; s < a.K; s += kBaThreads) cam[s] = kNoPos;
     for (int s = tid; s < a.P; s += kBaThreads) keys[s] = kBaNoKey;
-    for (int i = tid; i < a.n; i += kBaThreads) first[i] = kBaNone;
+    for (int i = tid; i < a.n; i += kBaThreads) first[i] = kNoPos;
     if (tid == 0) {
         s_init = s_n_moved = s_err = s_n_fixed = s_kind[0] = s_kind[1] = 0;
         s_moved[0] = s_moved[1] = -1;
@@ -179,7 +175,7 @@ __global__ __launch_bounds__(kBaThreads) void ba_window_kernel(BaArgs a) {
         }
         for (int i = 0; i < n; ++i) {
             const int s = s_chain[i];
-            if (cam[s] == kBaNone) {
+            if (cam[s] == kNoPos) {
                 cam[s] = kBaLocal;
                 dl[n_dl++] = s;
                 if (a.init_kf && a.init_kf[s]) s_init = 1;
@@ -188,7 +184,7 @@ __global__ __launch_bounds__(kBaThreads) void ba_window_kernel(BaArgs a) {
         const int back = s_chain[n - 1], p = a.prev_kf[back];  // :9240-9251
         if ((unsigned)p < (unsigned)a.K) {
             s_fix[0] = p;
-            if (cam[p] == kBaNone) cam[p] = kBaFixed;
+            if (cam[p] == kNoPos) cam[p] = kBaFixed;
         } else {
             cam[back] = kBaFixed;
             s_fix[0] = back;
@@ -201,54 +197,16 @@ __global__ __launch_bounds__(kBaThreads) void ba_window_kernel(BaArgs a) {
     __syncthreads();
     const int n_dl = s_n_dl;
 
-    // ---- 2: the local features
-    // The walk is the n_dl rows laid end to end, position e = r * cap + i (at most kf_cap * cap, which
-    // fits: PLVI_LOCAL_MAP_MAX_ENTRIES).  No step of either pass waits for the row before it.
-    const unsigned total = (unsigned)n_dl * (unsigned)a.cap;
-    for (unsigned e = tid; e < total; e += kBaThreads) {
-        const unsigned r = e / (unsigned)a.cap, i = e - r * (unsigned)a.cap;
-        const int s = dl[r];
-        if ((int)i >= clampi(a.ntab[s], 0, a.cap)) continue;
-        const int id = a.tab[(size_t)s * a.cap + i];
-        if (ba_feature(a, id, M)) atomicMin(first + id, e);
-    }
-    __syncthreads();
-    // ordered compaction: a thread takes kBaPer consecutive positions, one block scan per kBaThreads * kBaPer
-    int n_feat = 0;
-    for (unsigned base = 0; base < total; base += kBaThreads * kBaPer) {
-        const unsigned e0 = base + (unsigned)tid * kBaPer;
-        int ids[kBaPer];
-        unsigned flags = 0;
-#pragma unroll
-        for (int k = 0; k < kBaPer; ++k) ids[k] = -1;
-        if (e0 < total) {
-            unsigned r = e0 / (unsigned)a.cap, i = e0 - r * (unsigned)a.cap;
-            int s = dl[r], m = clampi(a.ntab[s], 0, a.cap);
-#pragma unroll
-            for (int k = 0; k < kBaPer; ++k) {
-                if (e0 + k >= total) break;
-                if ((int)i < m) ids[k] = a.tab[(size_t)s * a.cap + i];
-                if (++i == (unsigned)a.cap && ++r < (unsigned)n_dl) {  // the next row
-                    i = 0;
-                    s = dl[r];
-                    m = clampi(a.ntab[s], 0, a.cap);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kBaPer; ++k)
-                if (ba_feature(a, ids[k], M) && first[ids[k]] == e0 + k) flags |= 1u << k;
-        }
-        int tot;
-        int at = n_feat + block_scan<kBaWaves>(__popc(flags), s_wave, tid, &tot);
-#pragma unroll
-        for (int k = 0; k < kBaPer; ++k)
-            if (flags >> k & 1) {
-                lf[at] = ids[k];
-                if (at < o.feat_cap) o.local_feat[(size_t)q * o.feat_cap + at] = ids[k];
-                ++at;
-            }
-        n_feat += tot;
-    }
+    // ---- 2: the local features: the walk over the rows of dl[] (at most kf_cap * cap positions, which
+    // fits: PLVI_LOCAL_MAP_MAX_ENTRIES)
+    const KfTable v{a.tab, a.ntab, a.cap, a.n, a.f_bad};
+    const auto in_map = [&](int id) { return ba_in_map(a, id, M); };
+    first_mark<kBaThreads>((unsigned)n_dl * (unsigned)a.cap, first, row_walk(dl, v, in_map), false);
+    const int n_feat =
+        first_compact<kBaThreads, 8>(dl, n_dl, v, first, in_map, s_wave, [&](int at, int id, unsigned) {
+            lf[at] = id;
+            if (at < o.feat_cap) o.local_feat[(size_t)q * o.feat_cap + at] = id;
+        });
     __syncthreads();
 
     // ---- 3 / 5: the fixed cameras
@@ -258,7 +216,7 @@ __global__ __launch_bounds__(kBaThreads) void ba_window_kernel(BaArgs a) {
             const int id = lf[j], o1 = a.obs_off[id + 1];
             for (int ob = a.obs_off[id]; ob < o1; ++ob) {
                 const int kf = a.obs_kf[ob];
-                if ((unsigned)kf < (unsigned)a.K && cam[kf] == kBaNone) atomicMin(keys + kf, (u64)j << 32 | (unsigned)ob);
+                if ((unsigned)kf < (unsigned)a.K && cam[kf] == kNoPos) atomicMin(keys + kf, (u64)j << 32 | (unsigned)ob);
             }
         }
         __syncthreads();
@@ -270,8 +228,7 @@ __global__ __launch_bounds__(kBaThreads) void ba_window_kernel(BaArgs a) {
             else
                 ++mine;
         }
-        mine = wave_sum(mine);
-        if ((tid & (kWave - 1)) == 0 && mine) atomicAdd(&s_n_fixed, mine);
+        block_add(mine, &s_n_fixed, tid);
         __syncthreads();
         bitonic_sort<kBaThreads>(keys, a.P, tid);
         // ---- 4: the two-lowest rule
@@ -309,7 +266,7 @@ __global__ __launch_bounds__(kBaThreads) void ba_window_kernel(BaArgs a) {
             s_num_fixed = num_fixed;
         }
         // cam[] turns from stamps into positions in local || fixed
-        for (int s = tid; s < a.K; s += kBaThreads) cam[s] = kBaNone;
+        for (int s = tid; s < a.K; s += kBaThreads) cam[s] = kNoPos;
         __syncthreads();
         const int m0 = s_n_moved > 0 ? s_moved[0] : -1, m1 = s_n_moved > 1 ? s_moved[1] : -1;
         for (int t0 = 0; t0 <= n_row; t0 += kBaThreads) {
@@ -352,7 +309,7 @@ __global__ __launch_bounds__(kBaThreads) void ba_window_kernel(BaArgs a) {
                     mask &= mask - 1;
                     int add = 0;
                     if (tid == l) {
-                        if (ba_load(cam + c) != kBaNone) c = ba_choice(a, cam, lf[j]);  // an earlier lane took it
+                        if (ba_load(cam + c) != kNoPos) c = ba_choice(a, cam, lf[j]);  // an earlier lane took it
                         if (c >= 0) {
                             ba_store(cam + c, kBaFixed);
                             s_fix[nf] = c;
@@ -372,7 +329,7 @@ __global__ __launch_bounds__(kBaThreads) void ba_window_kernel(BaArgs a) {
         __syncthreads();
         n_local = s_n_opt;
         const int nf = s_n_fixed;
-        for (int s = tid; s < a.K; s += kBaThreads) cam[s] = kBaNone;
+        for (int s = tid; s < a.K; s += kBaThreads) cam[s] = kNoPos;
         __syncthreads();
         for (int i = tid; i < n_local + nf; i += kBaThreads) {
             const bool opt = i < n_local;
@@ -413,19 +370,15 @@ __global__ __launch_bounds__(kBaThreads) void ba_window_kernel(BaArgs a) {
                 o.edge_feat[e] = j;
                 o.edge_kf[e] = kf;
                 o.edge_idx[e] = idx;
-                o.edge_cam[e] = (int)cam[kf];  // kBaNone is -1
+                o.edge_cam[e] = (int)cam[kf];  // kNoPos is -1
                 o.edge_kind[e] = (uint8_t)kind;
             }
             ++at;
         }
         n_edges += tot;
     }
-    n_mono = wave_sum(n_mono);
-    n_stereo = wave_sum(n_stereo);
-    if ((tid & (kWave - 1)) == 0) {
-        if (n_mono) atomicAdd(&s_kind[0], n_mono);
-        if (n_stereo) atomicAdd(&s_kind[1], n_stereo);
-    }
+    block_add(n_mono, &s_kind[0], tid);
+    block_add(n_stereo, &s_kind[1], tid);
     __syncthreads();
     if (tid == 0) {
         const bool lines = a.mode == PLVI_BA_LINES;

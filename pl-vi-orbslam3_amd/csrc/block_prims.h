@@ -1,6 +1,6 @@
 // block_prims.h — the wave and workgroup primitives the kernels share: the 256-bit Hamming
-// distance, wave and workgroup scans, the wave sum, the bitonic sort of keys in LDS or global
-// memory, and the small integer helpers that go with them.
+// distance, wave and workgroup scans, the wave sum and the workgroup count built on it, the bitonic
+// sort of keys in LDS or global memory, and the small integer helpers that go with them.
 //
 // Barrier contracts of the block-wide functions (every thread of the workgroup calls them, with
 // uniform arguments apart from v and tid):
@@ -9,6 +9,8 @@
 //                     at once with the same s_wave.  It orders nothing but s_wave for the caller
 //                     after its second barrier: what a thread writes from the result is seen by
 //                     the others only after a barrier of the caller's (or the next call's).
+//   block_add         no barrier: *s_counter is initialised before a barrier of the caller's ahead of
+//                     the call, and holds the sum after a barrier of the caller's behind it.
 //   block_scan_array  s[] must be complete before the call (a barrier of the caller's); ends with
 //                     a barrier, after which every thread sees the scanned s[].  s_tmp as s_wave.
 //   bitonic_sort      key[] (and val[]) must be complete before the call (a barrier of the
@@ -20,6 +22,9 @@
 namespace plvi {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// 0 <= v < n: the test of a slot against a table, or of an id against a pool
+__device__ __forceinline__ bool in_range(int v, int n) { return (unsigned)v < (unsigned)n; }
 
 // the smallest lo * 2^k >= n (lo a power of two)
 __host__ __device__ __forceinline__ int pow2_at_least(int n, int lo) {
@@ -56,6 +61,13 @@ __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int m = kWave / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, kWave);
     return v;
+}
+
+// adds every thread's v to *s_counter (LDS): one atomicAdd a wave, none for a wave that sums to zero
+template <class T>
+__device__ __forceinline__ void block_add(T v, T* s_counter, int tid) {
+    v = wave_sum(v);
+    if ((tid & (kWave - 1)) == 0 && v) atomicAdd(s_counter, v);
 }
 
 // exclusive scan of v over a workgroup of NW waves; *total = the sum.  s_wave: NW ints of LDS.

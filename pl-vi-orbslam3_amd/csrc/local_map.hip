@@ -12,22 +12,21 @@
 //                        compaction of d_kf_order, pKFmax the first position of the largest count.
 //                        The expansion (:5474-5524) and the temporal walk (:5527-5544) are short
 //                        and sequential: thread 0 runs them against the listed-bitmap.
-//   lm_first_kernel      several workgroups per frame and feature kind.  Entry i of the r-th
-//                        keyframe of the reverse walk (:5331) has the traversal position
-//                        r * cap + i; every live entry atomicMin's its position into a
-//                        first-occurrence table keyed by pool id (the mnTrackReferenceForFrame
-//                        stamp of :5342 / :5348 restated as "the smallest position wins").
+//   lm_first_kernel      several workgroups per frame and feature kind: the mark pass of the
+//                        first-occurrence walk (first_walk.h) in its multi-workgroup form, over
+//                        the keyframes in reverse order (:5331), the table filled with 0x7f (the
+//                        mnTrackReferenceForFrame stamp of :5342 / :5348).
 //   lm_count_kernel      each workgroup owns a contiguous range of positions and counts the
 //                        entries that hold their id's minimum.
 //   lm_write_kernel      the same ranges again: the workgroup's base is the sum of the counts
 //                        before it, a block scan orders the kept entries inside it, and each kept
-//                        entry writes its list cell and gathers its rows (descriptors as dwords).
+//                        entry writes its list cell and gathers its rows (map_pool.h).
 // Points and lines keep separate lists and separate stamps, so the per-keyframe interleaving of
 // :5382-5395 cannot be seen in the outputs; the two kinds run as blockIdx.z = 0 / 1.
 #include <climits>
 #include <cstring>
 
-#include "block_prims.h"
+#include "first_walk.h"
 #include "map_pool.h"
 #include "plvi_common.h"
 
@@ -222,11 +221,7 @@ __global__ __launch_bounds__(kKfThreads) void lm_keyframes_kernel(LmArgs a) {
 // each keyframe's table in index order; NULL and bad entries dropped (:5340, :5344)
 __device__ __forceinline__ int entry_id(const LmSide& S, const int* kfl, int nlk, int p) {
     const int r = p / S.kcap, i = p - r * S.kcap;
-    const int kf = kfl[nlk - 1 - r];
-    if (i >= clampi(S.kf_n[kf], 0, S.kcap)) return -1;
-    const int id = S.kf_tab[(size_t)kf * S.kcap + i];
-    if ((unsigned)id >= (unsigned)S.n || S.bad[id]) return -1;
-    return id;
+    return KfTable{S.kf_tab, S.kf_n, S.kcap, S.n, S.bad}.at(kfl[nlk - 1 - r], i);
 }
 
 // position p is an occurrence of id: keep the smallest
@@ -278,8 +273,7 @@ __global__ __launch_bounds__(kListThreads) void lm_count_kernel(LmArgs a) {
             c += id >= 0 && is_first(S, f, id, p);
         }
     }
-    c = wave_sum(c);
-    if ((tid & (kWave - 1)) == 0 && c) atomicAdd(&s_cnt, c);
+    block_add(c, &s_cnt, tid);
     __syncthreads();
     if (tid == 0) S.cnt[(size_t)f * a.G + b] = s_cnt;
 }
@@ -310,6 +304,7 @@ __global__ __launch_bounds__(kListThreads) void lm_write_kernel(LmArgs a) {
     const int* kfl = a.kfl + (size_t)f * a.kf_cap;
     const unsigned* bits = S.seen_bits + (size_t)f * S.seen_words;
     const size_t row0 = (size_t)f * S.out_cap;
+    const PoolGather g{S.pos, S.sep, S.normal, S.dist, S.desc, S.o_pos, S.o_sep, S.o_normal, S.o_dist, S.o_desc};
     int p0, p1;
     group_range(nlk * S.kcap, a.G, b, &p0, &p1);
     int run = base;
@@ -337,33 +332,13 @@ __global__ __launch_bounds__(kListThreads) void lm_write_kernel(LmArgs a) {
                 const int obs = S.obs_off[id + 1] > S.obs_off[id];
                 S.o_flags[o] = (uint8_t)(unseen | obs << 1);
             }
-            if (S.o_pos) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) S.o_pos[3 * o + k] = S.pos[3 * (size_t)id + k];
-            }
-            if (S.o_sep) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) S.o_sep[6 * o + k] = S.sep[6 * (size_t)id + k];
-            }
-            if (S.o_normal) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) S.o_normal[3 * o + k] = S.normal[3 * (size_t)id + k];
-            }
-            if (S.o_dist) {
-                S.o_dist[2 * o] = S.dist[2 * (size_t)id];
-                S.o_dist[2 * o + 1] = S.dist[2 * (size_t)id + 1];
-            }
+            g.rows(o, (size_t)id);
         }
         __syncthreads();
-        if (S.o_desc) {  // 32-byte rows as 8 dwords, 8 consecutive lanes a row
-            const unsigned* src = reinterpret_cast<const unsigned*>(S.desc);
-            unsigned* dst = reinterpret_cast<unsigned*>(S.o_desc);
-            for (int k = tid; k < tot * 8; k += kListThreads) {
-                const int e = k >> 3, w = k & 7;
-                const int sid = s_id[e];
-                if (sid >= 0) dst[(row0 + s_out[e]) * 8 + w] = src[(size_t)sid * 8 + w];
-            }
-        }
+        g.descriptors<kListThreads>(tot, tid, [&](int e, size_t* at) {
+            *at = row0 + s_out[e];
+            return s_id[e];
+        });
         run += tot;
         // the next round's block_scan synchronises before s_id / s_out are written again
     }

@@ -4,45 +4,37 @@
 // window of DetectCommonRegionsFromBoW with its point cloud and owners (:893-915) and the window of
 // FindMatchesByProjection (:1162-1199).  Integers only.
 //
-// The reference's std::set<MapPoint*> makes "first come" decisions along a fixed traversal; here every
-// such decision is "the smallest traversal position wins", as in ba_window.hip:
+// The reference's std::set<MapPoint*> makes "first come" decisions along a fixed traversal; here they are
+// the first-occurrence walk of first_walk.h, with its reset (the scratch block needs no fill):
 //   window        thread 0: at most PLVI_LOOP_WIN_MAX slots, and dl[], the window without its repeats
 //                 and without the entries that name no slot (neither contributes a table).
 //   abort_at      the connected set is walked by the whole workgroup, each entry against the window:
 //                 atomicMin of the window position in LDS.
-//   point cloud   the rows of dl[] laid end to end, position e = r * kp_cap + i.  Three passes, none of
-//                 which waits for the row before it: first[id] = none for every id the walk meets (so
-//                 the scratch block needs no fill and the cost does not depend on the pool size),
-//                 atomicMin of e into first[id], then an ordered compaction of the entries that hold
-//                 their id's minimum, kLwPer consecutive positions a thread and one block scan per 8192.
-//   gathers       a second launch over (256-point chunks, queries): pos / normal / dist one thread a
-//                 point, descriptors as dwords with 8 consecutive lanes a row.
-//   merge         the same three passes over position j * n1 + k of at most 6 * cap1 matches; entry
-//                 (j, k) wins iff it holds its point's minimum, cell k takes the winner of the largest j,
-//                 num is the number of winners.
+//   point cloud   the walk over the rows of dl[].
+//   gathers       a second launch over (256-point chunks, queries): the gather of map_pool.h.
+//   merge         the mark pass over position j * n1 + k of at most 6 * cap1 matches; entry (j, k) wins
+//                 iff it holds its point's minimum, cell k takes the winner of the largest j, num is the
+//                 number of winners.
 // One workgroup per query in both list kernels.
 #include <climits>
 #include <cstring>
 
-#include "block_prims.h"
+#include "first_walk.h"
 #include "map_pool.h"
 #include "plvi_common.h"
 
 namespace plvi {
 
 constexpr int kLwThreads = 1024;
-constexpr int kLwPer = 8;  // positions a thread takes per block scan of the compaction
 constexpr int kLwWaves = kLwThreads / kWave;
 constexpr int kLwCov = PLVI_LOOP_COVISIBLES, kLwBow = PLVI_LOOP_BOW_WIN, kLwWin = PLVI_LOOP_WIN_MAX;
 constexpr int kLwGather = 256;  // points per workgroup of the gather
-constexpr unsigned kLwNone = 0xffffffffu;
 
 struct LwTables {
-    int K, cap, cand_stride, n;
+    int K, cand_stride;
     const uint8_t* kf_bad;
-    const int *tab, *ntab;  // [K][cap], [K]
+    KfTable v;  // the keypoint tables [K][kp_cap] over the MapPoint pool (:905 / :1190 / :846)
     const int *cand, *n_cand;
-    const uint8_t* p_bad;
     unsigned* first;  // [n_queries][n], in the scratch block
 };
 
@@ -60,12 +52,6 @@ struct LwMergeArgs {
 };
 
 inline size_t lw_per_query(int n) { return 4 * (size_t)n; }  // first[n]
-
-__device__ __forceinline__ bool lw_slot(const LwTables& t, int s) { return (unsigned)s < (unsigned)t.K; }
-// :905 / :1190 / :846
-__device__ __forceinline__ bool lw_point(const LwTables& t, int id) {
-    return (unsigned)id < (unsigned)t.n && !t.p_bad[id];
-}
 
 // GetBestCovisibilityKeyFrames(5) of slot s (in range) as stored; returns the length
 __device__ int lw_cov(const LwTables& t, int s, int* out) {
@@ -87,7 +73,7 @@ __global__ __launch_bounds__(kLwThreads) void loop_window_kernel(LwArgs a) {
     if (tid == 0) {
         int n = 0, err = 0;
         const bool known = bow || kind == PLVI_LOOP_WIN_PROJ || kind == PLVI_LOOP_WIN_LAST;
-        if (!known || !lw_slot(t, m) || (bow && a.q.cur_slot && !lw_slot(t, a.q.cur_slot[q]))) {
+        if (!known || !in_range(m, t.K) || (bow && a.q.cur_slot && !in_range(a.q.cur_slot[q], t.K))) {
             err = PLVI_LOOP_ERR_QUERY;
         } else if (bow) {
             if (!t.kf_bad[m]) {  // :797
@@ -106,12 +92,12 @@ __global__ __launch_bounds__(kLwThreads) void loop_window_kernel(LwArgs a) {
             s_win[n++] = m;
             if (kind == PLVI_LOOP_WIN_LAST)  // :1167-1182: every row is appended whole
                 for (int i = 0; i < nc; ++i)
-                    if (lw_slot(t, s_win[i])) n += lw_cov(t, s_win[i], s_win + n);
+                    if (in_range(s_win[i], t.K)) n += lw_cov(t, s_win[i], s_win + n);
         }
         int n_dl = 0;
         for (int w = 0; w < n && !bow; ++w) {
             const int s = s_win[w];
-            bool fresh = lw_slot(t, s);
+            bool fresh = in_range(s, t.K);
             for (int r = 0; r < n_dl && fresh; ++r) fresh = s_dl[r] != s;
             if (fresh) s_dl[n_dl++] = s;
         }
@@ -129,7 +115,7 @@ __global__ __launch_bounds__(kLwThreads) void loop_window_kernel(LwArgs a) {
             const int o1 = a.q.conn_off[q + 1];
             for (int c = max(a.q.conn_off[q], 0) + tid; c < o1; c += kLwThreads) {
                 const int s = a.q.conn_slot[c];
-                if (!lw_slot(t, s)) continue;
+                if (!in_range(s, t.K)) continue;
                 for (int w = 0; w < n_win; ++w)
                     if (s_win[w] == s) {
                         atomicMin(&s_abort, w);
@@ -147,62 +133,18 @@ __global__ __launch_bounds__(kLwThreads) void loop_window_kernel(LwArgs a) {
         return;
     }
 
-    // ---- the point cloud: the rows of dl[] laid end to end (at most kLwWin * cap positions, which
-    // fits: the host checks it)
-    unsigned* first = t.first + (size_t)q * t.n;
-    const unsigned cap = (unsigned)t.cap, total = (unsigned)n_dl * cap;
-    for (int pass = 0; pass < 2; ++pass) {
-        for (unsigned e = tid; e < total; e += kLwThreads) {
-            const unsigned r = e / cap, i = e - r * cap;
-            const int s = s_dl[r];
-            if ((int)i >= clampi(t.ntab[s], 0, t.cap)) continue;
-            const int id = t.tab[(size_t)s * cap + i];
-            if (!lw_point(t, id)) continue;
-            if (pass == 0)
-                first[id] = kLwNone;
-            else
-                atomicMin(first + id, e);
-        }
-        __syncthreads();
-    }
+    // ---- the point cloud: the walk over the rows of dl[] (at most kLwWin * cap positions, which fits:
+    // the host checks it)
+    unsigned* first = t.first + (size_t)q * t.v.n;
+    const auto every = [](int) { return true; };
+    first_mark<kLwThreads>((unsigned)n_dl * (unsigned)t.v.cap, first, row_walk(s_dl, t.v, every), true);
     const bool owners = kind == PLVI_LOOP_WIN_PROJ && o.pts_kf;
-    int n_pts = 0;
-    for (unsigned base = 0; base < total; base += kLwThreads * kLwPer) {
-        const unsigned e0 = base + (unsigned)tid * kLwPer;
-        int ids[kLwPer];
-        unsigned flags = 0;
-#pragma unroll
-        for (int k = 0; k < kLwPer; ++k) ids[k] = -1;
-        if (e0 < total) {
-            unsigned r = e0 / cap, i = e0 - r * cap;
-            int s = s_dl[r], nt = clampi(t.ntab[s], 0, t.cap);
-#pragma unroll
-            for (int k = 0; k < kLwPer; ++k) {
-                if (e0 + k >= total) break;
-                if ((int)i < nt) ids[k] = t.tab[(size_t)s * cap + i];
-                if (++i == cap && ++r < (unsigned)n_dl) {  // the next row
-                    i = 0;
-                    s = s_dl[r];
-                    nt = clampi(t.ntab[s], 0, t.cap);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kLwPer; ++k)
-                if (lw_point(t, ids[k]) && first[ids[k]] == e0 + k) flags |= 1u << k;
-        }
-        int tot;
-        int at = n_pts + block_scan<kLwWaves>(__popc(flags), s_wave, tid, &tot);
-#pragma unroll
-        for (int k = 0; k < kLwPer; ++k)
-            if (flags >> k & 1) {
-                if (at < o.pt_cap) {
-                    o.pts[(size_t)q * o.pt_cap + at] = ids[k];
-                    if (owners) o.pts_kf[(size_t)q * o.pt_cap + at] = s_dl[(e0 + k) / cap];
-                }
-                ++at;
-            }
-        n_pts += tot;
-    }
+    const auto write = [&](int at, int id, unsigned e) {
+        if (at >= o.pt_cap) return;
+        o.pts[(size_t)q * o.pt_cap + at] = id;
+        if (owners) o.pts_kf[(size_t)q * o.pt_cap + at] = s_dl[e / (unsigned)t.v.cap];
+    };
+    const int n_pts = first_compact<kLwThreads, 8>(s_dl, n_dl, t.v, first, every, s_wave, write);
     if (tid == 0) {
         o.n_win[q] = n_win;
         o.abort_at[q] = -1;
@@ -219,29 +161,9 @@ __global__ __launch_bounds__(kLwGather) void loop_gather_kernel(plvi_loop_output
     const int n = min(o.n_pts[q], o.pt_cap) - base;  // points of this chunk
     if (n <= 0) return;
     const size_t row0 = (size_t)q * o.pt_cap + base;
-    if (tid < n) {
-        const size_t at = row0 + tid, id = (size_t)o.pts[at];
-        if (o.pos) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) o.pos[3 * at + k] = pos[3 * id + k];
-        }
-        if (o.normal) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) o.normal[3 * at + k] = normal[3 * id + k];
-        }
-        if (o.dist) {
-            o.dist[2 * at] = dist[2 * id];
-            o.dist[2 * at + 1] = dist[2 * id + 1];
-        }
-    }
-    if (o.desc) {  // 32-byte rows as 8 dwords, 8 consecutive lanes a row
-        const unsigned* src = reinterpret_cast<const unsigned*>(desc);
-        unsigned* dst = reinterpret_cast<unsigned*>(o.desc);
-        for (int k = tid; k < min(n, kLwGather) * 8; k += kLwGather) {
-            const size_t at = row0 + (k >> 3);
-            dst[at * 8 + (k & 7)] = src[(size_t)o.pts[at] * 8 + (k & 7)];
-        }
-    }
+    const PoolGather g{pos, nullptr, normal, dist, desc, o.pos, nullptr, o.normal, o.dist, o.desc};
+    if (tid < n) g.rows(row0 + tid, (size_t)o.pts[row0 + tid]);
+    g.descriptors<kLwGather>(min(n, kLwGather), tid, [&](int e, size_t* at) { return o.pts[*at = row0 + e]; });
 }
 
 __global__ __launch_bounds__(kLwThreads) void loop_bow_merge_kernel(LwMergeArgs a) {
@@ -254,36 +176,24 @@ __global__ __launch_bounds__(kLwThreads) void loop_bow_merge_kernel(LwMergeArgs 
 
     if (tid < kLwBow) {  // a bad member was not searched (:820): its vector is empty
         const int s = tid < J ? a.win[(size_t)q * kLwWin + tid] : -1;
-        const bool ok = lw_slot(t, s) && !t.kf_bad[s];
+        const bool ok = in_range(s, t.K) && !t.kf_bad[s];
         s_slot[tid] = ok ? s : -1;
-        s_nt[tid] = ok ? clampi(t.ntab[s], 0, t.cap) : 0;
+        s_nt[tid] = ok ? t.v.len(s) : 0;
     }
     if (tid == 0) s_num = 0;
     __syncthreads();
-    unsigned* first = t.first + (size_t)q * t.n;
+    unsigned* first = t.first + (size_t)q * t.v.n;
     const int* m12 = a.m12 + (size_t)q * kLwBow * a.cap1;
     // the MapPoint of member j's match for k, -1 where :846 skips
     auto point = [&](int j, int k) {
         const int s = s_slot[j];
-        if (s < 0) return -1;
-        const int m = m12[(size_t)j * a.cap1 + k];
-        if ((unsigned)m >= (unsigned)s_nt[j]) return -1;
-        const int p = t.tab[(size_t)s * t.cap + m];
-        return lw_point(t, p) ? p : -1;
+        return s < 0 ? -1 : t.v.at(s, m12[(size_t)j * a.cap1 + k], s_nt[j]);
     };
-    const unsigned total = (unsigned)J * (unsigned)n1;
-    for (int pass = 0; pass < 2; ++pass) {
-        for (unsigned e = tid; e < total; e += kLwThreads) {
-            const int j = (int)(e / (unsigned)n1), k = (int)(e - (unsigned)j * (unsigned)n1);
-            const int p = point(j, k);
-            if (p < 0) continue;
-            if (pass == 0)
-                first[p] = kLwNone;
-            else
-                atomicMin(first + p, e);
-        }
-        __syncthreads();
-    }
+    const auto at_position = [&](unsigned e) {
+        const int j = (int)(e / (unsigned)n1);
+        return point(j, (int)(e - (unsigned)j * (unsigned)n1));
+    };
+    first_mark<kLwThreads>((unsigned)J * (unsigned)n1, first, at_position, true);
     int won = 0;
     for (int k = tid; k < n1; k += kLwThreads) {
         int cell = -1, owner = -1;
@@ -298,8 +208,7 @@ __global__ __launch_bounds__(kLwThreads) void loop_bow_merge_kernel(LwMergeArgs 
         a.matched_mp[(size_t)q * a.cap1 + k] = cell;
         a.matched_kf[(size_t)q * a.cap1 + k] = owner;
     }
-    won = wave_sum(won);
-    if ((tid & (kWave - 1)) == 0 && won) atomicAdd(&s_num, won);
+    block_add(won, &s_num, tid);
     __syncthreads();
     if (tid == 0) a.num[q] = s_num;
 }
@@ -318,15 +227,11 @@ static int lw_tables(int n_queries, const plvi_cull_keyframes* kf, const plvi_lo
     const long long rows = kf->kf_cap > kLwWin ? kf->kf_cap : kLwWin;
     if (rows * kf->kp_cap > PLVI_LOCAL_MAP_MAX_ENTRIES) return PLVI_E_CAPACITY;
     t->K = kf->kf_cap;
-    t->cap = kf->kp_cap;
     t->cand_stride = kf->cand_stride;
-    t->n = mp->n;
     t->kf_bad = kf->bad;
-    t->tab = kf->mp;
-    t->ntab = kf->nmp;
+    t->v = KfTable{kf->mp, kf->nmp, kf->kp_cap, mp->n, mp->bad};
     t->cand = kf->cand;
     t->n_cand = kf->n_cand;
-    t->p_bad = mp->bad;
     return PLVI_OK;
 }
 

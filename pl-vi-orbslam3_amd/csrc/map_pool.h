@@ -1,6 +1,6 @@
-// map_pool.h — what the local-map update and the covisibility graph share
-// about a plvi_local_map_pool: its argument check, its staging for their
-// host forms, and the keyframe vote over its observation lists.
+// map_pool.h — what the map-side modules share about a plvi_local_map_pool:
+// its argument check, its staging for their host forms, the keyframe vote
+// over its observation lists, and the gather of its attribute rows.
 #pragma once
 #include "host_stage.h"
 
@@ -44,5 +44,53 @@ __device__ __forceinline__ void vote_observations(int* hist, int K, const int* o
         if ((unsigned)kf < (unsigned)K) atomicAdd(hist + kf, 1);
     }
 }
+
+// The attribute gather of lm_write_kernel (local_map.hip) and loop_gather_kernel (loop_window.hip):
+// pool rows into the rows of a list, in the layouts of plvi_frustum_*_batch.  A null destination is
+// skipped; its source is then not read.
+struct PoolGather {
+    const float* pos;
+    const double* sep;
+    const float *normal, *dist;
+    const uint8_t* desc;
+    float* o_pos;
+    double* o_sep;
+    float *o_normal, *o_dist;
+    uint8_t* o_desc;
+
+    // one thread: the pos / sep / normal / dist rows of pool entry id into list row `at`
+    __device__ __forceinline__ void rows(size_t at, size_t id) const {
+        if (o_pos) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) o_pos[3 * at + k] = pos[3 * id + k];
+        }
+        if (o_sep) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) o_sep[6 * at + k] = sep[6 * id + k];
+        }
+        if (o_normal) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) o_normal[3 * at + k] = normal[3 * id + k];
+        }
+        if (o_dist) {
+            o_dist[2 * at] = dist[2 * id];
+            o_dist[2 * at + 1] = dist[2 * id + 1];
+        }
+    }
+
+    // NT threads: n descriptors, 32-byte rows as 8 dwords, 8 consecutive lanes a row.  row(e, &at) is
+    // the pool id of the e-th and sets its list row, or is negative to skip it.
+    template <int NT, class Row>
+    __device__ __forceinline__ void descriptors(int n, int tid, Row row) const {
+        if (!o_desc) return;
+        const unsigned* src = reinterpret_cast<const unsigned*>(desc);
+        unsigned* dst = reinterpret_cast<unsigned*>(o_desc);
+        for (int k = tid; k < n * 8; k += NT) {
+            size_t at;
+            const int id = row(k >> 3, &at);
+            if (id >= 0) dst[at * 8 + (k & 7)] = src[(size_t)id * 8 + (k & 7)];
+        }
+    }
+};
 
 }  // namespace plvi

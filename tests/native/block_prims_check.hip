@@ -1,6 +1,7 @@
 // block_prims_check.hip -- every primitive of csrc/block_prims.h in a one-workgroup kernel
-// against the host: block_scan and block_scan_array vs std::partial_sum, bitonic_sort vs
-// std::sort, hamming256 vs a bit loop, pow2_at_least vs its definition.  Exact equality.
+// against the host: block_scan and block_scan_array vs std::partial_sum, block_add vs
+// std::accumulate, bitonic_sort vs std::sort, hamming256 vs a bit loop, pow2_at_least vs its
+// definition.  Exact equality.
 // Exit 0 = every case identical.  Test infrastructure.
 #include <algorithm>
 #include <cstdio>
@@ -91,6 +92,39 @@ static void check_scan() {
             for (int t = 0; t < NT; ++t)
                 ok &= out[t] == ea[t] && out[NT + t] == eb[t] && out[2 * NT + t] == ea[NT] && out[3 * NT + t] == eb[NT];
             report(ok, "block_scan", NW, ka, kb);
+        }
+}
+
+// ---------------------------------------------------------------- block_add
+// two counters through the one pattern of the callers: initialise, barrier, add, barrier, read
+template <int NW>
+__global__ __launch_bounds__(NW * kWave) void add_kernel(const int* a, const int* b, int* out) {
+    __shared__ int s_cnt[2];
+    const int tid = threadIdx.x;
+    if (tid == 0) s_cnt[0] = s_cnt[1] = 0;
+    __syncthreads();
+    block_add(a[tid], &s_cnt[0], tid);
+    block_add(b[tid], &s_cnt[1], tid);
+    __syncthreads();
+    out[tid] = s_cnt[0];
+    out[NW * kWave + tid] = s_cnt[1];
+}
+
+template <int NW>
+static void check_add() {
+    const int NT = NW * kWave;
+    for (int ka = 0; ka < 3; ++ka)
+        for (int kb = 0; kb < 3; ++kb) {
+            std::vector<int> a = scan_input(NT, ka), b = scan_input(NT, kb);
+            if (kb == 2) std::fill(b.begin(), b.begin() + kWave, 0);  // a wave of zeros among the others
+            Dev<int> da(a), db(b), dout((size_t)2 * NT);
+            hipLaunchKernelGGL(add_kernel<NW>, dim3(1), dim3(NT), 0, nullptr, da.p, db.p, dout.p);
+            HIP_OK(hipDeviceSynchronize());
+            const std::vector<int> out = dout.get();
+            const int ea = std::accumulate(a.begin(), a.end(), 0), eb = std::accumulate(b.begin(), b.end(), 0);
+            bool ok = true;
+            for (int t = 0; t < NT; ++t) ok &= out[t] == ea && out[NT + t] == eb;
+            report(ok, "block_add", NW, ka, kb);
         }
 }
 
@@ -262,6 +296,9 @@ int main() {
     check_scan<4>();
     check_scan<8>();   // tri_match_kernel's 512 threads
     check_scan<16>();  // kfdb_select_kernel's 1024
+    check_add<1>();
+    check_add<4>();   // lm_count_kernel's 256 threads
+    check_add<16>();  // ba_window_kernel's and loop_bow_merge_kernel's 1024
     check_scan_array();
     check_sorts<64>();
     check_sorts<256>();

@@ -1,5 +1,5 @@
 """The wave / workgroup primitives of csrc/block_prims.h (hamming256, wave_sum, wave_incl_scan,
-block_scan, block_scan_array, bitonic_sort, pow2_at_least) against the host, each in a one-workgroup
+block_scan, block_add, block_scan_array, bitonic_sort, pow2_at_least) against the host, each in a one-workgroup
 kernel: tests/native/block_prims_check.hip."""
 import pathlib
 import subprocess
@@ -31,6 +31,7 @@ def test_block_prims_check_builds():
 @pytest.mark.gpu
 def test_block_prims_match_host():
     """block_scan<1, 4, 8, 16> twice back to back through one s_wave (all zero / all one / a 0, 1, large mix),
+    block_add into two counters by 1, 4 and 16 waves (all zero / all one / a mix with a wave of zeros),
     block_scan_array at n = 0, 1, 255, 256, 257, 481, 3073, bitonic_sort of unsigned and 64-bit keys with and
     without a carried val at n = 2, 256, 512, 8192 by 64, 256 and 1024 threads (duplicates, a ~0 padding tail;
     with val every (key, val) pair survives), both hamming256 overloads at distances 0, 1, 255, 256 and others,
