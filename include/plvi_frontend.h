@@ -1720,6 +1720,12 @@ int plvi_covis_weight_batch(plvi_covis_graph* h, int n, const int* d_a, const in
  * [kf_cap] (GetVectorCovisibleKeyFrames without a copy); each may be NULL. */
 int plvi_covis_rows(plvi_covis_graph* h, const int** d_ord_kf, const int** d_ord_w, const int** d_ord_n, int* conn_cap);
 
+/* The twin for the weight maps: device pointers to the key and weight tables
+ * [kf_cap][conn_cap], rows unsorted, and their counts [kf_cap]
+ * (mConnectedKeyFrameWeights without a copy); each may be NULL. */
+int plvi_covis_map_rows(plvi_covis_graph* h, const int** d_map_kf, const int** d_map_w, const int** d_map_n,
+                        int* conn_cap);
+
 /* Host copies of one slot, synchronous: the map in ascending slot order, the
  * ordered list as stored; tables of conn_cap entries, each may be NULL. */
 int plvi_covis_download(plvi_covis_graph* h, int slot, int* map_kf, int* map_w, int* n_map, int* ord_kf, int* ord_w,
@@ -2274,6 +2280,243 @@ int plvi_loop_window(const plvi_cull_keyframes* kf, const plvi_local_map_pool* m
 int plvi_loop_bow_merge(const plvi_cull_keyframes* kf, const plvi_local_map_pool* mp, const int* win,
                         const int* n_win, const int* abort_at, const int* matches12, const int* n1, int cap1,
                         int* matched_mp, int* matched_kf, int* num);
+
+/* -------------------------------------------------------- Essential graph
+ * The integer work of LoopClosing::CorrectLoop[WithLines]
+ * (src/LoopClosing.cc:1212-1473, :1475-1712) and of
+ * Optimizer::OptimizeEssentialGraph / OptimizeEssentialGraph4DoF
+ * (src/Optimizer.cc:6952-7305, :14411-) around the Sim3 arithmetic and the
+ * solver: the corrected window with the keyframe that corrects each MapPoint
+ * / MapLine first (plvi_loop_correct), and the vertex list, the ordered edge
+ * list and the reference keyframe of every feature (plvi_essential_graph).
+ * Integers only; every output equals the reference's.  One loop closure per
+ * call.  Every Sim3 / cv::Mat product, the measurements and information
+ * matrices, the solver, SetPose and UpdateNormalAndDepth stay with the caller.
+ *
+ * Tables.  plvi_cull_keyframes is read for kf_cap, kp_cap / kl_cap, bad,
+ * init_kf, mp / nmp, ml / nml, cand / n_cand / cand_stride (the ordered rows
+ * of plvi_covis_rows in place), kf_id, prev_kf and next_kf; the last three are
+ * required here.  The pools are read for n and bad.  plvi_eg_keyframes adds
+ * what the two functions read besides; plvi_eg_features is one per pool.
+ * Distinct slots have distinct kf_id (the reference keys sInsertedEdges and
+ * the cur / loop exemption by mnId; here both go by slot).
+ *
+ * Address order.  `order` models every std::set<KeyFrame*> and std::map<
+ * KeyFrame*, ...> iteration: a slot named twice counts at its first position,
+ * a slot in [0, kf_cap) that `order` does not name sorts above the named ones,
+ * by slot.
+ *
+ * plvi_loop_correct (:1252-1253, :1294-1345; the points-only twin :1557-1586:
+ * ml == NULL or kf->ml == NULL selects CorrectLoop).
+ *   1. win = the cand row of cur_slot as stored, then cur_slot
+ *      (mvpCurrentConnectedKFs).  An entry outside [0, kf_cap) is listed as
+ *      stored and contributes nothing.  No isBad() and no map test (:1294).
+ *   2. win_sorted = the distinct members in range, in address order (the
+ *      iteration of CorrectedSim3).
+ *   3. The members of win_sorted are walked in order, each one's mp row in
+ *      index order.  An entry is listed in pts, with the member in pts_kf, iff
+ *      it is not NULL, in range, not bad, corr_by[id] != kf_id[cur_slot] on
+ *      entry, and was not met earlier in the walk.  Lines likewise over ml.
+ *   4. Every listed feature is stamped: corr_by[id] = kf_id[cur_slot],
+ *      corr_ref[id] = the member -- past pt_cap / ln_cap too: the stamp is
+ *      state, not a list.  A NULL features struct, or a NULL corr_by in it,
+ *      means nothing is stamped on entry and nothing is written.
+ *
+ * plvi_essential_graph.  M = map_id[cur_slot]; vpKFs = the entries of `order`
+ * (first positions, in range) whose map is M, in order.  win / n_win [1] are
+ * those of plvi_loop_correct (n_win under the count contract against
+ * win_cap); lc_kf [win_cap][lc_cap] / n_lc [win_cap] hold LoopConnections by
+ * window position, each row in address order.  A slot at two positions is
+ * read at its last one (LoopConnections[pKFi] = overwrites).
+ *   1. Vertices (:6985-7021, :14442-14479): the members of vpKFs that are not
+ *      bad, in order.  vert_flags bit 0 = fixed (init_kf in 7DOF, slot ==
+ *      loop_slot in 4DOF), bit 1 = the slot is a window member (its estimate
+ *      comes from CorrectedSim3).
+ *   2. Loop-connection edges (:7030-7058): keys = the distinct window slots in
+ *      range, in address order; each key's row in its order.  The pair (i, j)
+ *      is skipped iff !(i == cur_slot && j == loop_slot) and GetWeight(i, j) <
+ *      PLVI_EG_MIN_FEAT (the map rows, 0 if absent); an entry outside [0,
+ *      kf_cap) is skipped.  Otherwise edge LOOPCONN (i, j), and the unordered
+ *      pair counts as inserted.
+ *   3. Normal edges, for every member i of vpKFs in order -- a bad one too
+ *      (:7068 has no isBad()).  parent, loop and prev_kf entries outside [0,
+ *      kf_cap) are read as NULL.
+ *      7DOF: TREE (i, parent); LOOP (i, l) for l in i's loop row in order with
+ *        kf_id[l] < kf_id[i]; COVIS (i, n) for n in the prefix of i's ordered
+ *        row with weight >= PLVI_EG_MIN_FEAT (the rule of
+ *        plvi_covis_by_weight_batch) in order, with n in range, n != parent,
+ *        not a child of i, not in i's loop row, not bad, kf_id[n] < kf_id[i]
+ *        and the pair not inserted; INERTIAL (i, prev_kf) if imu[i].
+ *      4DOF: no TREE edge and no parent test (pParentKF is a literal NULL,
+ *        :14545); INERTIAL (i, prev_kf) first, without the imu test; then
+ *        LOOP; then COVIS with the extra tests n != prev_kf[i] and n !=
+ *        next_kf[i].
+ *   4. edge_a is vertex 0 (i), edge_b vertex 1.  n_edges [5] counts by kind;
+ *      the edge list is their sum long.  PLVI_EG_ERR_NO_VERTEX is set when an
+ *      emitted edge names a slot that is not a vertex (bad, or outside vpKFs:
+ *      the reference hands g2o a null vertex); the edge is emitted all the
+ *      same.
+ *   5. pt_ref [mp->n] / ln_ref [ml->n] (optional; :7235-7301): -1 for a bad
+ *      feature or one outside map M; else, in 7DOF, corr_by[id] ==
+ *      kf_id[cur_slot] ? corr_ref[id] : ref_kf[id]; in 4DOF ref_kf[id].
+ *
+ * Outputs follow the count contract: every count is a full length, nothing is
+ * written at or past a capacity, err is written by every call.
+ *
+ * Limits.  cand_stride and win_cap <= PLVI_EG_MAX_WIN - 1 resp.
+ * PLVI_EG_MAX_WIN (the window is sorted in LDS), PLVI_EG_MAX_WIN * max(kp_cap,
+ * kl_cap) <= PLVI_LOCAL_MAP_MAX_ENTRIES, kf_cap <= 2^24, n_order <= 2^30;
+ * PLVI_E_CAPACITY beyond.  No bound on kf_cap from LDS, none on the pools. */
+#define PLVI_EG_MAX_WIN (PLVI_COVIS_MAX_CONN + 1) /* longest window */
+#define PLVI_EG_MIN_FEAT 100                      /* minFeat of Optimizer.cc:6982 / :14440 */
+enum { /* mode */
+  PLVI_EG_7DOF = 0, /* OptimizeEssentialGraph */
+  PLVI_EG_4DOF = 1, /* OptimizeEssentialGraph4DoF */
+};
+enum { /* edge_kind, and the index into n_edges */
+  PLVI_EG_EDGE_LOOPCONN = 0,
+  PLVI_EG_EDGE_TREE = 1,
+  PLVI_EG_EDGE_LOOP = 2,
+  PLVI_EG_EDGE_COVIS = 3,
+  PLVI_EG_EDGE_INERTIAL = 4,
+};
+enum { /* err, bits */
+  PLVI_EG_ERR_WIN = 1,        /* the window is longer than win_cap */
+  PLVI_EG_ERR_PTS = 2,        /* the point list is longer than pt_cap */
+  PLVI_EG_ERR_LNS = 4,        /* the line list is longer than ln_cap */
+  PLVI_EG_ERR_QUERY = 8,      /* cur_slot (or loop_slot) outside [0, kf_cap): every count is 0, nothing else written */
+  PLVI_EG_ERR_VERT = 16,      /* more vertices than vert_cap */
+  PLVI_EG_ERR_EDGE = 32,      /* more edges than edge_cap */
+  PLVI_EG_ERR_NO_VERTEX = 64, /* an emitted edge names a slot that is not a vertex */
+  PLVI_EG_ERR_LC = 128,       /* a row of LoopConnections is longer than lc_cap */
+};
+
+/* The keyframe side besides plvi_cull_keyframes, by slot. */
+typedef struct plvi_eg_keyframes {
+  int n_order;          /* entries of order */
+  int map_stride;       /* row length of map_kf / map_w */
+  const int* order;     /* [n_order] the occupied slots in ascending address, as in plvi_covis_keyframes */
+  const int* map_id;    /* [kf_cap] GetMap() as an id; NULL = one map */
+  const int* parent;    /* [kf_cap] GetParent() or -1; NULL = none */
+  const int* child_off; /* [kf_cap + 1] CSR of GetChilds(), membership only; NULL (both) = none */
+  const int* child;
+  const int* loop_off;  /* [kf_cap + 1] CSR of GetLoopEdges() in std::set<KeyFrame*> order; NULL (both) = none */
+  const int* loop;
+  const uint8_t* imu;   /* [kf_cap] bImu; NULL = 0 */
+  const int* cand_w;    /* [kf_cap][cand_stride] mvOrderedWeights: d_ord_w of plvi_covis_rows in place */
+  const int* map_kf;    /* [kf_cap][map_stride] the keys of mConnectedKeyFrameWeights, unsorted: */
+  const int* map_w;     /* [kf_cap][map_stride] plvi_covis_map_rows in place */
+  const int* map_n;     /* [kf_cap] */
+} plvi_eg_keyframes;
+
+/* One per pool, by id. */
+typedef struct plvi_eg_features {
+  const int* ref_kf;  /* [n] GetReferenceKeyFrame() as a slot */
+  unsigned* corr_by;  /* [n] mnCorrectedByKF, in/out */
+  int* corr_ref;      /* [n] mnCorrectedReference as a slot, in/out; required with corr_by */
+  const int* map_id;  /* [n] GetMap() as an id; NULL = one map */
+} plvi_eg_features;
+
+typedef struct plvi_loop_correct_outputs {
+  int win_cap, pt_cap, ln_cap;
+  int* win;        /* [win_cap] mvpCurrentConnectedKFs as slots */
+  int* n_win;      /* [1] */
+  int* win_sorted; /* [win_cap] the distinct members in range, in address order */
+  int* n_sorted;   /* [1] */
+  int* pts;        /* [pt_cap] the MapPoints corrected, in traversal order */
+  int* pts_kf;     /* [pt_cap] the member that corrects each */
+  int* n_pts;      /* [1] */
+  int* lns;        /* [ln_cap] */
+  int* lns_kf;     /* [ln_cap] */
+  int* n_lns;      /* [1]; 0 without lines */
+  int* err;        /* [1] PLVI_EG_ERR_* */
+} plvi_loop_correct_outputs;
+
+typedef struct plvi_eg_outputs {
+  int vert_cap, edge_cap;
+  int* vert;       /* [vert_cap] slots */
+  int* vert_flags; /* [vert_cap] bit 0 fixed, bit 1 window member */
+  int* n_vert;     /* [1] */
+  int* edge_a;     /* [edge_cap] vertex 0 */
+  int* edge_b;     /* [edge_cap] vertex 1 */
+  int* edge_kind;  /* [edge_cap] PLVI_EG_EDGE_* */
+  int* n_edges;    /* [5] by kind */
+  int* pt_ref;     /* [mp->n]; may be NULL; needs fmp */
+  int* ln_ref;     /* [ml->n]; may be NULL; needs ml and fml */
+  int* err;        /* [1] PLVI_EG_ERR_* */
+} plvi_eg_outputs;
+
+/* Bytes of the scratch blocks: a rank table by slot plus, for the correction,
+ * a first-occurrence table by pool id; for the graph, the last window
+ * position by slot, two counts per entry of order and a flag per cell of
+ * lc_kf.  0 for a negative argument. */
+size_t plvi_loop_correct_scratch_bytes(int kf_cap, int mp_n, int ml_n);
+size_t plvi_essential_graph_scratch_bytes(int kf_cap, int n_order, int win_cap, int lc_cap);
+
+/* The device forms.  The structs are host memory, read before the call
+ * returns; their pointers are device pointers.  PLVI_E_BADARG for a negative
+ * size, a missing required pointer (everything not marked optional; a list
+ * with capacity 0 may be NULL), a CSR given in part, corr_by without corr_ref,
+ * an unknown mode or a scratch block below its size.  d_scratch needs no
+ * initialisation; calls that share it must be ordered.  Asynchronous on
+ * `stream`, no host read of device data, no allocation: capturable.
+ * plvi_loop_correct_device reads of eg only order / n_order.  One 1024-thread
+ * workgroup walks the window; the normal edges run a wave per entry of
+ * order. */
+int plvi_loop_correct_device(int cur_slot, const plvi_cull_keyframes* kf, const plvi_eg_keyframes* eg,
+                             const plvi_local_map_pool* mp, const plvi_local_map_pool* ml,
+                             const plvi_eg_features* fmp, const plvi_eg_features* fml,
+                             const plvi_loop_correct_outputs* out, void* d_scratch, size_t scratch_bytes,
+                             void* stream);
+int plvi_essential_graph_device(int cur_slot, int loop_slot, int mode, const int* d_win, const int* d_n_win,
+                                int win_cap, const int* d_lc_kf, const int* d_n_lc, int lc_cap,
+                                const plvi_cull_keyframes* kf, const plvi_eg_keyframes* eg,
+                                const plvi_local_map_pool* mp, const plvi_local_map_pool* ml,
+                                const plvi_eg_features* fmp, const plvi_eg_features* fml, const plvi_eg_outputs* out,
+                                void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* LoopConnections (:1406-1424) on a covisibility graph, between the two calls
+ * above.  win [n_win] is host memory in both forms (the caller has it: it
+ * computes a pose per member).  For each window position p in order whose
+ * slot is in range: the slot's ordered row is copied to scratch row p
+ * (vpPreviousNeighbors: it sees the updates of the positions before p), then
+ * plvi_covis_update_batch runs for that one query with its outputs at index p
+ * of `out` (arrays of n_win entries; the cells of a position that names no
+ * slot are not written).  After the last position, per position:
+ *   lc_kf[p] = the keys of the slot's weight map minus scratch row p minus
+ *   every window member, in address order (kf->order); n_lc[p] its full
+ *   length, 0 for a position that names no slot.
+ * Taking the keys after the last update is exact: an update rewrites the map
+ * of its own keyframe only, from a counter that does not depend on connection
+ * state, and otherwise adds the updated keyframe -- a window member, erased
+ * anyway -- to other maps.  d_err [1] has PLVI_EG_ERR_LC when a row is longer
+ * than lc_cap; the graph's own overflow is out->err[p].  A slot at two
+ * positions gets two rows.  kf / mp / ml / out as for
+ * plvi_covis_update_batch; n_win <= PLVI_EG_MAX_WIN.  The scratch block is
+ * plvi_covis_scratch_bytes(1, kf_cap) plus a rank table, the window and the
+ * snapshot rows.  The device form is capturable like the batch call. */
+size_t plvi_loop_connections_scratch_bytes(int n_win, int kf_cap, int conn_cap);
+int plvi_loop_connections_device(plvi_covis_graph* h, int n_win, const int* win, const plvi_covis_keyframes* kf,
+                                 const plvi_local_map_pool* mp, const plvi_local_map_pool* ml,
+                                 const plvi_covis_outputs* out, int lc_cap, int* d_lc_kf, int* d_n_lc, int* d_err,
+                                 void* d_scratch, size_t scratch_bytes, void* stream);
+/* ... from host tables, synchronous: first_conn, parent and covis are updated
+ * in place.  Returns 0, PLVI_E_CAPACITY when err[0] != 0, or another error. */
+int plvi_loop_connections(plvi_covis_graph* h, int n_win, const int* win, const plvi_covis_keyframes* kf,
+                          const plvi_local_map_pool* mp, const plvi_local_map_pool* ml, const plvi_covis_outputs* out,
+                          int lc_cap, int* lc_kf, int* n_lc, int* err);
+
+/* The host forms, synchronous: the same structs and arrays with host pointers
+ * (corr_by / corr_ref are updated in place).  Return 0, PLVI_E_CAPACITY when
+ * err has a bit other than PLVI_EG_ERR_NO_VERTEX (everything is still
+ * written), or another error. */
+int plvi_loop_correct(int cur_slot, const plvi_cull_keyframes* kf, const plvi_eg_keyframes* eg,
+                      const plvi_local_map_pool* mp, const plvi_local_map_pool* ml, const plvi_eg_features* fmp,
+                      const plvi_eg_features* fml, const plvi_loop_correct_outputs* out);
+int plvi_essential_graph(int cur_slot, int loop_slot, int mode, const int* win, const int* n_win, int win_cap,
+                         const int* lc_kf, const int* n_lc, int lc_cap, const plvi_cull_keyframes* kf,
+                         const plvi_eg_keyframes* eg, const plvi_local_map_pool* mp, const plvi_local_map_pool* ml,
+                         const plvi_eg_features* fmp, const plvi_eg_features* fml, const plvi_eg_outputs* out);
 
 /* ---------------------------------------------------------------- Stereo
  * Rectified stereo of the stereo Frame constructors (src/Frame.cc:95-140,

@@ -611,6 +611,16 @@ extern "C" int plvi_covis_rows(plvi_covis_graph* h, const int** d_ord_kf, const 
     return PLVI_OK;
 }
 
+extern "C" int plvi_covis_map_rows(plvi_covis_graph* h, const int** d_map_kf, const int** d_map_w, const int** d_map_n,
+                                   int* conn_cap) {
+    if (!h) return PLVI_E_BADARG;
+    if (d_map_kf) *d_map_kf = h->g.map_kf;
+    if (d_map_w) *d_map_w = h->g.map_w;
+    if (d_map_n) *d_map_n = h->g.map_n;
+    if (conn_cap) *conn_cap = h->g.C;
+    return PLVI_OK;
+}
+
 extern "C" int plvi_covis_download(plvi_covis_graph* h, int slot, int* map_kf, int* map_w, int* n_map, int* ord_kf,
                                    int* ord_w, int* n_ord, int* err) {
     if (!h || slot < 0 || slot >= h->g.K) return PLVI_E_BADARG;

@@ -1862,6 +1862,14 @@ class Covisibility:
         _call("plvi_covis_rows", self.h, *[ctypes.byref(x) for x in p], ctypes.byref(c))
         return tuple(x.value for x in p)
 
+    def map_rows(self):
+        """(map_kf, map_w, map_n) device addresses of the weight-map tables [kf_cap][conn_cap], rows unsorted, and
+        their counts."""
+        p = [ctypes.c_void_p() for _ in range(3)]
+        c = ctypes.c_int()
+        _call("plvi_covis_map_rows", self.h, *[ctypes.byref(x) for x in p], ctypes.byref(c))
+        return tuple(x.value for x in p)
+
     def download(self, slot, fill=-7):
         """One slot's state: dict(map_kf, map_w (ascending slot), ord_kf, ord_w (as stored), err).  The arrays are
         conn_cap + 1 long and sentinel-filled past their counts n_map / n_ord."""
@@ -2457,3 +2465,329 @@ class LoopWindow:
         r = {k: a[:1] for k, a in res.items()}
         r.update(rc=rc, past={k: a[1].tolist() for k, a in res.items()})
         return r
+
+
+EG_MAX_WIN = COVIS_MAX_CONN + 1  # PLVI_EG_MAX_WIN: longest window
+EG_MIN_FEAT = 100                # PLVI_EG_MIN_FEAT: minFeat of OptimizeEssentialGraph
+EG_7DOF, EG_4DOF = 0, 1
+EG_EDGE_LOOPCONN, EG_EDGE_TREE, EG_EDGE_LOOP, EG_EDGE_COVIS, EG_EDGE_INERTIAL = range(5)
+(EG_ERR_WIN, EG_ERR_PTS, EG_ERR_LNS, EG_ERR_QUERY, EG_ERR_VERT, EG_ERR_EDGE, EG_ERR_NO_VERTEX,
+ EG_ERR_LC) = (1 << i for i in range(8))
+
+_EG_CULL = ("bad", "init_kf", "mp", "nmp", "ml", "nml", "cand", "n_cand", "kf_id", "prev_kf", "next_kf")
+_EG_KF = {"order": np.int32, "map_id": np.int32, "parent": np.int32, "child_off": np.int32, "child": np.int32,
+          "loop_off": np.int32, "loop": np.int32, "imu": np.uint8, "cand_w": np.int32, "map_kf": np.int32,
+          "map_w": np.int32, "map_n": np.int32}
+_EG_FEAT = {"ref_kf": np.int32, "corr_by": np.uint32, "corr_ref": np.int32, "map_id": np.int32}
+_EG_CORRECT_LISTS = {"win": "win_cap", "win_sorted": "win_cap", "pts": "pt_cap", "pts_kf": "pt_cap", "lns": "ln_cap",
+                     "lns_kf": "ln_cap"}
+_EG_CORRECT_N = ("n_win", "n_sorted", "n_pts", "n_lns", "err")
+_EG_GRAPH_LISTS = {"vert": "vert_cap", "vert_flags": "vert_cap", "edge_a": "edge_cap", "edge_b": "edge_cap",
+                   "edge_kind": "edge_cap"}
+
+
+class EgKeyframes(ctypes.Structure):
+    """plvi_eg_keyframes."""
+    _fields_ = [("n_order", _LM_I), ("map_stride", _LM_I)] + [(k, _LM_V) for k in _EG_KF]
+
+
+class EgFeatures(ctypes.Structure):
+    """plvi_eg_features."""
+    _fields_ = [(k, _LM_V) for k in _EG_FEAT]
+
+
+class LoopCorrectOutputs(ctypes.Structure):
+    """plvi_loop_correct_outputs."""
+    _fields_ = [("win_cap", _LM_I), ("pt_cap", _LM_I), ("ln_cap", _LM_I)] + \
+               [(k, _LM_V) for k in ("win", "n_win", "win_sorted", "n_sorted", "pts", "pts_kf", "n_pts", "lns",
+                                     "lns_kf", "n_lns", "err")]
+
+
+class EgOutputs(ctypes.Structure):
+    """plvi_eg_outputs."""
+    _fields_ = [("vert_cap", _LM_I), ("edge_cap", _LM_I)] + \
+               [(k, _LM_V) for k in ("vert", "vert_flags", "n_vert", "edge_a", "edge_b", "edge_kind", "n_edges",
+                                     "pt_ref", "ln_ref", "err")]
+
+
+class EssentialGraph:
+    """The integer work of LoopClosing::CorrectLoop[WithLines] and Optimizer::OptimizeEssentialGraph[4DoF] over
+    resident tables: the corrected window and the correction owners (plvi_loop_correct), LoopConnections
+    (plvi_loop_connections) and the vertices, edges and feature references (plvi_essential_graph).
+
+    ``keyframes``: a dict of numpy arrays named as the fields of plvi_cull_keyframes (bad, mp / nmp, cand / n_cand,
+    kf_id, prev_kf, next_kf and optionally init_kf, ml / nml) and of plvi_eg_keyframes (order, cand_w, map_kf /
+    map_w / map_n and optionally map_id, parent, child_off / child, loop_off / loop, imu).  ``points`` / ``lines``:
+    dicts with bad and optionally ref_kf, corr_by, corr_ref, map_id.  ``rows``: a dict of device addresses cand,
+    n_cand, cand_w, map_kf, map_w, map_n and their row length ``stride`` (Covisibility.rows() and .map_rows()),
+    which replace those six tables in the device forms: the graph's rows are read in place.
+
+    The ``*_device`` methods run on device copies (``self.dev``; the stamps written by ``correct_device`` are read
+    by ``graph_device``), the ``*_host`` methods go through the host forms and update the host arrays in place.
+    Each returns a dict of its outputs, sentinel-filled where nothing was written, plus "rc"; the device forms add
+    "dev" (the device address of every output) and, with run=False, return (step(stream), fetch()) instead."""
+
+    def __init__(self, keyframes, points, lines=None, rows=None):
+        self._lib = load()
+        self.kf = {k: _table(keyframes[k], _CULL_KF[k]) for k in _EG_CULL if keyframes.get(k) is not None}
+        self.eg = {k: _table(keyframes[k], dt) for k, dt in _EG_KF.items() if keyframes.get(k) is not None}
+        feat = lambda p: None if p is None else (  # noqa: E731
+            {"bad": _table(p["bad"], np.uint8)},
+            {k: _table(p[k], dt) for k, dt in _EG_FEAT.items() if p.get(k) is not None})
+        self.pools = [feat(points), feat(lines)]
+        self.kf_cap = len(self.kf["bad"])
+        self.rows = rows
+        self.dev = None
+
+    def _tables(self):
+        t = {("kf", k): a for k, a in self.kf.items()}
+        t.update({("eg", k): a for k, a in self.eg.items()})
+        for g, p in zip(("mp", "ml"), self.pools):
+            if p is not None:
+                t[(g, "bad")] = p[0]["bad"]
+                t.update({("f" + g, k): a for k, a in p[1].items()})
+        return t
+
+    def _check_tables(self):
+        """Every companion array has the length its table gives it: refused here, before the library reads them."""
+        K = self.kf_cap
+        _same_len(K, **{"keyframes." + k: a for k, a in self.kf.items()})
+        _same_len(K, **{"keyframes." + k: a for k, a in self.eg.items()
+                        if k not in ("order", "child_off", "child", "loop_off", "loop")})
+        for off, row in (("child_off", "child"), ("loop_off", "loop")):
+            if (off in self.eg) != (row in self.eg):
+                raise ValueError(f"keyframes.{off} and keyframes.{row} go together")
+            if off in self.eg:
+                _same_len(K + 1, **{"keyframes." + off: self.eg[off]})
+                _same_len(max(int(self.eg[off][K]), 0), **{"keyframes." + row: self.eg[row]})
+        if "cand" in self.kf and "cand_w" in self.eg and self.kf["cand"].shape != self.eg["cand_w"].shape:
+            raise ValueError("keyframes.cand_w has not the shape of keyframes.cand")
+        if "map_kf" in self.eg and self.eg["map_kf"].shape != self.eg.get("map_w", self.eg["map_kf"]).shape:
+            raise ValueError("keyframes.map_w has not the shape of keyframes.map_kf")
+        for name, p in zip(("points", "lines"), self.pools):
+            if p is not None:
+                _same_len(len(p[0]["bad"]), **{f"{name}.{k}": a for k, a in p[1].items()})
+                if ("corr_by" in p[1]) != ("corr_ref" in p[1]):
+                    raise ValueError(f"{name}.corr_by and {name}.corr_ref go together")
+
+    def upload(self):
+        if self.dev is None:
+            tabs = self._tables()
+            self.dev = dict(zip(tabs, _to_device(*tabs.values())[0]))
+        return self.dev
+
+    def _n(self, p):
+        return 0 if self.pools[p] is None else len(self.pools[p][0]["bad"])
+
+    def _structs(self, ptr, rows=None):
+        """(kf, eg, mp, ml, fmp, fml) with the addresses ptr(group, name) gives."""
+        width = lambda d, k: d[k].shape[1] if k in d and d[k].ndim == 2 else 0  # noqa: E731
+        kf = CullKeyframes(self.kf_cap, width(self.kf, "mp"), width(self.kf, "ml"), width(self.kf, "cand"))
+        for k in self.kf:
+            setattr(kf, k, ptr("kf", k))
+        eg = EgKeyframes(len(self.eg.get("order", ())), width(self.eg, "map_kf"))
+        for k in self.eg:
+            setattr(eg, k, ptr("eg", k))
+        if rows:
+            kf.cand_stride = eg.map_stride = rows["stride"]
+            kf.cand, kf.n_cand = rows["cand"], rows["n_cand"]
+            for k in ("cand_w", "map_kf", "map_w", "map_n"):
+                setattr(eg, k, rows[k])
+        pools, feats = [], []
+        for g, p in zip(("mp", "ml"), self.pools):
+            pools.append(None if p is None else LocalMapPool(len(p[0]["bad"]), ptr(g, "bad")))
+            feats.append(None if p is None or not p[1] else EgFeatures(**{k: ptr("f" + g, k) for k in p[1]}))
+        return (kf, eg, *pools, *feats)
+
+    @staticmethod
+    def _outputs(lists, caps, scalars, fill):
+        """Pre-filled host outputs: every list one cell longer than its capacity, every count one int (n_edges 5)."""
+        res = {k: np.full(caps[c] + 1, fill, np.int32) for k, c in lists.items()}
+        res.update({k: np.full(5 if k == "n_edges" else 1, fill, np.int32) for k in scalars})
+        return res
+
+    def _stamps(self, fetch_table):
+        return {f"{name}_{k}": fetch_table("f" + g, k) for g, name, p in zip(("mp", "ml"), ("pt", "ln"), self.pools)
+                if p is not None for k in ("corr_by", "corr_ref") if k in p[1]}
+
+    def _dev_table(self, group, name):
+        a = self._tables()[(group, name)]
+        return self.dev[(group, name)].download(np.empty_like(a))
+
+    # ---- A
+    def _correct_caps(self, win_cap, pt_cap, ln_cap):
+        stride = self.rows["stride"] if self.rows else (self.kf["cand"].shape[1] if "cand" in self.kf else 0)
+        return dict(win_cap=stride + 1 if win_cap is None else win_cap,
+                    pt_cap=max(self._n(0), 1) if pt_cap is None else pt_cap,
+                    ln_cap=max(self._n(1), 1) if ln_cap is None else ln_cap)
+
+    def correct_device(self, cur_slot, win_cap=None, pt_cap=None, ln_cap=None, fill=-7, stream=None, run=True):
+        """plvi_loop_correct_device.  Returns win, win_sorted, pts, pts_kf, lns, lns_kf (capacity + 1 long), the
+        counts and err (one int each), and the stamp tables pt_corr_by, pt_corr_ref, ln_corr_by, ln_corr_ref as
+        they stand on the device afterwards."""
+        self._check_tables()
+        caps = self._correct_caps(win_cap, pt_cap, ln_cap)
+        res = self._outputs(_EG_CORRECT_LISTS, caps, _EG_CORRECT_N, fill)
+        dev = self.upload()
+        structs = self._structs(lambda g, k: dev[(g, k)].ptr, self.rows)
+        obuf = dict(zip(res, _to_device(*res.values())[0]))
+        out = LoopCorrectOutputs(**caps, **{k: b.ptr for k, b in obuf.items()})
+        sb = load().plvi_loop_correct_scratch_bytes(self.kf_cap, self._n(0), self._n(1))
+        scratch = DeviceBuffer(sb)
+
+        def step(s=None):
+            return _status("plvi_loop_correct_device", int(cur_slot), *structs, out, scratch.ptr, sb, s or None)
+
+        def fetch(rc=0):
+            _sync()
+            r = {k: obuf[k].download(a) for k, a in res.items()}
+            r.update(self._stamps(self._dev_table))
+            r.update(rc=rc, keep=(obuf, scratch), dev={k: b.ptr for k, b in obuf.items()})
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
+
+    def correct_host(self, cur_slot, win_cap=None, pt_cap=None, ln_cap=None, fill=-7):
+        """plvi_loop_correct: the same dict; the host arrays corr_by / corr_ref are updated in place.  "rc" is
+        PLVI_E_CAPACITY when err is not 0; any other refusal raises."""
+        self._check_tables()
+        caps = self._correct_caps(win_cap, pt_cap, ln_cap)
+        res = self._outputs(_EG_CORRECT_LISTS, caps, _EG_CORRECT_N, fill)
+        tabs = self._tables()
+        structs = self._structs(lambda g, k: tabs[(g, k)].ctypes.data)
+        out = LoopCorrectOutputs(**caps, **{k: a.ctypes.data for k, a in res.items()})
+        rc = _status("plvi_loop_correct", int(cur_slot), *structs, out)
+        if rc < 0 and rc != PLVI_E_CAPACITY:
+            raise PlviError(rc, "plvi_loop_correct")
+        r = dict(res)
+        r.update(self._stamps(lambda g, k: tabs[(g, k)].copy()))
+        r["rc"] = rc
+        return r
+
+    # ---- B
+    @staticmethod
+    def _connection_outputs(n_win, lc_cap, fill):
+        res = {k: np.full(n_win + 1, fill, np.int32) for k in _COVIS_OUT}
+        res["lc_kf"] = np.full((n_win + 1, max(lc_cap, 1)), fill, np.int32)
+        res["n_lc"] = np.full(n_win + 1, fill, np.int32)
+        res["lc_err"] = np.full(1, fill, np.int32)
+        return res
+
+    @staticmethod
+    def connections_device(cov, win, lc_cap, fill=-7, stream=None, run=True):
+        """plvi_loop_connections_device on the Covisibility `cov` (its resident tables): win is the window as a
+        host sequence.  Returns the outputs of the updates by window position (n_counted, n_conn, kf_max, w_max,
+        new_parent, err), lc_kf [n_win + 1][lc_cap], n_lc [n_win + 1] and lc_err."""
+        win = _table(win, np.int32)
+        n_win = len(win)
+        res = EssentialGraph._connection_outputs(n_win, lc_cap, fill)
+        kf, mp, ml = cov._structs(lambda g, k: cov.dev[(g, k)].ptr)
+        obuf = dict(zip(res, _to_device(*res.values())[0]))
+        out = CovisOutputs(*[obuf[k].ptr for k in _COVIS_OUT])
+        sb = load().plvi_loop_connections_scratch_bytes(n_win, cov.kf_cap, cov.conn_cap)
+        scratch = DeviceBuffer(sb)
+
+        def step(s=None):
+            return _status("plvi_loop_connections_device", cov.h, n_win, win, kf, mp, ml, out, lc_cap,
+                           obuf["lc_kf"].ptr, obuf["n_lc"].ptr, obuf["lc_err"].ptr, scratch.ptr, sb, s or None)
+
+        def fetch(rc=0):
+            _sync()
+            r = {k: obuf[k].download(a) for k, a in res.items()}
+            r.update(rc=rc, keep=(obuf, scratch, win), dev={k: b.ptr for k, b in obuf.items()})
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
+
+    @staticmethod
+    def connections_host(cov, win, lc_cap, fill=-7):
+        """plvi_loop_connections: the host arrays first_conn / parent / covis given to cov.set_tables are updated
+        in place.  "rc" is PLVI_E_CAPACITY when lc_err is not 0; any other refusal raises."""
+        win = _table(win, np.int32)
+        n_win = len(win)
+        res = EssentialGraph._connection_outputs(n_win, lc_cap, fill)
+        tabs = cov._tables()
+        kf, mp, ml = cov._structs(lambda g, k: tabs[(g, k)].ctypes.data)
+        out = CovisOutputs(*[res[k].ctypes.data for k in _COVIS_OUT])
+        rc = _status("plvi_loop_connections", cov.h, n_win, win, kf, mp, ml, out, lc_cap, res["lc_kf"], res["n_lc"],
+                     res["lc_err"])
+        if rc < 0 and rc != PLVI_E_CAPACITY:
+            raise PlviError(rc, "plvi_loop_connections")
+        res["rc"] = rc
+        return res
+
+    # ---- C
+    def _graph_inputs(self, win, n_win, lc_kf, n_lc, win_cap, lc_cap):
+        """win / lc_kf / n_lc as host arrays with their capacities, or device addresses with the capacities given."""
+        if isinstance(win, (int, np.integer)):
+            return None, (int(win), int(n_win), int(lc_kf), int(n_lc)), win_cap, lc_cap
+        win, n_lc = _table(win, np.int32), _table(n_lc, np.int32)
+        lc_kf = np.ascontiguousarray(lc_kf, np.int32)
+        if lc_kf.ndim != 2 or len(lc_kf) != len(win) or len(n_lc) != len(win):
+            raise ValueError(f"lc_kf {lc_kf.shape} / n_lc {n_lc.shape} do not match the window of {len(win)}")
+        n = np.array([len(win) if n_win is None else n_win], np.int32)
+        return (win, n, lc_kf, n_lc), None, len(win), lc_kf.shape[1]
+
+    def _graph_caps(self, vert_cap, edge_cap):
+        return dict(vert_cap=max(self.kf_cap, 1) if vert_cap is None else vert_cap,
+                    edge_cap=4 * max(self.kf_cap, 1) if edge_cap is None else edge_cap)
+
+    def _graph_outputs(self, caps, refs, fill):
+        res = self._outputs(_EG_GRAPH_LISTS, caps, ("n_vert", "n_edges", "err"), fill)
+        if refs:
+            res["pt_ref"] = np.full(self._n(0) + 1, fill, np.int32)
+            if self.pools[1] is not None:
+                res["ln_ref"] = np.full(self._n(1) + 1, fill, np.int32)
+        return res
+
+    def graph_device(self, cur_slot, loop_slot, mode, win, n_win, lc_kf, n_lc, win_cap=None, lc_cap=None,
+                     vert_cap=None, edge_cap=None, refs=True, fill=-7, stream=None, run=True):
+        """plvi_essential_graph_device.  win [win_cap], lc_kf [win_cap][lc_cap] and n_lc [win_cap] are numpy arrays
+        (uploaded; n_win None = all of win) or, with n_win, device addresses (then win_cap and lc_cap are given):
+        the outputs of correct_device and connections_device in place.  Returns vert, vert_flags, edge_a, edge_b,
+        edge_kind (capacity + 1 long), n_vert, n_edges [5], err and, with refs, pt_ref / ln_ref."""
+        self._check_tables()
+        host, addr, win_cap, lc_cap = self._graph_inputs(win, n_win, lc_kf, n_lc, win_cap, lc_cap)
+        caps = self._graph_caps(vert_cap, edge_cap)
+        res = self._graph_outputs(caps, refs, fill)
+        dev = self.upload()
+        structs = self._structs(lambda g, k: dev[(g, k)].ptr, self.rows)
+        ibuf = _to_device(*host)[0] if host else ()
+        addr = addr or tuple(b.ptr for b in ibuf)
+        obuf = dict(zip(res, _to_device(*res.values())[0]))
+        out = EgOutputs(**caps, **{k: b.ptr for k, b in obuf.items()})
+        sb = load().plvi_essential_graph_scratch_bytes(self.kf_cap, len(self.eg.get("order", ())), win_cap, lc_cap)
+        scratch = DeviceBuffer(sb)
+
+        def step(s=None):
+            return _status("plvi_essential_graph_device", int(cur_slot), int(loop_slot), mode, addr[0], addr[1],
+                           win_cap, addr[2], addr[3], lc_cap, *structs, out, scratch.ptr, sb, s or None)
+
+        def fetch(rc=0):
+            _sync()
+            r = {k: obuf[k].download(a) for k, a in res.items()}
+            r.update(rc=rc, keep=(ibuf, obuf, scratch), dev={k: b.ptr for k, b in obuf.items()})
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
+
+    def graph_host(self, cur_slot, loop_slot, mode, win, n_win, lc_kf, n_lc, vert_cap=None, edge_cap=None, refs=True,
+                   fill=-7):
+        """plvi_essential_graph with numpy inputs; the same dict.  "rc" is PLVI_E_CAPACITY when err has a bit other
+        than EG_ERR_NO_VERTEX; any other refusal raises."""
+        self._check_tables()
+        host, _, win_cap, lc_cap = self._graph_inputs(win, n_win, lc_kf, n_lc, None, None)
+        caps = self._graph_caps(vert_cap, edge_cap)
+        res = self._graph_outputs(caps, refs, fill)
+        tabs = self._tables()
+        structs = self._structs(lambda g, k: tabs[(g, k)].ctypes.data)
+        out = EgOutputs(**caps, **{k: a.ctypes.data for k, a in res.items()})
+        rc = _status("plvi_essential_graph", int(cur_slot), int(loop_slot), mode, host[0], host[1], win_cap, host[2],
+                     host[3], lc_cap, *structs, out)
+        if rc < 0 and rc != PLVI_E_CAPACITY:
+            raise PlviError(rc, "plvi_essential_graph")
+        res["rc"] = rc
+        return res
