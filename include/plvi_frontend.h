@@ -54,12 +54,18 @@ enum {
  *  GEMM_FMA        the pose product Rcw*P + tcw of the frustum tests (cv::gemm,
  *                  3x3 * 3x1 + 3x1 float) as OpenCV's AVX2-dispatched build
  *                  contracts it, fma(a2,b2, fma(a0,b0, a1*b1)), instead of the
- *                  baseline (a0*b0 + a1*b1) + a2*b2 (plvi_frustum_params.compat) */
+ *                  baseline (a0*b0 + a1*b1) + a2*b2 (plvi_frustum_params.compat)
+ *  SCALEADD_FMA    the accumulation normal + normali / cv::norm(normali) of
+ *                  UpdateNormalAndDepth (cv::scaleAdd of a 3x1 float row, its
+ *                  scalar tail) as OpenCV's AVX2-dispatched build contracts it,
+ *                  fma(normali, alpha, normal), instead of the baseline
+ *                  normali*alpha + normal (plvi_refresh_params.compat) */
 enum {
   PLVI_COMPAT_GAUSS_ROUNDED = 1,
   PLVI_COMPAT_RESIZE_V_GENERIC = 2,
   PLVI_COMPAT_EXP_CV_TABLE = 4,
   PLVI_COMPAT_GEMM_FMA = 8,
+  PLVI_COMPAT_SCALEADD_FMA = 16,
 };
 
 /* Per-frame device error flags of a batch (plvi_orb_errors / plvi_lines_errors). */
@@ -2517,6 +2523,165 @@ int plvi_essential_graph(int cur_slot, int loop_slot, int mode, const int* win, 
                          const int* lc_kf, const int* n_lc, int lc_cap, const plvi_cull_keyframes* kf,
                          const plvi_eg_keyframes* eg, const plvi_local_map_pool* mp, const plvi_local_map_pool* ml,
                          const plvi_eg_features* fmp, const plvi_eg_features* fml, const plvi_eg_outputs* out);
+
+/* --------------------------------------------------------- Feature refresh
+ * MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:427-494) and
+ * MapLine::UpdateNormalAndDepth (src/MapLine.cc:339-382) for NLeft == -1
+ * (leftIndex always valid, rightIndex always -1), and
+ * ComputeDistinctiveDescriptors (plvi_distinctive_descriptors_batch above)
+ * fed from resident tables: the pair the reference calls back to back after
+ * local BA, SearchInNeighbors, CreateNewMapPoints, Replace, CorrectLoop and
+ * global BA.  The columns normal / dist / desc of plvi_local_map_pool are
+ * updated in place at the rows a list of pool ids names, so a resident map
+ * needs no host walk between a traversal (local_feat of plvi_ba_window, pts /
+ * lns of plvi_loop_correct, the targets of Fuse) and the next frustum test.
+ *
+ * One implementation serves both kinds (params->kind).  what is a mask of
+ * PLVI_REFRESH_NORMAL and PLVI_REFRESH_DESC.
+ *
+ * NORMAL, per id (state bit 0):
+ *  1. a bad feature returns.  The list is obs_off[id+1] - obs_off[id] clamped
+ *     to [0, max_obs]; entries whose obs_kf is outside [0, kf_cap) are ignored;
+ *     a list with no entry left returns (observations.empty()).  The row is
+ *     left alone.
+ *  2. Pos: pos[id] for points; for lines the midpoint of sep[id] in double,
+ *     an add then a multiply by 0.5, then (float) (Converter::toCvMat).
+ *  3. for each observer in list order -- bad keyframes are NOT skipped, the
+ *     reference's loop has no isBad():
+ *       normali = Pos - ow[kf]            one float subtract per component
+ *       s       = cv::norm(normali)       exact float squares summed in double, sqrt
+ *       alpha   = (float)(1.0 / s)
+ *       normal  = normali * alpha + normal   per component (see below)
+ *  4. n = the observers counted; normal * (float)(1.0 / (double)n).
+ *  5. dist = (float)cv::norm(Pos - ow[ref_kf]).
+ *  6. level: points, the octave info[ref_kf][idx], idx the obs_idx of ref_kf's
+ *     entry in the list -- or 0 when ref_kf is not in the list
+ *     (observations[pRefKF] default-constructs the tuple: the octave of
+ *     keypoint 0); lines, 0 (MapLine.cc:373).
+ *  7. mfMaxDistance = dist * scale[level]; mfMinDistance = mfMaxDistance /
+ *     scale[n_levels - 1]; dist[id] = {min, max}.
+ * Precondition failures: the row is left alone, the state is 0 and one err bit
+ * is raised: ref_kf outside [0, kf_cap) (ERR_REF), level >= n_levels
+ * (ERR_LEVEL), idx outside [0, min(cnt[ref_kf], cap)) -- which includes
+ * cnt[ref_kf] == 0 when ref_kf is not in the list (ERR_KEYPOINT; points only).
+ * A keyframe must appear once per list (observations are map keys); of two
+ * entries for ref_kf the first is taken.  The float sum of step 3 depends on
+ * the list order in its last bits: the library takes the caller's order
+ * (INTEGRATION.md).
+ *
+ * What the reference objects pin (tests/test_ref_objects_feature_refresh.py):
+ * the calls operator-(Mat, Mat), cv::norm, operator/(Mat, double),
+ * operator+(Mat const&, MatExpr const&); the double add and multiply of the
+ * midpoint; cvtsi2sd of n ahead of operator/; cvtsd2ss behind cv::norm; the
+ * mulss and divss of step 7; no fused instruction in either function.
+ * Parity unpinned: OpenCV's own arithmetic inside those calls.  cv::norm and
+ * the elementwise subtract are taken as the frustum tests take them.
+ * normal + normali / s is taken as MatOp_AddEx resolving to
+ * scaleAdd(normali, 1/s, normal): alpha narrowed to float, then
+ * src * alpha + acc per element in the scalar tail of a 3-element row.  An
+ * AVX2-dispatched OpenCV contracts that tail to a fused multiply-add, the
+ * baseline does not: PLVI_COMPAT_SCALEADD_FMA (params->compat) selects
+ * fma(normali, alpha, normal); 0 is the unfused form.  normal / n goes through
+ * convertTo with a zero offset, which contraction cannot change.
+ *
+ * DESC, per id (state bit 1): the function of
+ * plvi_distinctive_descriptors_batch on the list of step 1 (a bad feature has
+ * an empty list), where an entry is ignored when its keyframe is out of
+ * range or bad (MapPoint.cc:349) or its obs_idx is outside
+ * [0, min(cnt[kf], cap)); the pool row is kf * cap + obs_idx of kf->desc.  A
+ * CSR over the ids (every list at its clamped length, ignored entries as row
+ * -1, so best_pos counts them as f19 does) is built in scratch, the public
+ * batch call runs on it, and row id of desc is written where best_pos >= 0.
+ * n_rows is the full length of that CSR; when it exceeds row_cap,
+ * PLVI_REFRESH_ERR_ROWS is raised, no descriptor is written and best_pos is
+ * -1 for every id.  NORMAL is unaffected.
+ *
+ * Outputs by id position i: state[i] is always written (0 for an id outside
+ * [0, n)); best_pos / best_median are written when DESC is in what.
+ * Duplicate ids are allowed: both writers store the same values.  n_rows and
+ * err are written by every call (n_rows = 0 without DESC).
+ *
+ * Lists of up to 8 / 16 / 32 entries (by max_obs) share a wave in groups of
+ * that many lanes: a lane per observer for the gather, the reciprocal norm and
+ * the product, then the group adds in list order.  A longer list is walked by
+ * its group 32 entries at a time.  kf_cap * cap and n_ids * max_obs must fit
+ * an int (PLVI_E_CAPACITY). */
+enum { /* plvi_refresh_params.kind */
+  PLVI_REFRESH_POINTS = 0,
+  PLVI_REFRESH_LINES = 1,
+};
+enum { /* plvi_refresh_params.what, and the bits of state */
+  PLVI_REFRESH_NORMAL = 1,
+  PLVI_REFRESH_DESC = 2,
+};
+enum { /* err, bits */
+  PLVI_REFRESH_ERR_ROWS = 1,     /* n_rows > row_cap: no descriptor written */
+  PLVI_REFRESH_ERR_REF = 2,      /* a ref_kf outside [0, kf_cap) */
+  PLVI_REFRESH_ERR_LEVEL = 4,    /* an octave >= n_levels */
+  PLVI_REFRESH_ERR_KEYPOINT = 8, /* ref_kf's keypoint index outside its table (cnt 0 in the absent case) */
+};
+#define PLVI_REFRESH_MAX_LEVELS 64
+
+/* The keyframe side of one kind, by slot. */
+typedef struct plvi_refresh_keyframes {
+  int kf_cap;
+  int cap;             /* row length of info / desc: kp_cap or kl_cap */
+  const uint8_t* bad;  /* [kf_cap] isBad() */
+  const float* ow;     /* [kf_cap][3] GetCameraCenter() */
+  const int* cnt;      /* [kf_cap] N or N_l, read as clamped to [0, cap] */
+  const uint8_t* info; /* [kf_cap][cap] bits 0-5 the octave: kp_info / kl_info in place; points only */
+  const uint8_t* desc; /* [kf_cap][cap][32] mDescriptors / mDescriptors_Line; DESC only */
+} plvi_refresh_keyframes;
+
+/* Host struct, read before the call returns. */
+typedef struct plvi_refresh_params {
+  int kind;     /* PLVI_REFRESH_POINTS / LINES */
+  int what;     /* PLVI_REFRESH_NORMAL | PLVI_REFRESH_DESC */
+  int n_levels; /* mnScaleLevels / mnScaleLevels_l, 1 .. PLVI_REFRESH_MAX_LEVELS */
+  int max_obs;  /* <= PLVI_DISTINCTIVE_MAX_OBS */
+  int row_cap;  /* rows of the scratch CSR; DESC only */
+  int compat;   /* PLVI_COMPAT_SCALEADD_FMA */
+  float scale[PLVI_REFRESH_MAX_LEVELS]; /* mvScaleFactors / mvScaleFactors_l */
+} plvi_refresh_params;
+
+typedef struct plvi_refresh_outputs {
+  float* normal;    /* [n][3] in place; may be the pool's own column; NULL without NORMAL */
+  float* dist;      /* [n][2] likewise */
+  uint8_t* desc;    /* [n][32] likewise; NULL without DESC; 4-byte aligned */
+  uint8_t* state;   /* [n_ids] */
+  int* best_pos;    /* [n_ids] optional */
+  int* best_median; /* [n_ids] optional */
+  int* n_rows;      /* [1] */
+  int* err;         /* [1] PLVI_REFRESH_ERR_* */
+} plvi_refresh_outputs;
+
+/* Bytes of the scratch block: the CSR, best_pos / best_median and the chosen
+ * rows.  0 for a negative argument. */
+size_t plvi_feature_refresh_scratch_bytes(int n_ids, int row_cap);
+
+/* The device form: the structs are host memory read before the call returns,
+ * their pointers device pointers.  pool is read for n, bad, obs_off, obs_kf
+ * and pos (points) or sep (lines); feat for obs_idx; ref for ref_kf.
+ * PLVI_E_BADARG for a negative size, a missing pointer its kind and what
+ * need, an unknown kind, a what of 0 or with other bits, n_levels outside
+ * its range or a scratch block below its size; PLVI_E_CAPACITY for max_obs
+ * above PLVI_DISTINCTIVE_MAX_OBS.  n_ids == 0 writes n_rows and err only.
+ * d_scratch needs no initialisation; calls that share it must be ordered.
+ * Asynchronous on `stream`, no host read of device data, no allocation:
+ * capturable. */
+int plvi_feature_refresh_batch(const plvi_refresh_keyframes* kf, const plvi_local_map_pool* pool,
+                               const plvi_ba_features* feat, const plvi_eg_features* ref,
+                               const plvi_refresh_params* params, const int* d_ids, int n_ids,
+                               const plvi_refresh_outputs* out, void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* The host form, synchronous: the same structs and arrays with host pointers;
+ * normal / dist / desc are updated in place.  Returns the number of ids with
+ * the NORMAL bit set, PLVI_E_CAPACITY when err != 0 (everything is still
+ * written), or another error. */
+int plvi_feature_refresh(const plvi_refresh_keyframes* kf, const plvi_local_map_pool* pool,
+                         const plvi_ba_features* feat, const plvi_eg_features* ref,
+                         const plvi_refresh_params* params, const int* ids, int n_ids,
+                         const plvi_refresh_outputs* out);
 
 /* ---------------------------------------------------------------- Stereo
  * Rectified stereo of the stereo Frame constructors (src/Frame.cc:95-140,

@@ -2791,3 +2791,189 @@ class EssentialGraph:
             raise PlviError(rc, "plvi_essential_graph")
         res["rc"] = rc
         return res
+
+
+COMPAT_GEMM_FMA = 8       # PLVI_COMPAT_GEMM_FMA (plvi_frustum_params.compat)
+COMPAT_SCALEADD_FMA = 16  # PLVI_COMPAT_SCALEADD_FMA (plvi_refresh_params.compat)
+REFRESH_POINTS, REFRESH_LINES = 0, 1
+REFRESH_NORMAL, REFRESH_DESC = 1, 2
+REFRESH_ERR_ROWS, REFRESH_ERR_REF, REFRESH_ERR_LEVEL, REFRESH_ERR_KEYPOINT = 1, 2, 4, 8
+REFRESH_MAX_LEVELS = 64  # PLVI_REFRESH_MAX_LEVELS
+
+_REFRESH_FEAT = {"bad": (np.uint8, None), "obs_off": (np.int32, None), "obs_kf": (np.int32, None),
+                 "obs_idx": (np.int32, None), "ref_kf": (np.int32, None), **_LM_ROWS}
+_REFRESH_COLUMNS = ("normal", "dist", "desc")
+
+
+class RefreshKeyframes(ctypes.Structure):
+    """plvi_refresh_keyframes."""
+    _fields_ = [("kf_cap", _LM_I), ("cap", _LM_I)] + [(k, _LM_V) for k in ("bad", "ow", "cnt", "info", "desc")]
+
+
+class RefreshParams(ctypes.Structure):
+    """plvi_refresh_params."""
+    _fields_ = [(k, _LM_I) for k in ("kind", "what", "n_levels", "max_obs", "row_cap", "compat")] + \
+               [("scale", ctypes.c_float * REFRESH_MAX_LEVELS)]
+
+
+class RefreshOutputs(ctypes.Structure):
+    """plvi_refresh_outputs."""
+    _fields_ = [(k, _LM_V) for k in ("normal", "dist", "desc", "state", "best_pos", "best_median", "n_rows", "err")]
+
+
+class FeatureRefresh:
+    """MapPoint / MapLine::UpdateNormalAndDepth and ComputeDistinctiveDescriptors for a list of pool ids over
+    resident tables (plvi_feature_refresh[_batch]): the pool columns normal, dist and desc are updated in place.
+
+    ``keyframes``: a dict of numpy arrays of one kind -- bad [K], ow [K][3], cnt [K] (or nmp / nml), info [K][cap]
+    (or kp_info / kl_info; points) and desc [K][cap][32] (DESC).  ``features``: a dict with bad, obs_off, obs_kf,
+    obs_idx, ref_kf, pos (points) or sep (lines) and the columns normal [n][3], dist [n][2], desc [n][32] --
+    the arrays LocalBAWindow and EssentialGraph take plus the pool rows of LocalMap.  ``scale``: mvScaleFactors
+    (or mvScaleFactors_l); ``max_obs``: the longest list walked, by default the longest list of the pool.
+
+    ``batch`` runs on device copies (``self.dev``, which keep the refreshed columns), ``host`` goes through the
+    host form and updates ``self.feat`` in place.  Both return a dict: state, best_pos, best_median [n_ids],
+    n_rows, err, the three columns and "rc"."""
+
+    def __init__(self, keyframes, features, kind=REFRESH_POINTS, scale=(1.0,), max_obs=None, compat=0, cap=None):
+        self._lib = load()
+        self.kind = int(kind)
+        pts = self.kind == REFRESH_POINTS
+        pick = lambda *names: next((keyframes[k] for k in names if keyframes.get(k) is not None), None)  # noqa: E731
+        self.kf = {"bad": _table(pick("bad"), np.uint8), "ow": _table(pick("ow"), np.float32, 3),
+                   "cnt": _table(pick("cnt", "nmp" if pts else "nml"), np.int32),
+                   "info": _table(pick("info", "kp_info" if pts else "kl_info"), np.uint8)}
+        self.kf = {k: a for k, a in self.kf.items() if a is not None}
+        self.kf_cap = len(self.kf["bad"])
+        if cap is None:
+            cap = self.kf["info"].shape[1] if "info" in self.kf else np.shape(keyframes["desc"])[1]
+        self.cap = int(cap)
+        if keyframes.get("desc") is not None:
+            self.kf["desc"] = np.ascontiguousarray(keyframes["desc"], np.uint8).reshape(-1, self.cap, 32)
+        self.feat = {k: _table(features[k], dt, w) for k, (dt, w) in _REFRESH_FEAT.items()
+                     if features.get(k) is not None}
+        self.scale = np.ascontiguousarray(scale, np.float32)
+        if not 1 <= len(self.scale) <= REFRESH_MAX_LEVELS:
+            raise ValueError(f"scale has {len(self.scale)} levels, expected 1 to {REFRESH_MAX_LEVELS}")
+        self.n = len(self.feat["bad"])
+        if max_obs is None:
+            max_obs = int(np.diff(self.feat["obs_off"]).max(initial=1)) if self.n else 1
+        self.max_obs = max(int(max_obs), 1)
+        self.compat = int(compat)
+        self.dev = None
+
+    def _check_tables(self):
+        """Every companion array has the length its table gives it: refused here, before the library reads them."""
+        _same_len(self.kf_cap, **{"keyframes." + k: a for k, a in self.kf.items()})
+        for k in ("info", "desc"):
+            if k in self.kf and self.kf[k].shape[1:2] != (self.cap,):
+                raise ValueError(f"keyframes.{k} has rows of {self.kf[k].shape[1:2]}, expected {self.cap}")
+        f, n = self.feat, self.n
+        _same_len(n + 1, **{"features.obs_off": f["obs_off"]})
+        _same_len(n, **{"features." + k: a for k, a in f.items() if k not in ("obs_off", "obs_kf", "obs_idx")})
+        n_obs = int(f["obs_off"][n])
+        if len(f["obs_kf"]) < n_obs:
+            raise ValueError(f"features.obs_kf has {len(f['obs_kf'])} records, obs_off names {n_obs}")
+        _same_len(len(f["obs_kf"]), **{"features.obs_idx": f.get("obs_idx")})
+
+    def _tables(self):
+        t = {("kf", k): a for k, a in self.kf.items()}
+        t.update({("f", k): a for k, a in self.feat.items()})
+        return t
+
+    def upload(self):
+        if self.dev is None:
+            tabs = self._tables()
+            self.dev = dict(zip(tabs, _to_device(*tabs.values())[0]))
+        return self.dev
+
+    def _structs(self, ptr):
+        kf = RefreshKeyframes(self.kf_cap, self.cap, **{k: ptr("kf", k) for k in self.kf})
+        pool = LocalMapPool(self.n, **{k: ptr("f", k) for k in self.feat if k not in ("obs_idx", "ref_kf")})
+        feat = BAFeatures(ptr("f", "obs_idx")) if "obs_idx" in self.feat else None
+        ref = EgFeatures(ref_kf=ptr("f", "ref_kf")) if "ref_kf" in self.feat else None
+        return kf, pool, feat, ref
+
+    def _params(self, what, row_cap, compat):
+        p = RefreshParams(self.kind, int(what), len(self.scale), self.max_obs, int(row_cap),
+                          self.compat if compat is None else int(compat))
+        p.scale[:len(self.scale)] = self.scale.tolist()
+        return p
+
+    def rows_of(self, ids):
+        """The full length of the observation list plvi_feature_refresh builds for ``ids``: n_rows."""
+        ids = np.asarray(ids, np.int64).reshape(-1)
+        ok = (ids >= 0) & (ids < self.n)
+        idc = np.where(ok, ids, 0)
+        ln = np.clip(self.feat["obs_off"][idc + 1].astype(np.int64) - self.feat["obs_off"][idc], 0, self.max_obs)
+        return int(np.where(ok & (self.feat["bad"][idc] == 0), ln, 0).sum()) if len(ids) else 0
+
+    @staticmethod
+    def _host(n_ids, best, fill):
+        res = {"state": np.full(n_ids + 1, fill & 0x7f, np.uint8),  # one cell more than is written
+               "n_rows": np.full(1, fill, np.int32), "err": np.full(1, fill, np.int32)}
+        if best:
+            res.update(best_pos=np.full(n_ids + 1, fill, np.int32), best_median=np.full(n_ids + 1, fill, np.int32))
+        return res
+
+    @staticmethod
+    def _result(res, n_ids, rc):
+        r = {k: (a[:n_ids] if k not in ("n_rows", "err") else int(a[0])) for k, a in res.items()}
+        r.update(rc=rc, past={k: a[n_ids].tolist() for k, a in res.items() if k not in ("n_rows", "err")})
+        return r
+
+    def batch(self, ids=None, what=REFRESH_NORMAL | REFRESH_DESC, row_cap=None, compat=None, d_ids=None, n_ids=None,
+              best=True, fill=-7, stream=None, run=True):
+        """plvi_feature_refresh_batch of ``ids`` (a numpy list, or a device address ``d_ids`` of ``n_ids`` ints,
+        which needs ``row_cap``).  Adds "dev", the device addresses of the three columns, and "past" (the cell
+        after the last id of every per-id output).  run=False returns (step(stream), fetch()) for capture."""
+        self._check_tables()
+        dev = self.upload()
+        structs = self._structs(lambda g, k: dev[(g, k)].ptr)
+        keep = []
+        if d_ids is None:
+            ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+            n_ids = len(ids)
+            keep += _to_device(ids)[0]
+            d_ids = keep[0].ptr
+            if row_cap is None:
+                row_cap = self.rows_of(ids)
+        params = self._params(what, 0 if row_cap is None else row_cap, compat)
+        res = self._host(n_ids, best, fill)
+        obuf = dict(zip(res, _to_device(*res.values())[0]))
+        cols = {k: dev[("f", k)].ptr if ("f", k) in dev else None for k in _REFRESH_COLUMNS}
+        out = RefreshOutputs(**cols, **{k: b.ptr for k, b in obuf.items()})
+        sb = load().plvi_feature_refresh_scratch_bytes(n_ids, params.row_cap)
+        scratch = DeviceBuffer(sb)
+
+        def step(s=None):
+            return _status("plvi_feature_refresh_batch", *structs, params, d_ids, n_ids, out, scratch.ptr, sb, s or None)
+
+        def fetch(rc=0):
+            _sync()
+            r = self._result({k: obuf[k].download(a) for k, a in res.items()}, n_ids, rc)
+            r.update({k: dev[("f", k)].download(np.empty_like(self.feat[k])) for k in _REFRESH_COLUMNS
+                      if k in self.feat})
+            r.update(dev=cols, keep=(keep, obuf, scratch))
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
+
+    def host(self, ids, what=REFRESH_NORMAL | REFRESH_DESC, row_cap=None, compat=None, best=True, fill=-7):
+        """plvi_feature_refresh with numpy inputs: the columns of ``self.feat`` are updated in place.  "rc" is the
+        number of ids with the NORMAL bit, or PLVI_E_CAPACITY when err is not 0; any other refusal raises."""
+        self._check_tables()
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        tabs = self._tables()
+        structs = self._structs(lambda g, k: tabs[(g, k)].ctypes.data)
+        params = self._params(what, self.rows_of(ids) if row_cap is None else row_cap, compat)
+        res = self._host(len(ids), best, fill)
+        cols = {k: self.feat[k].ctypes.data if k in self.feat else None for k in _REFRESH_COLUMNS}
+        out = RefreshOutputs(**cols, **{k: a.ctypes.data for k, a in res.items()})
+        rc = _status("plvi_feature_refresh", *structs, params, ids, len(ids), out)
+        if rc < 0 and rc != PLVI_E_CAPACITY:
+            raise PlviError(rc, "plvi_feature_refresh")
+        r = self._result(res, len(ids), rc)
+        r.update({k: self.feat[k] for k in _REFRESH_COLUMNS if k in self.feat})
+        return r
