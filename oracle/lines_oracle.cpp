@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "cvprim.h"
+#include "oracle_api.h"
 #include "ref_fma.h"
 
 namespace oracle {
@@ -131,6 +132,9 @@ struct LSD {
     ImageF64 scaled, angles, modgrad;
     std::vector<unsigned char> used;
     std::vector<RegionPoint> reg;
+    // test census (oracle_lsd_regions): when set, detect appends one record
+    // {seed_x, seed_y, size, depth, min_reg_size} per region_grow call
+    std::vector<int>* census = nullptr;
 
     bool isAligned(int address, double theta, double prec) const {  // :1136-1152
         if (address < 0) return false;
@@ -295,6 +299,11 @@ struct LSD {
                     int reg_size;
                     double reg_angle;
                     region_grow(x, y, reg_size, reg_angle, prec);
+                    if (census) {
+                        int ymax = y;
+                        for (int i = 0; i < reg_size; ++i) ymax = std::max(ymax, reg[i].y);
+                        census->insert(census->end(), {x, y, reg_size, ymax - y, min_reg_size});
+                    }
                     if (reg_size < min_reg_size) continue;
                     double r[4];
                     region2rect(reg_size, reg_angle, prec, r);
@@ -659,6 +668,24 @@ extern "C" int oracle_lsd_raw(const uint8_t* img, int w, int h, float lsd_scale,
     *n = (int)l.size() / 4;
     if (*n > cap) return -3;
     std::memcpy(lines, l.data(), l.size() * sizeof(float));
+    return 0;
+}
+
+// Region census for one image: one record of 5 ints {seed_x, seed_y, size,
+// depth (largest point row - seed row), min_reg_size} for every seed flsd
+// visits, in visiting order.  *n = records; -3 when they exceed cap.
+extern "C" int oracle_lsd_regions(const uint8_t* img, int w, int h, float lsd_scale, int32_t* recs, int cap, int* n) {
+    ImageU8 im;
+    im.create(w, h);
+    std::memcpy(im.px.data(), img, (size_t)w * h);
+    LSD lsd;
+    lsd.SCALE = (double)lsd_scale;
+    std::vector<int> census;
+    lsd.census = &census;
+    lsd.detect(im);
+    *n = (int)census.size() / 5;
+    if (*n > cap) return -3;
+    std::memcpy(recs, census.data(), census.size() * sizeof(int));
     return 0;
 }
 

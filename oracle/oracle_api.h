@@ -8,6 +8,11 @@
 extern "C" {
 #endif
 typedef struct { float x, y, size, angle, response; int32_t octave, class_id; } plvi_keypoint;
+// One record per seed flsd visits (every region_grow call), in visiting order.
+typedef struct { int32_t seed_x, seed_y, size, depth /* largest point row - seed row */, min_reg_size; } oracle_lsd_region;
+// Region census of one image at the given LSD scale (lines_oracle.cpp): *n =
+// records, written to recs[0 .. *n) when they fit cap (else -3 is returned).
+int oracle_lsd_regions(const uint8_t* img, int w, int h, float lsd_scale, int32_t* recs /* cap x 5 */, int cap, int* n);
 #ifdef __cplusplus
 }
 #endif

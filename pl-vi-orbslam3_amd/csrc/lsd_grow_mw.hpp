@@ -103,7 +103,12 @@ struct MwCtl {
     int stat[kMwStatN];  // [0] dispatched [1] dropped [2] regrown [3] exact (undispatched) [4] trivial [5] committed
                    // speculative [6] walk cycles [7] walker growth cycles [8] walk entries [9] blocked on a
                    // growing head [10] kernel cycles (wave 0) [11] speculative growth cycles (sum over waves)
-                   // [12] unused [13] blocks (completed regions) [14] block setup cycles / 16
+                   // [12] grown exactly by the walker, whatever the cause: a regrown region [2], an
+                   // undispatched seed [3], or a log entry whose slot is neither grown nor growing
+                   // (so [12] >= [2] + [3]).  The walk resolves every seed flsd visits exactly once,
+                   // as trivial, committed speculative or walker-grown: [4] + [5] + [12] = flsd's
+                   // region_grow calls, whatever the schedule
+                   // [13] blocks (completed regions) [14] block setup cycles / 16
                    // [15] block round cycles / 16
                    // PLVI_MW_DIAG: [16]/[17] walker waits on a revalidation regrowth (count / cycles)
                    // [18]/[19] waits on a first growth [20..25] walker regrowths by distance (in commits)
@@ -606,6 +611,7 @@ __device__ int mw_walk(const MwEnv& E, lds_u8* pool, lds_i32* dlog, unsigned* sl
             mw_own_clear(E, qy, XQ, n, spilled, lane);
             if (STATS && lane == 0) {
                 mw_stat(ctl, 7, (int)(__builtin_amdgcn_s_memtime() - tg0));
+                mw_stat(ctl, 12, 1);
                 if (si < 0) mw_stat(ctl, 3, 1);
             }
             for (int j = lane; j < n; j += 64) {

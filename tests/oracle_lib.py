@@ -248,6 +248,28 @@ def lsd_raw(img, lsd_scale=0.8, cap=20000):
     return out[:n.value].copy()
 
 
+LSD_REGION_DTYPE = np.dtype([("seed_x", "<i4"), ("seed_y", "<i4"), ("size", "<i4"), ("depth", "<i4"),
+                             ("min_reg_size", "<i4")])
+
+
+def lsd_regions(img, lsd_scale=0.8):
+    """Region census of flsd: one record per seed it visits (every region_grow call), in visiting order:
+    seed_x, seed_y, size, depth (largest point row - seed row), min_reg_size; `kept` = size >= min_reg_size
+    (the regions that become raw segments)."""
+    lib = load()
+    V, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    lib.oracle_lsd_regions.argtypes = [V, I, I, F, V, I, ctypes.POINTER(I)]
+    lib.oracle_lsd_regions.restype = I
+    img = np.ascontiguousarray(img, np.uint8)
+    h, w = img.shape
+    cap = w * h  # a region per pixel at the most
+    out = np.zeros(cap, LSD_REGION_DTYPE)
+    n = ctypes.c_int()
+    rc = lib.oracle_lsd_regions(_p(img), w, h, lsd_scale, _p(out), cap, ctypes.byref(n))
+    assert rc == 0, rc
+    return out[:n.value].copy()
+
+
 def lsd_planes(img, lsd_scale=0.8):
     """flsd's scaled image, angle (rad, NOTDEF -1024) and modgrad planes (f64)."""
     lib = load()

@@ -2,7 +2,8 @@
 regions of one frame grow concurrently and commit in raster seed order after
 validation (lsd.cpp:476-533, 635-686).  Parity: the lines equal the oracle's
 and the sequential kernel's bit for bit; the counters show the speculative
-path, the regrow path and the walker's exact path all ran."""
+path ran and account for every region the oracle grows (trivial + committed
+speculative + grown by the walker = its region count per (frame, octave))."""
 import ctypes
 
 import numpy as np
@@ -48,13 +49,14 @@ def _run(monkeypatch, frames, mw, stats=False):
     out = _tables(lx, n)
     if stats:
         lib.plvi_lines_debug_mw_stats(lx._h, ctypes.c_void_p(0))
-        return out, plvi.download(st.ptr, np.zeros(n * 2 * 16, np.int32)).reshape(n, 2, 16)
+        halves = [lx.pyramid_level(1, frame=f) for f in range(n)]  # the octave-1 images the extractor built
+        return out, plvi.download(st.ptr, np.zeros(n * 2 * 16, np.int32)).reshape(n, 2, 16), halves
     return out
 
 
 def test_mw_matches_oracle_and_sequential(plvi_lib, monkeypatch):
     frames = synth.batch(6, seed0=300)
-    mw, st = _run(monkeypatch, frames, 256, stats=True)
+    mw, st, halves = _run(monkeypatch, frames, 256, stats=True)
     seq = _run(monkeypatch, frames, 0)
     for f in range(len(frames)):
         assert _same(mw[f], seq[f]), f"frame {f}: multi-wave != sequential kernel"
@@ -64,6 +66,13 @@ def test_mw_matches_oracle_and_sequential(plvi_lib, monkeypatch):
     # dispatched, dropped, regrown, exact, trivial, committed speculative
     assert tot[0] > 0 and tot[5] > 0 and tot[4] > 0, tot
     assert tot[5] + tot[2] <= tot[0]
+    # whatever the schedule, the walk resolves every seed flsd visits exactly once: as trivial [4], by
+    # committing its speculative region [5] or by growing it itself [12] (regrown [2], undispatched [3], ...)
+    for f in range(len(frames)):
+        for o, src in enumerate((frames[f], halves[f])):
+            s, n = st[f, o], len(ol.lsd_regions(src))
+            assert s[4] + s[5] + s[12] == n, f"frame {f} octave {o}: {s[4]} + {s[5]} + {s[12]} != {n} regions"
+            assert s[12] >= s[2] + s[3], f"frame {f} octave {o}: {s[12]} < {s[2]} + {s[3]}"
 
 
 def test_mw_real_and_extreme_frames(plvi_lib, monkeypatch):
