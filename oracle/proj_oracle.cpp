@@ -185,6 +185,7 @@ extern "C" int oracle_search_by_projection(
         if (u < minX || u > maxX) continue;
         if (v < minY || v > maxY) continue;
         const int nLastOctave = loct[i];
+        if (nLastOctave < 0) continue;  // no scale factor (the reference would read mvScaleFactors[-1])
         const float radius = th * scale_factors[nLastOctave];
         std::vector<size_t> vIndices2;
         if (bForward)
@@ -312,6 +313,7 @@ extern "C" int oracle_search_by_projection2(
         if (u < minX || u > maxX) continue;
         if (v < minY || v > maxY) continue;
         const int nLastOctave = loct[i];
+        if (nLastOctave < 0) continue;  // no scale factor (the reference would read mvScaleFactors[-1])
         const float radius = th * scale_factors[nLastOctave];
         const std::vector<size_t> vIndices2 = area(grid, keys, u, v, radius, nLastOctave);
         if (vIndices2.empty()) continue;
@@ -472,6 +474,7 @@ extern "C" int oracle_search_local(int n_cur, const float* cx_, const float* cy_
     for (int iMP = 0; iMP < n_mp; iMP++) {
         if (!(mp_flags[iMP] & 1)) continue;
         const int nPredictedLevel = level[iMP];
+        if (nPredictedLevel < 0) continue;  // no scale factor (the reference would read mvScaleFactors[-1])
         float r = view_cos[iMP] > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos
         if (bFactor) r *= th;
         const std::vector<size_t> vIndices =
@@ -543,7 +546,7 @@ extern "C" int oracle_search_local2(int n_left, const float* lx, const float* ly
     for (int iMP = 0; iMP < n_mp; iMP++) {
         const bool inView = mp_flags[iMP] & 1, inViewR = mp_flags[iMP] & 4;
         if (!inView && !inViewR) continue;
-        if (inView) {
+        if (inView && level[iMP] >= 0) {  // a negative level has no scale factor: no left candidate
             const int nPredictedLevel = level[iMP];
             float r = view_cos[iMP] > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos
             if (bFactor) r *= th;

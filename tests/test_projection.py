@@ -7,7 +7,9 @@ Parity unpinned: the reference has no tests for these; the C++ oracle
 (oracle/proj_oracle.cpp) restates the cited lines, is checked here against
 pure-Python restatements of the grid and the window query, and the HIP path
 is compared with the oracle exactly (match table incl. overwrites and the
-rotation filter's NULLs, nmatches)."""
+rotation filter's NULLs, nmatches).  That an overwrite, a re-scan and a
+nulled overwritten keypoint really occur is proved on crafted scenes in
+tests/test_proj_branches.py (the "overwrite" and "contention" cases)."""
 import math
 
 import numpy as np

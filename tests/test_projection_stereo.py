@@ -9,7 +9,8 @@ oracle_search_by_projection2, host libm for atan2f / cosf / sinf as the referenc
 cited lines; with a Pinhole rig it is checked here against the one-camera oracle on a frame whose right image
 is empty, and its KannalaBrandt8 projection against a float64 model; the HIP path (search_by_projection2_kernel,
 csrc/proj.hip, glibc atan2f / cosf / sinf restated in csrc/plvi_math.h) is compared with the oracle exactly
-(both match tables incl. overwrites and the rotation filter's NULLs, nmatches).
+(both match tables incl. overwrites and the rotation filter's NULLs, nmatches); the "overwrite" case of
+tests/test_proj_branches.py proves on a crafted scene that an overwrite occurs in both images.
 
 Reference quirks the oracle and the kernel both encode (a change to either
 must keep them): the right pass projects x3Dr with CurrentFrame.mpCamera, not

@@ -1105,3 +1105,620 @@ class StereoLineSet:
             return t
         return (tab(self.L), np.array(self.dl, np.uint8).reshape(-1, 32), tab(self.R),
                 np.array(self.dr, np.uint8).reshape(-1, 32), tab(self.un))
+
+
+# ------------------------------------------------- the tracking projection matchers (csrc/proj.hip), traced
+# Pure-Python restatements of the five guided searches of tracking, written from the reference lines, each
+# sequential like the reference:
+#   py_proj_traced   SearchByProjection(CurrentFrame, LastFrame, th, bMono)   ORBmatcher.cc:1962-2178, one camera
+#                    (Nleft == -1) and two cameras (:1985-2153)
+#   py_local_traced  SearchByProjection(F, vpMapPoints, th, ...)               ORBmatcher.cc:44-143 and :44-214
+#   py_reloc_traced  SearchByProjection(CurrentFrame, pKF, sAlreadyFound, ...) ORBmatcher.cc:2180-2300
+# over one GetFeaturesInArea walker (Frame.cc:1006-1075, pj_in_area) and ComputeThreeMaxima (ORBmatcher.cc:
+# 2304-2345, py_three_maxima).  Every one returns (nmatches, [match table per image], trace): per image and
+# point a set of PJ_* outcome codes, the scan against the flags on entry ("p1": what phase 1 of the kernels
+# computes) and against the flags at the point's turn ("fin"), the rotation histogram and the kept bins.
+# `mut` switches one deliberate mistake on (PJ_MUTANTS); tests/test_proj_branches.py uses it to prove that
+# the crafted inputs tell that mistake from the reference behaviour.
+PJ_NAMES = ("NOT_SEARCHED", "BAD_LEVEL", "BEHIND", "OUT_OF_BOUNDS", "DEPTH_RANGE", "WINDOW_RIGHT", "WINDOW_LEFT",
+            "WINDOW_BELOW", "WINDOW_ABOVE", "EMPTY_WINDOW", "ALL_BLOCKED", "OVER_THRESHOLD", "RATIO_REJECTED",
+            "ACCEPTED", "ACCEPTED_BY_LEVEL", "ACCEPTED_AFTER_RESCAN", "LOST_AFTER_RESCAN", "OVERWROTE", "MIRRORED",
+            "UNBLOCKED_PARTNER", "ROT_DROPPED", "SIDE_SKIPPED")
+(PJ_NOT_SEARCHED, PJ_BAD_LEVEL, PJ_BEHIND, PJ_OUT_OF_BOUNDS, PJ_DEPTH_RANGE, PJ_WINDOW_RIGHT, PJ_WINDOW_LEFT,
+ PJ_WINDOW_BELOW, PJ_WINDOW_ABOVE, PJ_EMPTY_WINDOW, PJ_ALL_BLOCKED, PJ_OVER_THRESHOLD, PJ_RATIO_REJECTED,
+ PJ_ACCEPTED, PJ_ACCEPTED_BY_LEVEL, PJ_ACCEPTED_AFTER_RESCAN, PJ_LOST_AFTER_RESCAN, PJ_OVERWROTE, PJ_MIRRORED,
+ PJ_UNBLOCKED_PARTNER, PJ_ROT_DROPPED, PJ_SIDE_SKIPPED) = range(len(PJ_NAMES))
+PJ_WINDOW_RETURNS = (PJ_WINDOW_RIGHT, PJ_WINDOW_LEFT, PJ_WINDOW_BELOW, PJ_WINDOW_ABOVE)  # in the reference's order
+PJ_TAKEN = (PJ_ACCEPTED, PJ_ACCEPTED_BY_LEVEL)
+# no phase-2 re-scan / re-scan when the best was taken only / no `unblocked` handling / ties to the lowest index /
+# |dx| <= radius / er >= radius / ratio product in double / rint bin / >= in ComputeThreeMaxima / <= in its 10 %
+# cut / one decrement per nulled keypoint / bestDist < TH_HIGH
+PJ_MUTANTS = ("no_rescan", "rescan_best_only", "no_unblocked", "low_index_tie", "le_radius", "ge_uright",
+              "ratio_double", "rint_bin", "ge_three_maxima", "le_ten_percent", "dec_per_keypoint", "lt_th_high")
+TM_BRANCHES = ("first", "second", "third", "cut_two", "cut_third", "keep_three")
+PJ_TH_HIGH, PJ_HISTO = 100, 30
+
+
+def _libm_f32(name, nargs):
+    import ctypes
+    import ctypes.util
+    fn = getattr(ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6"), name)
+    fn.restype, fn.argtypes = ctypes.c_float, [ctypes.c_float] * nargs
+    return lambda *a: np.float32(fn(*(float(t) for t in a)))
+
+
+def pj_project(camera, kb8, x, y, z):
+    """Pinhole::project (Pinhole.cpp:30-33) or KannalaBrandt8::project (KannalaBrandt8.cpp:33-48, the host
+    libm and the fused sites of oracle/proj_oracle.cpp) on float32."""
+    f = np.float32
+    fx, fy, cx, cy = (f(t) for t in camera[:4])
+    x, y, z = f(x), f(y), f(z)
+    if kb8 is None:
+        return f(f(f(fx * x) / z) + cx), f(f(f(fy * y) / z) + cy)
+    atan2f, cosf, sinf = _libm_f32("atan2f", 2), _libm_f32("cosf", 1), _libm_f32("sinf", 1)
+    k = [f(t) for t in kb8]
+    theta = atan2f(np.sqrt(fmaf(x, x, f(y * y))), z)
+    psi = atan2f(y, x)
+    t2 = f(theta * theta)
+    t3 = f(theta * t2)
+    t5 = f(t3 * t2)
+    t7 = f(t5 * t2)
+    t9 = f(t7 * t2)
+    r = fmaf(k[3], t9, fmaf(k[2], t7, fmaf(k[1], t5, fmaf(k[0], t3, theta))))
+    return fmaf(f(fx * r), cosf(psi), cx), fmaf(f(fy * r), sinf(psi), cy)
+
+
+def pj_window(grid, x, y, r):
+    """The cell range of GetFeaturesInArea (Frame.cc:1013-1037): ((x0, x1, y0, y1), 0), or (None, k) where the
+    reference returns early at its k-th test (1..4)."""
+    f = np.float32
+    min_x, _, min_y, _, inv_w, inv_h = (f(t) for t in grid)
+    x, y, r = f(x), f(y), f(r)
+    x0 = max(0, math.floor(f(f(f(x - min_x) - r) * inv_w)))
+    if x0 >= 64:
+        return None, 1
+    x1 = min(63, math.ceil(f(f(f(x - min_x) + r) * inv_w)))
+    if x1 < 0:
+        return None, 2
+    y0 = max(0, math.floor(f(f(f(y - min_y) - r) * inv_h)))
+    if y0 >= 48:
+        return None, 3
+    y1 = min(47, math.ceil(f(f(f(y - min_y) + r) * inv_h)))
+    if y1 < 0:
+        return None, 4
+    return (x0, x1, y0, y1), 0
+
+
+def pj_in_area(cells, k, grid, x, y, r, lo, hi, mut=()):
+    """GetFeaturesInArea(x, y, r, lo, hi) -> (vIndices in the reference's order, early-return number)."""
+    f = np.float32
+    win, ret = pj_window(grid, x, y, r)
+    if win is None:
+        return [], ret
+    x, y, r = f(x), f(y), f(r)
+    check = lo > 0 or hi >= 0
+    le = "le_radius" in mut
+    out = []
+    for ix in range(win[0], win[1] + 1):
+        for iy in range(win[2], win[3] + 1):
+            for i in cells[ix][iy]:
+                o = int(k["octave"][i])
+                if check and (o < lo or (hi >= 0 and o > hi)):
+                    continue
+                dx, dy = abs(f(k["x"][i] - x)), abs(f(k["y"][i] - y))
+                if (dx <= r and dy <= r) if le else (dx < r and dy < r):
+                    out.append(i)
+    return out, 0
+
+
+def py_rot_bin(a, b, mut=()):
+    """The rotation-histogram bin of a - b (ORBmatcher.cc:2071-2077): float factor 1.0f / HISTO_LENGTH, round()."""
+    f = np.float32
+    rot = f(f(a) - f(b))
+    if rot < 0:
+        rot = f(rot + f(360.0))
+    v = f(rot * f(f(1.0) / f(PJ_HISTO)))
+    b_ = int(np.rint(v)) if "rint_bin" in mut else int(math.floor(float(v) + 0.5))  # v >= 0: half away from zero
+    return 0 if b_ == PJ_HISTO else b_
+
+
+def py_three_maxima(hist, mut=()):
+    """ComputeThreeMaxima (ORBmatcher.cc:2304-2345) on the bin counts -> ((ind1, ind2, ind3), branches taken)."""
+    f = np.float32
+    ge, le = "ge_three_maxima" in mut, "le_ten_percent" in mut
+    max1 = max2 = max3 = 0
+    ind1 = ind2 = ind3 = -1
+    taken = set()
+    for i, s in enumerate(hist):
+        if (s >= max1) if ge else (s > max1):
+            max3, max2, max1 = max2, max1, s
+            ind3, ind2, ind1 = ind2, ind1, i
+            taken.add("first")
+        elif (s >= max2) if ge else (s > max2):
+            max3, max2 = max2, s
+            ind3, ind2 = ind2, i
+            taken.add("second")
+        elif (s >= max3) if ge else (s > max3):
+            max3, ind3 = s, i
+            taken.add("third")
+    lim = f(f(0.1) * f(max1))
+
+    def cut(m):
+        return f(m) <= lim if le else f(m) < lim
+    if cut(max2):
+        ind2 = ind3 = -1
+        taken.add("cut_two")
+    elif cut(max3):
+        ind3 = -1
+        taken.add("cut_third")
+    else:
+        taken.add("keep_three")
+    return (ind1, ind2, ind3), taken
+
+
+class _PjSide:
+    """One image of the frame: mvKeys(Un), the grid, mvpMapPoints as (match, blocked)."""
+
+    def __init__(self, kps, desc, blocked, grid, mp_desc):
+        from batch_pack import hamming
+        from test_projection import _py_grid
+        self.k, self.n = kps, len(kps)
+        self.cells = _py_grid(kps["x"], kps["y"], grid)
+        self.pre = np.zeros(self.n, bool) if blocked is None else np.asarray(blocked).astype(bool)
+        self.blk = self.pre.copy()
+        self.match = np.full(self.n, -1, np.int32)
+        self.nulled = np.zeros(self.n, bool)
+        self.oct = kps["octave"]
+        self.dist = hamming(mp_desc, desc) if self.n and len(mp_desc) else np.zeros((len(mp_desc), self.n), np.int32)
+
+    def table(self):
+        return np.where(self.nulled, -2, self.match).astype(np.int32)
+
+
+def _pj_scan(idxs, blk, drow, reject, mut):
+    """The candidate loop: first argmin and first argmin of the rest, in vIndices order."""
+    bd, bi, bd2, bi2 = 256, -1, 256, -1
+    for i in (sorted(idxs) if "low_index_tie" in mut else idxs):
+        if blk[i] or (reject is not None and reject(i)):
+            continue
+        d = int(drow[i])
+        if d < bd:
+            bd2, bi2, bd, bi = bd, bi, d, i
+        elif d < bd2:
+            bd2, bi2 = d, i
+    return bd, bi, bd2, bi2
+
+
+def _pj_pick(side, idxs, drow, reject, two, mut):
+    """(p1, fin): the scan against the flags on entry and the one the point's turn gets.  The reference is
+    sequential, so fin is the scan against the current flags; the schedule mutants keep p1 where a kernel with
+    that mistake would."""
+    p1 = _pj_scan(idxs, side.pre, drow, reject, mut)
+    seq = _pj_scan(idxs, side.blk, drow, reject, mut)
+
+    def moved(i):
+        return i >= 0 and side.blk[i] != side.pre[i]
+    if "no_rescan" in mut:
+        fin = p1
+    elif "rescan_best_only" in mut:
+        fin = seq if moved(p1[1]) else p1
+    elif "no_unblocked" in mut:
+        fin = seq if moved(p1[1]) or (two and moved(p1[3])) else p1
+    else:
+        fin = seq
+    if not two:
+        p1, fin = p1[:2] + (256, -1), fin[:2] + (256, -1)
+    return p1, fin
+
+
+def _pj_trace(sides, n):
+    return {"codes": [[set() for _ in range(n)] for _ in sides], "p1": [[None] * n for _ in sides],
+            "fin": [[None] * n for _ in sides], "rescans": [], "verdicts": set(), "window_returns": set(),
+            "hist": [0] * PJ_HISTO, "keep": None, "three_maxima": set(), "entries": []}
+
+
+def _pj_record(tr, s, i, p1, fin, v1, vf):
+    tr["p1"][s][i], tr["fin"][s][i] = p1, fin
+    tr["codes"][s][i].add(vf)
+    if p1 != fin:
+        tr["rescans"].append((s, i))
+        tr["verdicts"].add((v1, vf))
+        if vf in PJ_TAKEN:
+            tr["codes"][s][i].add(PJ_ACCEPTED_AFTER_RESCAN)
+        elif v1 in PJ_TAKEN:
+            tr["codes"][s][i].add(PJ_LOST_AFTER_RESCAN)
+
+
+def _pj_empty(tr, s, i, ret):
+    tr["codes"][s][i].add(PJ_WINDOW_RETURNS[ret - 1] if ret else PJ_EMPTY_WINDOW)
+    if ret:
+        tr["window_returns"].add(ret)
+
+
+def _pj_verdict_one(t, thr, mut):
+    if t[1] < 0:
+        return PJ_ALL_BLOCKED
+    return PJ_ACCEPTED if (t[0] < thr if "lt_th_high" in mut else t[0] <= thr) else PJ_OVER_THRESHOLD
+
+
+def _pj_verdict_two(t, side, nnratio, mut):
+    """The level-aware ratio test of the local search (ORBmatcher.cc:124-129): a float product."""
+    bd, bi, bd2, bi2 = t
+    if bi < 0:
+        return PJ_ALL_BLOCKED
+    if not (bd < PJ_TH_HIGH if "lt_th_high" in mut else bd <= PJ_TH_HIGH):
+        return PJ_OVER_THRESHOLD
+    lvl, lvl2 = int(side.oct[bi]), (int(side.oct[bi2]) if bi2 >= 0 else -1)
+    if "ratio_double" in mut:
+        fails = bd > float(np.float32(nnratio)) * bd2
+    else:
+        fails = np.float32(bd) > np.float32(np.float32(nnratio) * np.float32(bd2))
+    if lvl == lvl2 and fails:
+        return PJ_RATIO_REJECTED
+    return PJ_ACCEPTED_BY_LEVEL if bi2 >= 0 and fails else PJ_ACCEPTED
+
+
+def _pj_store(tr, sides, s, i, bi, obs):
+    side = sides[s]
+    if side.match[bi] >= 0:
+        tr["codes"][s][i].add(PJ_OVERWROTE)
+    side.match[bi] = i
+    side.blk[bi] = bool(obs)
+
+
+def _pj_rotation(tr, sides, nm, check_ori, mut):
+    """The rotation filter (ORBmatcher.cc:2155-2175 / :2284-2296): every entry of a dropped bin NULLs its keypoint
+    and decrements nmatches."""
+    if not check_ori:
+        return nm
+    for s, bi, b, i in tr["entries"]:
+        tr["hist"][b] += 1
+    keep, taken = py_three_maxima(tr["hist"], mut)
+    tr["keep"], tr["three_maxima"] = keep, taken
+    dropped = [(s, bi, i) for s, bi, b, i in tr["entries"] if b not in keep]
+    for s, bi, i in dropped:
+        sides[s].nulled[bi] = True
+        tr["codes"][s][i].add(PJ_ROT_DROPPED)
+    return nm - (len({(s, bi) for s, bi, _ in dropped}) if "dec_per_keypoint" in mut else len(dropped))
+
+
+def _pj_levels(forward, backward, L):
+    if forward:
+        return L, -1
+    if backward:
+        return 0, L
+    return L - 1, L + 1
+
+
+def py_proj_traced(case, th, forward=0, backward=0, check_ori=1, mut=(), nlevels=8):
+    """SearchByProjection(CurrentFrame, LastFrame, th, bMono): one camera (case keys of util.projection_case) or
+    two (util.projection_stereo_case)."""
+    f = np.float32
+    c = case
+    two = "kps_r" in c
+    grid, sf, md = c["grid"], c["scale_factors"], c["mp_desc"]
+    if two:
+        sides = [_PjSide(c["kps"], c["desc"], c["blocked"], grid, md),
+                 _PjSide(c["kps_r"], c["desc_r"], c["blocked_r"], grid, md)]
+        uright = None
+    else:
+        sides = [_PjSide(c["cur_kps"], c["cur_desc"], c["cur_blocked"], grid, md)]
+        uright = c.get("cur_uright")
+    min_x, max_x, min_y, max_y = (f(t) for t in grid[:4])
+    n = len(c["flags"])
+    tr = _pj_trace(sides, n)
+    nm = 0
+    for i in range(n):
+        cs = [tr["codes"][s][i] for s in range(len(sides))]
+        if not c["flags"][i] & 1:
+            for s_ in cs:
+                s_.add(PJ_NOT_SEARCHED)
+            continue
+        obs = bool(c["flags"][i] & 2)
+        xc, yc, zc = (f(t) for t in c["x3dc"][i])
+        invzc = f(1.0 / float(zc))
+        if invzc < 0:
+            cs[0].add(PJ_BEHIND)
+            continue
+        u, v = pj_project(c["camera"], c.get("kb8") if two else None, xc, yc, zc)
+        if u < min_x or u > max_x or v < min_y or v > max_y:
+            cs[0].add(PJ_OUT_OF_BOUNDS)
+            continue
+        L = int(c["last_octave"][i])
+        if L < 0 or L >= nlevels:
+            cs[0].add(PJ_BAD_LEVEL)
+            continue
+        radius = f(f(th) * f(sf[L]))
+        lo, hi = _pj_levels(forward, backward, L)
+        for s, side in enumerate(sides):
+            if s == 1:
+                u, v = pj_project(c["camera"], c.get("kb8"), *c["x3dr"][i])
+            idxs, ret = pj_in_area(side.cells, side.k, grid, u, v, radius, lo, hi, mut)
+            if not idxs:
+                _pj_empty(tr, s, i, ret)
+                if s == 0:  # `continue` at :2035: the right image is not searched either
+                    if two:
+                        cs[1].add(PJ_SIDE_SKIPPED)
+                    break
+                continue
+            reject = None
+            if uright is not None:
+                ur = fmaf(-f(c["camera"][4]), invzc, u)  # fused in the reference object, as the oracle has it
+
+                def reject(i2, ur=ur):
+                    if not uright[i2] > 0:
+                        return False
+                    er = abs(f(ur - f(uright[i2])))
+                    return er >= radius if "ge_uright" in mut else er > radius
+            p1, fin = _pj_pick(side, idxs, side.dist[i], reject, False, mut)
+            v1, vf = _pj_verdict_one(p1, PJ_TH_HIGH, mut), _pj_verdict_one(fin, PJ_TH_HIGH, mut)
+            _pj_record(tr, s, i, p1, fin, v1, vf)
+            if vf == PJ_ACCEPTED:
+                _pj_store(tr, sides, s, i, fin[1], obs)
+                nm += 1
+                if check_ori:
+                    tr["entries"].append((s, fin[1], py_rot_bin(c["last_angle"][i], side.k["angle"][fin[1]], mut), i))
+    nm = _pj_rotation(tr, sides, nm, check_ori, mut)
+    return nm, [s.table() for s in sides], tr
+
+
+def py_reloc_traced(case, th, orb_dist, check_ori=1, mut=(), nlevels=8):
+    """SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (case keys of util.reloc_case)."""
+    f = np.float32
+    c = case
+    grid, sf = c["grid"], c["scale_factors"]
+    sides = [_PjSide(c["cur_kps"], c["cur_desc"], c["cur_blocked"], grid, c["mp_desc"])]
+    side = sides[0]
+    min_x, max_x, min_y, max_y = (f(t) for t in grid[:4])
+    n = len(c["kf_flags"])
+    tr = _pj_trace(sides, n)
+    nm = 0
+    for i in range(n):
+        cs = tr["codes"][0][i]
+        if not c["kf_flags"][i] & 1:
+            cs.add(PJ_NOT_SEARCHED)
+            continue
+        u, v = pj_project(c["camera"], None, *c["x3dc"][i])  # no depth test (:2205-2212)
+        if u < min_x or u > max_x or v < min_y or v > max_y:
+            cs.add(PJ_OUT_OF_BOUNDS)
+            continue
+        d3, dmin, dmax = (f(t) for t in c["dist"][i])
+        if d3 < dmin or d3 > dmax:
+            cs.add(PJ_DEPTH_RANGE)
+            continue
+        L = int(c["level"][i])
+        if L < 0 or L >= nlevels:
+            cs.add(PJ_BAD_LEVEL)
+            continue
+        radius = f(f(th) * f(sf[L]))
+        idxs, ret = pj_in_area(side.cells, side.k, grid, u, v, radius, L - 1, L + 1, mut)
+        if not idxs:
+            _pj_empty(tr, 0, i, ret)
+            continue
+        p1, fin = _pj_pick(side, idxs, side.dist[i], None, False, mut)
+        v1, vf = _pj_verdict_one(p1, orb_dist, mut), _pj_verdict_one(fin, orb_dist, mut)
+        _pj_record(tr, 0, i, p1, fin, v1, vf)
+        if vf == PJ_ACCEPTED:
+            _pj_store(tr, sides, 0, i, fin[1], True)
+            nm += 1
+            if check_ori:
+                tr["entries"].append((0, fin[1], py_rot_bin(c["kf_angle"][i], side.k["angle"][fin[1]], mut), i))
+    nm = _pj_rotation(tr, sides, nm, check_ori, mut)
+    return nm, [side.table()], tr
+
+
+def py_local_traced(case, th, nnratio=0.8, mut=(), nlevels=8):
+    """SearchByProjection(F, vpMapPoints, th, ...): one camera (case keys of util.local_case) or two
+    (util.local_stereo_case)."""
+    f = np.float32
+    c = case
+    two = "kps_r" in c
+    grid, sf, md = c["grid"], c["scale_factors"], c["mp_desc"]
+    if two:
+        sides = [_PjSide(c["kps"], c["desc"], c["blocked"], grid, md),
+                 _PjSide(c["kps_r"], c["desc_r"], c["blocked_r"], grid, md)]
+        proj, lvl, pair, uright = (c["mp_proj"], c["mp_proj_r"]), (c["mp_level"], c["mp_level_r"]), \
+            (c["l2r"], c["r2l"]), None
+    else:
+        sides = [_PjSide(c["cur_kps"], c["cur_desc"], c["cur_blocked"], grid, md)]
+        proj, lvl, pair, uright = (c["mp_proj"],), (c["mp_level"],), (None,), c.get("cur_uright")
+    n = len(c["mp_flags"])
+    tr = _pj_trace(sides, n)
+    nm = 0
+    for m in range(n):
+        fl = int(c["mp_flags"][m])
+        obs = bool(fl & 2)
+        for s, side in enumerate(sides):
+            cs = tr["codes"][s][m]
+            if not fl & (1, 4)[s]:
+                cs.add(PJ_NOT_SEARCHED)
+                continue
+            L = int(lvl[s][m])
+            if L < 0 or L >= nlevels:
+                cs.add(PJ_BAD_LEVEL)
+                continue
+            x, y, xr, vcos = (f(t) for t in proj[s][m])
+            r = f(2.5) if float(vcos) > 0.998 else f(4.0)  # RadiusByViewingCos (:216-222)
+            if s == 0 and float(f(th)) != 1.0:
+                r = f(r * f(th))
+            radius = f(r * f(sf[L]))
+            idxs, ret = pj_in_area(side.cells, side.k, grid, x, y, radius, L - 1, L, mut)
+            if not idxs:
+                _pj_empty(tr, s, m, ret)
+                continue
+            reject = None
+            if uright is not None:
+                def reject(i2, xr=xr, radius=radius):
+                    if not uright[i2] > 0:
+                        return False
+                    er = abs(f(xr - f(uright[i2])))
+                    return er >= radius if "ge_uright" in mut else er > radius
+            p1, fin = _pj_pick(side, idxs, side.dist[m], reject, True, mut)
+            v1, vf = _pj_verdict_two(p1, side, nnratio, mut), _pj_verdict_two(fin, side, nnratio, mut)
+            _pj_record(tr, s, m, p1, fin, v1, vf)
+            if vf == PJ_RATIO_REJECTED:
+                if two and s == 0 and fl & 4:
+                    tr["codes"][1][m].add(PJ_SIDE_SKIPPED)
+                break  # the `continue` at :127 / :197: the next MapPoint
+            if vf in PJ_TAKEN:
+                _pj_store(tr, sides, s, m, fin[1], obs)
+                nm += 1
+                o = int(pair[s][fin[1]]) if pair[s] is not None else -1
+                if o != -1:  # the stereo observation in the other image (:132-136 / :199-203), unchecked
+                    other = sides[1 - s]
+                    cs.add(PJ_MIRRORED)
+                    if other.blk[o] and not obs:
+                        cs.add(PJ_UNBLOCKED_PARTNER)
+                    other.match[o] = m
+                    other.blk[o] = obs
+                    nm += 1
+    return nm, [s.table() for s in sides], tr
+
+
+class ProjScene:
+    """Hand-placed inputs of one of the five searches (kind: "proj", "proj2", "local", "local2", "reloc"), in the
+    dict layout of the util.*_case generators.  Keypoints go where the builder puts them, descriptors are a
+    random base with chosen bits flipped (flip / flip_at), so every Hamming distance is known.  The camera is
+    fx = fy = 1, cx = cy = 0 unless given, and a point at depth z (a power of two) is x3Dc = (u z, v z, z): its
+    projection is (u, v) exactly; mbf = 8, so ur = u - 8 / z."""
+    KINDS = ("proj", "proj2", "local", "local2", "reloc")
+
+    def __init__(self, kind, seed, W=752, H=480, uright=False, kb8=None, camera=None):
+        from oracle_lib import KEYPOINT_DTYPE
+        f = np.float32
+        assert kind in self.KINDS
+        self.kind, self.rng, self.dtype = kind, np.random.default_rng(seed), KEYPOINT_DTYPE
+        self.two = kind in ("proj2", "local2")
+        self.grid = (f(0), f(W), f(0), f(H), f(64) / f(W), f(48) / f(H))
+        self.camera = camera or (f(1), f(1), f(0), f(0), f(8))
+        self.kb8, self.uright = kb8, uright
+        self.sf = orb_scale_factors()
+        self.K, self.D, self.B, self.U, self.pairs = ([], []), ([], []), ([], []), [], []
+        self.P = []
+        self._opener = None
+
+    def desc(self):
+        return self.rng.integers(0, 256, 32, dtype=np.uint8)
+
+    def flip(self, d, k):
+        return flip_bits(d, k, self.rng)
+
+    @staticmethod
+    def flip_at(d, positions):
+        bits = np.unpackbits(np.asarray(d, np.uint8))
+        bits[list(positions)] ^= 1
+        return np.packbits(bits)
+
+    def kp(self, x, y, o=0, d=None, angle=0.0, blocked=0, ur=-1.0, side=0):
+        self.K[side].append((np.float32(x), np.float32(y), int(o), np.float32(angle)))
+        self.D[side].append(self.desc() if d is None else np.asarray(d, np.uint8))
+        self.B[side].append(int(blocked))
+        if side == 0:
+            self.U.append(np.float32(ur))
+        return len(self.K[side]) - 1
+
+    def link(self, il, ir):
+        """mvLeftToRightMatch[il] = ir and mvRightToLeftMatch[ir] = il."""
+        self.pairs.append((il, ir))
+
+    def opener(self):
+        """A spot of the left image with one far-off keypoint per octave: a two-camera frame-to-frame point
+        projected there has a non-empty left window (and no left match), so its right image is searched."""
+        if self._opener is None:
+            self._opener = (np.float32(700.0), np.float32(24.0))
+            for o in range(8):
+                self.kp(*self._opener, o=o)
+        return self._opener
+
+    def pt(self, u, v, L=0, d=None, angle=0.0, on=1, obs=1, z=1.0, right=None, xr=0.0, vcos=1.0,
+           dist=(5.0, 2.5, 10.0), x3=None, x3r=None):
+        """A LastFrame point / MapPoint / KF MapPoint projected at (u, v) (level L) and, in a two-camera kind, at
+        right = (ur, vr[, Lr]) of the right image (local2: None = not in view there; proj2: None = (u, v))."""
+        f = np.float32
+        self.P.append({"u": f(u), "v": f(v), "L": int(L), "d": self.desc() if d is None else np.asarray(d, np.uint8),
+                       "angle": f(angle), "on": int(on), "obs": int(obs), "z": f(z), "right": right, "xr": f(xr),
+                       "vcos": f(vcos), "dist": dist, "x3": x3, "x3r": x3r})
+        return len(self.P) - 1
+
+    def _kps(self, side):
+        k = np.zeros(len(self.K[side]), self.dtype)
+        for i, (x, y, o, a) in enumerate(self.K[side]):
+            k["x"][i], k["y"][i], k["octave"][i], k["angle"][i] = x, y, o, a
+        k["size"], k["class_id"] = 31, -1
+        return k
+
+    def case(self):
+        f = np.float32
+        P, n = self.P, len(self.P)
+
+        def col(key, dtype, tail=()):
+            return np.array([p[key] for p in P], dtype).reshape((n,) + tail)
+
+        def x3(p, uv):
+            return (f(uv[0] * p["z"]), f(uv[1] * p["z"]), p["z"])
+        desc = [np.array(d, np.uint8).reshape(-1, 32) for d in self.D]
+        blk = [np.array(b, np.uint8) for b in self.B]
+        c = {"kind": self.kind, "grid": self.grid, "scale_factors": self.sf, "mp_desc": col("d", np.uint8, (32,))}
+        if self.two:
+            c.update(kps=self._kps(0), desc=desc[0], blocked=blk[0], kps_r=self._kps(1), desc_r=desc[1],
+                     blocked_r=blk[1])
+        else:
+            c.update(cur_kps=self._kps(0), cur_desc=desc[0], cur_blocked=blk[0])
+            if self.kind != "reloc":
+                c["cur_uright"] = np.array(self.U, np.float32) if self.uright else None
+        flags = np.array([p["on"] | p["obs"] << 1 for p in P], np.uint8)
+        if self.kind in ("proj", "proj2", "reloc"):
+            c["camera"] = self.camera
+            c["x3dc"] = np.array([p["x3"] if p["x3"] is not None else x3(p, (p["u"], p["v"])) for p in P],
+                                 np.float32).reshape(n, 3)
+        if self.kind in ("proj", "proj2"):
+            c.update(flags=flags, last_octave=col("L", np.int32), last_angle=col("angle", np.float32))
+        if self.kind == "proj2":
+            c["x3dr"] = np.array([p["x3r"] if p["x3r"] is not None else
+                                  x3(p, p["right"][:2] if p["right"] is not None else (p["u"], p["v"])) for p in P],
+                                 np.float32).reshape(n, 3)
+            c["kb8"] = None if self.kb8 is None else np.array(self.kb8, np.float32)
+        if self.kind == "reloc":
+            c.update(kf_flags=(flags & 1), level=col("L", np.int32), kf_angle=col("angle", np.float32),
+                     dist=np.array([p["dist"] for p in P], np.float32).reshape(n, 3))
+        if self.kind in ("local", "local2"):
+            c.update(mp_flags=flags, mp_level=col("L", np.int32),
+                     mp_proj=np.array([(p["u"], p["v"], p["xr"], p["vcos"]) for p in P], np.float32).reshape(n, 4))
+        if self.kind == "local2":
+            r = [p["right"] for p in P]
+            c["mp_flags"] = flags | np.array([4 if t is not None else 0 for t in r], np.uint8)
+            c["mp_proj_r"] = np.array([(t[0], t[1], 0.0, p["vcos"]) if t is not None else (0.0, 0.0, 0.0, 1.0)
+                                       for t, p in zip(r, P)], np.float32).reshape(n, 4)
+            c["mp_level_r"] = np.array([(t[2] if len(t) > 2 else p["L"]) if t is not None else -1
+                                        for t, p in zip(r, P)], np.int32)
+            c["l2r"] = np.full(len(self.K[0]), -1, np.int32)
+            c["r2l"] = np.full(len(self.K[1]), -1, np.int32)
+            for il, ir in self.pairs:
+                c["l2r"][il], c["r2l"][ir] = ir, il
+        return c
+
+
+def pj_restate(case, call, mut=()):
+    """The traced restatement of the case's kind; call = {th, forward, backward, ori, nnratio, orb_dist}."""
+    if case["kind"] in ("proj", "proj2"):
+        return py_proj_traced(case, call["th"], call["forward"], call["backward"], call["ori"], mut)
+    if case["kind"] == "reloc":
+        return py_reloc_traced(case, call["th"], call["orb_dist"], call["ori"], mut)
+    return py_local_traced(case, call["th"], call["nnratio"], mut)
+
+
+def pj_oracle(case, call):
+    """The C++ oracle's answer in the same form: (nmatches, [tables])."""
+    import oracle_lib
+    kind = case["kind"]
+    if kind == "proj":
+        r = oracle_lib.search_by_projection(case, call["th"], call["forward"], call["backward"], call["ori"])
+    elif kind == "proj2":
+        r = oracle_lib.search_by_projection_stereo(case, call["th"], call["forward"], call["backward"], call["ori"])
+    elif kind == "reloc":
+        r = oracle_lib.search_reloc(case, call["th"], call["orb_dist"], call["ori"])
+    elif kind == "local":
+        r = oracle_lib.search_local(case, call["th"], call["nnratio"])
+    else:
+        r = oracle_lib.search_local_stereo(case, call["th"], call["nnratio"])
+    return r[0], list(r[1:])
