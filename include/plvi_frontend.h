@@ -2683,6 +2683,159 @@ int plvi_feature_refresh(const plvi_refresh_keyframes* kf, const plvi_local_map_
                          const plvi_refresh_params* params, const int* ids, int n_ids,
                          const plvi_refresh_outputs* out);
 
+/* --------------------------------------------------------- GBA propagation
+ * The second half of LoopClosing::RunGlobalBundleAdjustment[WithLines]
+ * (src/LoopClosing.cc:3727-3930 and the line twin from :3996), once the
+ * solver has returned: the breadth-first walk of the spanning tree from the
+ * map's origin keyframes (plvi_gba_walk) and the pass over every MapPoint and
+ * MapLine of the map (plvi_gba_correct).  The walk is integers only.  Every
+ * 4x4 pose product, the velocity and the bias, SetPose, the solver and
+ * InformNewBigChange stay with the caller (INTEGRATION.md has the sequence).
+ * One-camera keyframes.
+ *
+ * plvi_gba_walk (:3727-3843).  plvi_cull_keyframes is read for kf_cap and
+ * bad; plvi_eg_keyframes for order / n_order and child_off / child (NULL,
+ * both = no children).  The child rows carry membership only; the call sorts
+ * them.  origins [n_origins] are slots (mvpKeyFrameOrigins in vector order),
+ * loop_kf is nLoopKF, kf_ba_for [kf_cap] is mnBAGlobalForKF, in/out.
+ *   1. The queue starts as origins in the order given.  An origin outside
+ *      [0, kf_cap) is left out and raises PLVI_GBA_ERR_ORIGIN.  An origin is
+ *      not tested for bad or for its stamp, and is not stamped (:3731).
+ *   2. The front entry's child row is taken in address order: ascending rank,
+ *      the rank of a slot being its first position in `order`, n_order + slot
+ *      for a slot that order does not name.  A child outside [0, kf_cap) or
+ *      bad is skipped with everything below it (:3741).  A child whose stamp
+ *      is not loop_kf is stamped and flagged new (:3744-3768): the caller owes
+ *      it Tchildc * parent.mTcwGBA, the velocity and the bias.  Every child
+ *      not skipped is appended, new or not (:3769).
+ *   3. Every queue entry is a keyframe whose mTcwBefGBA / SetPose the caller
+ *      replays (:3773-3775).
+ * walk [walk_cap] is the queue in order, walk_parent the slot whose row
+ * queued each entry (-1 for an origin), walk_new 0 / 1.  A parent stands
+ * before its children, so one pass over the list computes the new poses.
+ * n_walk, n_new and err are written by every call; n_walk is a full length
+ * under the count contract: nothing is written at or past walk_cap, and
+ * n_walk > walk_cap raises PLVI_GBA_ERR_WALK.  The stamps are state, as in
+ * plvi_loop_correct: every visited child is stamped whatever walk_cap is.
+ * visited [kf_cap] (optional) gets a 1 for every queue entry and is not
+ * cleared: the !mTcwBefGBA.empty() the correction needs after a first GBA.
+ *
+ * Precondition: the child CSR is a forest -- no slot in two rows, no origin
+ * in a row, no origin twice.  The queue is kf_cap entries of scratch.  Tables
+ * that are no forest are still walked as the reference's loop walks them (a
+ * child met twice is new at its first queue position only) for as long as
+ * the queue holds; when the tail would pass kf_cap the walk stops and
+ * PLVI_GBA_ERR_CYCLE is raised -- the reference would not terminate or would
+ * visit more than kf_cap entries -- and the outputs are unspecified but
+ * inside their arrays.  A child row that does not lie inside the first kf_cap
+ * entries of child (a forest has fewer) is read as empty and raises the same
+ * bit.  Limits as for the essential graph: kf_cap <= 2^24, n_order <= 2^30,
+ * PLVI_E_CAPACITY beyond.
+ *
+ * plvi_gba_correct (:3847-3884 points, :3887-3930 lines; params->kind).  The
+ * pool is read for n, bad and pos (points) or sep (lines); feat for ref_kf
+ * and map_id; feat_ba_for [n] is the feature's mnBAGlobalForKF; pos_gba is
+ * mPosGBA, [n][3] float for points, [n][6] double for lines.  Per pool id:
+ *   state 0  a bad feature, or one whose map_id is not params->map
+ *            (GetAllMapPoints of the active map): the row is left alone.
+ *   state 1  feat_ba_for[id] == loop_kf: the row becomes pos_gba[id], a bit
+ *            copy (:3856-3860).
+ *   else r = ref_kf[id].  r outside [0, kf_cap): state 0 and
+ *            PLVI_GBA_ERR_REF (the reference would dereference NULL).
+ *            kf_ba_for[r] != loop_kf or !has_bef[r]: state 0 (:3866-3870).
+ *            bad[r] is not tested: the reference has no isBad() there.
+ *   state 2  Xc = Rcw_bef * X + tcw_bef, X' = Rwc * Xc + twc (:3873-3882).
+ *            Lines: each endpoint narrowed to float (Converter::toCvMat),
+ *            the same two products, the result widened to double
+ *            (Converter::toVector3d).
+ * Each of the six rows is cv::Mat R * X + t in the form the frustum tests
+ * take for Rcw * P + tcw: float products and sums in cv::gemm's small-matrix
+ * order, contracted with PLVI_COMPAT_GEMM_FMA (params->compat), then
+ * (float)((double)s + (double)t).  What pins it:
+ * tests/test_ref_objects_gba_propagate.py.  The output column may be the
+ * array the pool names as const.  state [n] is written for every id, counts
+ * [3] by state and err by every call. */
+enum { /* plvi_gba_params.kind */
+  PLVI_GBA_POINTS = 0,
+  PLVI_GBA_LINES = 1,
+};
+enum { /* err, bits */
+  PLVI_GBA_ERR_ORIGIN = 1, /* an origin outside [0, kf_cap): left out */
+  PLVI_GBA_ERR_CYCLE = 2,  /* the child CSR is not a forest: the walk stopped at kf_cap queue entries */
+  PLVI_GBA_ERR_WALK = 4,   /* n_walk > walk_cap */
+  PLVI_GBA_ERR_REF = 8,    /* a ref_kf outside [0, kf_cap) */
+};
+
+typedef struct plvi_gba_walk_outputs {
+  int walk_cap;
+  int* walk;         /* [walk_cap] slots in queue order */
+  int* walk_parent;  /* [walk_cap] the slot whose row queued the entry; -1 for an origin */
+  uint8_t* walk_new; /* [walk_cap] 1 = stamped by this call */
+  int* n_walk;       /* [1] */
+  int* n_new;        /* [1] */
+  int* err;          /* [1] PLVI_GBA_ERR_* */
+  uint8_t* visited;  /* [kf_cap] optional; 1 for every queue entry, otherwise untouched */
+} plvi_gba_walk_outputs;
+
+/* The keyframe side of the correction, by slot.  A pose is 12 floats: the
+ * nine entries of R row-major, then t. */
+typedef struct plvi_gba_poses {
+  int kf_cap;
+  const unsigned* kf_ba_for; /* [kf_cap] mnBAGlobalForKF after the walk */
+  const uint8_t* has_bef;    /* [kf_cap] !mTcwBefGBA.empty() */
+  const float* tcw_bef;      /* [kf_cap][12] mTcwBefGBA */
+  const float* twc;          /* [kf_cap][12] GetPoseInverse() after SetPose */
+} plvi_gba_poses;
+
+/* Host struct, read before the call returns. */
+typedef struct plvi_gba_params {
+  int kind;         /* PLVI_GBA_POINTS / LINES */
+  unsigned loop_kf; /* nLoopKF */
+  int map;          /* the active map's id, compared with feat->map_id (NULL = one map) */
+  int compat;       /* PLVI_COMPAT_GEMM_FMA */
+} plvi_gba_params;
+
+typedef struct plvi_gba_correct_outputs {
+  float* pos;     /* [n][3] points: may be the pool's own column */
+  double* sep;    /* [n][6] lines: likewise */
+  uint8_t* state; /* [n] 0 left alone, 1 the solver's position, 2 carried by the reference keyframe */
+  int* counts;    /* [3] by state */
+  int* err;       /* [1] PLVI_GBA_ERR_REF */
+} plvi_gba_correct_outputs;
+
+/* Bytes of the walk's scratch block: the rank table, the first queue
+ * position, the usable count and the sorted rows by slot, and the queue.  0
+ * for a negative argument. */
+size_t plvi_gba_walk_scratch_bytes(int kf_cap);
+
+/* The device forms.  The structs are host memory, read before the call
+ * returns; their pointers are device pointers.  PLVI_E_BADARG for a negative
+ * size, kf_cap < 1, a missing required pointer (a list with capacity 0 may be
+ * NULL), a CSR given in part, an unknown kind or a scratch block below its
+ * size.  d_scratch needs no initialisation; calls that share it must be
+ * ordered.  Asynchronous on `stream`, no host read of device data, no
+ * allocation, the counters reset by memset nodes: capturable.  A wave per
+ * slot sorts the rows, then one 1024-thread workgroup walks the queue up to
+ * 1024 entries a step (one wave alone while the frontier fits it); the
+ * correction runs a thread per pool id. */
+int plvi_gba_walk_device(const plvi_cull_keyframes* kf, const plvi_eg_keyframes* eg, const int* d_origins,
+                         int n_origins, unsigned loop_kf, unsigned* d_kf_ba_for, const plvi_gba_walk_outputs* out,
+                         void* d_scratch, size_t scratch_bytes, void* stream);
+int plvi_gba_correct_device(const plvi_local_map_pool* pool, const plvi_eg_features* feat,
+                            const unsigned* d_feat_ba_for, const void* d_pos_gba, const plvi_gba_poses* poses,
+                            const plvi_gba_params* params, const plvi_gba_correct_outputs* out, void* stream);
+
+/* The host forms, synchronous: the same structs and arrays with host
+ * pointers; kf_ba_for, visited and the output column are updated in place.
+ * plvi_gba_walk returns n_walk, plvi_gba_correct the number of rows written
+ * (states 1 and 2); PLVI_E_CAPACITY when err != 0 (everything is still
+ * written), or another error. */
+int plvi_gba_walk(const plvi_cull_keyframes* kf, const plvi_eg_keyframes* eg, const int* origins, int n_origins,
+                  unsigned loop_kf, unsigned* kf_ba_for, const plvi_gba_walk_outputs* out);
+int plvi_gba_correct(const plvi_local_map_pool* pool, const plvi_eg_features* feat, const unsigned* feat_ba_for,
+                     const void* pos_gba, const plvi_gba_poses* poses, const plvi_gba_params* params,
+                     const plvi_gba_correct_outputs* out);
+
 /* ---------------------------------------------------------------- Stereo
  * Rectified stereo of the stereo Frame constructors (src/Frame.cc:95-140,
  * :225-300). */

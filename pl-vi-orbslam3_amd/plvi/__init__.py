@@ -2977,3 +2977,279 @@ class FeatureRefresh:
         r = self._result(res, len(ids), rc)
         r.update({k: self.feat[k] for k in _REFRESH_COLUMNS if k in self.feat})
         return r
+
+
+GBA_POINTS, GBA_LINES = 0, 1
+GBA_ERR_ORIGIN, GBA_ERR_CYCLE, GBA_ERR_WALK, GBA_ERR_REF = 1, 2, 4, 8
+
+_GBA_KF = {"bad": np.uint8, "order": np.int32, "child_off": np.int32, "child": np.int32, "kf_ba_for": np.uint32}
+_GBA_FEAT = {"bad": (np.uint8, None), "ref_kf": (np.int32, None), "map_id": (np.int32, None),
+             "ba_for": (np.uint32, None)}
+_GBA_POSES = {"kf_ba_for": (np.uint32, None), "has_bef": (np.uint8, None), "tcw_bef": (np.float32, 12),
+              "twc": (np.float32, 12)}
+_GBA_WALK_LISTS = {"walk": np.int32, "walk_parent": np.int32, "walk_new": np.uint8}
+_GBA_WALK_N = ("n_walk", "n_new", "err")
+
+
+class GbaWalkOutputs(ctypes.Structure):
+    """plvi_gba_walk_outputs."""
+    _fields_ = [("walk_cap", _LM_I)] + [(k, _LM_V) for k in ("walk", "walk_parent", "walk_new", "n_walk", "n_new",
+                                                            "err", "visited")]
+
+
+class GbaPoses(ctypes.Structure):
+    """plvi_gba_poses."""
+    _fields_ = [("kf_cap", _LM_I)] + [(k, _LM_V) for k in _GBA_POSES]
+
+
+class GbaParams(ctypes.Structure):
+    """plvi_gba_params."""
+    _fields_ = [("kind", _LM_I), ("loop_kf", ctypes.c_uint), ("map", _LM_I), ("compat", _LM_I)]
+
+
+class GbaCorrectOutputs(ctypes.Structure):
+    """plvi_gba_correct_outputs."""
+    _fields_ = [(k, _LM_V) for k in ("pos", "sep", "state", "counts", "err")]
+
+
+class _GbaWalk:
+    """plvi_gba_walk[_device] on the tables of a GBAPropagation."""
+
+    def __init__(self, owner):
+        self.o = owner
+
+    def _outputs(self, walk_cap, visited, fill):
+        o = self.o
+        walk_cap = o.kf_cap if walk_cap is None else int(walk_cap)
+        if walk_cap < 0:
+            raise ValueError(f"walk_cap {walk_cap} is negative")
+        res = {k: np.full(walk_cap + 1, fill & 0x7f if dt is np.uint8 else fill, dt)  # one cell past the capacity
+               for k, dt in _GBA_WALK_LISTS.items()}
+        res.update({k: np.full(1, fill, np.int32) for k in _GBA_WALK_N})
+        if visited is True:
+            visited = np.zeros(o.kf_cap, np.uint8)
+        if visited is not None and visited is not False:
+            res["visited"] = _table(visited, np.uint8)
+            _same_len(o.kf_cap, visited=res["visited"])
+        return walk_cap, res
+
+    def _structs(self, ptr):
+        o = self.o
+        kf = CullKeyframes(o.kf_cap, 0, 0, 0)
+        kf.bad = ptr("kf", "bad")
+        eg = EgKeyframes(len(o.kf.get("order", ())), 0)
+        for k in ("order", "child_off", "child"):
+            if k in o.kf:
+                setattr(eg, k, ptr("kf", k))
+        return kf, eg
+
+    def batch(self, origins, loop_kf, walk_cap=None, visited=True, scratch=None, fill=-7, stream=None, run=True):
+        """plvi_gba_walk_device on the device copies (``owner.dev``; the stamps stay there for ``correct.batch``).
+        ``visited``: True = a zeroed table, an array = its start, None = no table.  ``scratch``: (device address,
+        bytes) of a block of the caller's.  Returns walk, walk_parent, walk_new (walk_cap + 1 long), n_walk, n_new,
+        err, visited, kf_ba_for as it stands on the device, "rc" and "dev"; run=False returns (step(stream),
+        fetch()) for capture."""
+        o = self.o
+        o._check_keyframes()
+        origins = _table(origins, np.int32).reshape(-1)
+        walk_cap, res = self._outputs(walk_cap, visited, fill)
+        sb = load().plvi_gba_walk_scratch_bytes(o.kf_cap)
+        if scratch is not None and scratch[1] < sb:
+            raise ValueError(f"the scratch block has {scratch[1]} bytes, the walk needs {sb}")
+        dev = o.upload()
+        structs = self._structs(lambda g, k: dev[(g, k)].ptr)
+        obuf = dict(zip(res, _to_device(*res.values())[0]))
+        ibuf = _to_device(origins)[0]
+        own = None if scratch is not None else DeviceBuffer(sb)
+        sptr, sbytes = scratch if scratch is not None else (own.ptr, sb)
+        out = GbaWalkOutputs(walk_cap, **{k: b.ptr for k, b in obuf.items()})
+
+        def step(s=None):
+            return _status("plvi_gba_walk_device", *structs, ibuf[0].ptr, len(origins), int(loop_kf),
+                           dev[("kf", "kf_ba_for")].ptr, out, sptr, sbytes, s or None)
+
+        def fetch(rc=0):
+            _sync()
+            r = {k: obuf[k].download(a) for k, a in res.items()}
+            r["kf_ba_for"] = dev[("kf", "kf_ba_for")].download(np.empty_like(o.kf["kf_ba_for"]))
+            r.update(rc=rc, keep=(obuf, ibuf, own), dev={k: b.ptr for k, b in obuf.items()})
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
+
+    def host(self, origins, loop_kf, walk_cap=None, visited=True, fill=-7):
+        """plvi_gba_walk: the same dict; ``owner.kf["kf_ba_for"]`` is stamped in place.  "rc" is n_walk, or
+        PLVI_E_CAPACITY when err is not 0; any other refusal raises."""
+        o = self.o
+        o._check_keyframes()
+        origins = _table(origins, np.int32).reshape(-1)
+        walk_cap, res = self._outputs(walk_cap, visited, fill)
+        structs = self._structs(lambda g, k: o.kf[k].ctypes.data)
+        out = GbaWalkOutputs(walk_cap, **{k: a.ctypes.data for k, a in res.items()})
+        rc = _status("plvi_gba_walk", *structs, origins, len(origins), int(loop_kf), o.kf["kf_ba_for"], out)
+        if rc < 0 and rc != PLVI_E_CAPACITY:
+            raise PlviError(rc, "plvi_gba_walk")
+        r = dict(res)
+        r.update(kf_ba_for=o.kf["kf_ba_for"].copy(), rc=rc)
+        return r
+
+
+class _GbaCorrect:
+    """plvi_gba_correct[_device] on the pools of a GBAPropagation."""
+
+    def __init__(self, owner):
+        self.o = owner
+
+    def _prepare(self, kind, poses):
+        o = self.o
+        if kind not in (GBA_POINTS, GBA_LINES):
+            raise ValueError(f"unknown kind {kind}")
+        feat = o.pools[kind]
+        if feat is None:
+            raise ValueError("no pool of that kind was given")
+        o._check_pool(kind)
+        poses = {k: _table(poses[k], dt, w) for k, (dt, w) in _GBA_POSES.items() if poses.get(k) is not None}
+        if "kf_ba_for" not in poses and "kf_ba_for" in o.kf:
+            poses["kf_ba_for"] = o.kf["kf_ba_for"]
+        missing = [k for k in _GBA_POSES if k not in poses]
+        if missing:
+            raise ValueError(f"poses lacks {missing}")
+        _same_len(o.kf_cap, **{"poses." + k: a for k, a in poses.items()})
+        return feat, poses, "sep" if kind == GBA_LINES else "pos"
+
+    @staticmethod
+    def _outputs(n, fill):
+        return {"state": np.full(n + 1, fill & 0x7f, np.uint8), "counts": np.full(3, fill, np.int32),
+                "err": np.full(1, fill, np.int32)}
+
+    def batch(self, kind, loop_kf, poses, map=0, compat=0, column=None, stamps_on_device=False, fill=-7, stream=None,
+              run=True):
+        """plvi_gba_correct_device.  ``poses``: a dict has_bef [K], tcw_bef [K][12], twc [K][12] and optionally
+        kf_ba_for (default: the keyframe table's; with stamps_on_device the device copy ``walk.batch`` stamped).
+        ``column`` None writes the pool's own device column in place, an array is a separate output that starts as
+        given.  Returns state (n + 1 long), counts, err, the column under "pos" / "sep", "rc" and "dev" (the
+        device addresses of the outputs and of the column)."""
+        o = self.o
+        feat, poses, col = self._prepare(kind, poses)
+        n = len(feat["bad"])
+        res = self._outputs(n, fill)
+        dev = o.upload()
+        g = "ml" if kind == GBA_LINES else "mp"
+        pbuf = dict(zip(poses, _to_device(*poses.values())[0]))
+        if stamps_on_device:
+            pbuf["kf_ba_for"] = dev[("kf", "kf_ba_for")]
+        obuf = dict(zip(res, _to_device(*res.values())[0]))
+        if column is None:
+            cbuf, host_col = dev[(g, col)], np.empty_like(feat[col])
+        else:
+            host_col = _table(column, *_LM_ROWS[col]).copy()
+            _same_len(n, column=host_col)
+            cbuf = _to_device(host_col)[0][0]
+        pool = LocalMapPool(n, **{k: dev[(g, k)].ptr for k in ("bad", col)})
+        ef = EgFeatures(**{k: dev[(g, k)].ptr for k in ("ref_kf", "map_id") if k in feat})
+        dposes = GbaPoses(o.kf_cap, **{k: b.ptr for k, b in pbuf.items()})
+        params = GbaParams(int(kind), int(loop_kf), int(map), int(compat))
+        out = GbaCorrectOutputs(**{col: cbuf.ptr}, **{k: b.ptr for k, b in obuf.items()})
+
+        def step(s=None):
+            return _status("plvi_gba_correct_device", pool, ef, dev[(g, "ba_for")].ptr, dev[(g, "pos_gba")].ptr,
+                           dposes, params, out, s or None)
+
+        def fetch(rc=0):
+            _sync()
+            r = {k: obuf[k].download(a) for k, a in res.items()}
+            r[col] = cbuf.download(host_col)
+            r.update(rc=rc, keep=(pbuf, obuf, cbuf), dev=dict({k: b.ptr for k, b in obuf.items()}, **{col: cbuf.ptr}))
+            return r
+        if not run:
+            return step, fetch
+        return fetch(step(stream))
+
+    def host(self, kind, loop_kf, poses, map=0, compat=0, column=None, fill=-7):
+        """plvi_gba_correct: the same dict; with ``column`` None the pool's host column is updated in place.  "rc"
+        is the number of rows written, or PLVI_E_CAPACITY when err is not 0; any other refusal raises."""
+        o = self.o
+        feat, poses, col = self._prepare(kind, poses)
+        n = len(feat["bad"])
+        res = self._outputs(n, fill)
+        if column is None:
+            host_col = feat[col]
+        else:
+            host_col = _table(column, *_LM_ROWS[col]).copy()
+            _same_len(n, column=host_col)
+        pool = LocalMapPool(n, **{k: feat[k].ctypes.data for k in ("bad", col)})
+        ef = EgFeatures(**{k: feat[k].ctypes.data for k in ("ref_kf", "map_id") if k in feat})
+        dposes = GbaPoses(o.kf_cap, **{k: a.ctypes.data for k, a in poses.items()})
+        params = GbaParams(int(kind), int(loop_kf), int(map), int(compat))
+        out = GbaCorrectOutputs(**{col: host_col.ctypes.data}, **{k: a.ctypes.data for k, a in res.items()})
+        rc = _status("plvi_gba_correct", pool, ef, feat["ba_for"], feat["pos_gba"], dposes, params, out)
+        if rc < 0 and rc != PLVI_E_CAPACITY:
+            raise PlviError(rc, "plvi_gba_correct")
+        r = dict(res)
+        r[col] = host_col
+        r["rc"] = rc
+        return r
+
+
+class GBAPropagation:
+    """The second half of LoopClosing::RunGlobalBundleAdjustment[WithLines] over resident tables: ``walk`` is the
+    breadth-first walk of the spanning tree from the map's origins (plvi_gba_walk[_device]), ``correct`` the pass
+    over every MapPoint / MapLine (plvi_gba_correct[_device]).  Each has ``.batch`` (device copies, ``self.dev``)
+    and ``.host`` (the host forms, updating the host arrays in place).
+
+    ``keyframes``: a dict of numpy arrays bad [K], kf_ba_for [K] (mnBAGlobalForKF) and optionally order,
+    child_off [K + 1] / child.  ``points`` / ``lines``: dicts with bad, ref_kf, ba_for (the feature's
+    mnBAGlobalForKF), pos_gba ([n][3] float32 / [n][6] float64), the column pos [n][3] / sep [n][6] and optionally
+    map_id."""
+
+    def __init__(self, keyframes, points=None, lines=None):
+        self._lib = load()
+        self.kf = {k: _table(keyframes[k], dt) for k, dt in _GBA_KF.items() if keyframes.get(k) is not None}
+        self.kf_cap = len(self.kf["bad"])
+
+        def pool(p, col):
+            if p is None:
+                return None
+            f = {k: _table(p[k], dt, w) for k, (dt, w) in _GBA_FEAT.items() if p.get(k) is not None}
+            f[col] = _table(p[col], *_LM_ROWS[col])
+            f["pos_gba"] = _table(p["pos_gba"], *_LM_ROWS[col])
+            return f
+        self.pools = [pool(points, "pos"), pool(lines, "sep")]
+        self.dev = None
+        self.walk = _GbaWalk(self)
+        self.correct = _GbaCorrect(self)
+
+    def _check_keyframes(self):
+        """Every companion array has the length its table gives it: refused here, before the library reads them."""
+        K = self.kf_cap
+        if K < 1:
+            raise ValueError("the keyframe table is empty")
+        if "kf_ba_for" not in self.kf:
+            raise ValueError("keyframes.kf_ba_for is required")
+        _same_len(K, **{"keyframes.kf_ba_for": self.kf["kf_ba_for"]})
+        if ("child_off" in self.kf) != ("child" in self.kf):
+            raise ValueError("keyframes.child_off and keyframes.child go together")
+        if "child_off" in self.kf:
+            _same_len(K + 1, **{"keyframes.child_off": self.kf["child_off"]})
+            _same_len(max(int(self.kf["child_off"][K]), 0), **{"keyframes.child": self.kf["child"]})
+
+    def _check_pool(self, kind):
+        f = self.pools[kind]
+        missing = [k for k in ("bad", "ref_kf", "ba_for") if k not in f]
+        if missing:
+            raise ValueError(f"the pool lacks {missing}")
+        _same_len(len(f["bad"]), **{("lines." if kind else "points.") + k: a for k, a in f.items()})
+
+    def _tables(self):
+        t = {("kf", k): a for k, a in self.kf.items()}
+        for g, p in zip(("mp", "ml"), self.pools):
+            if p is not None:
+                t.update({(g, k): a for k, a in p.items()})
+        return t
+
+    def upload(self):
+        if self.dev is None:
+            tabs = self._tables()
+            self.dev = dict(zip(tabs, _to_device(*tabs.values())[0]))
+        return self.dev

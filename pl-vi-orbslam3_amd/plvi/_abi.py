@@ -42,14 +42,15 @@ class PlviError(RuntimeError):
 
 
 # ------------------------------------------------------------ signatures
-_SCALARS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
+_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double}
 _DECL = re.compile(r"^[ \t]*([A-Za-z_][\w \t\*]*?)\s*\b(plvi_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", re.M)
 _NAME = re.compile(r"\b(plvi_[a-z0-9_]+)\s*\(")
 
 
 def _ctype(decl, name, named, where):
     """The ctypes type of one C parameter (named) or return type: a pointer is c_void_p (const char* is
-    c_char_p), int / size_t / float / double are their scalars, anything else is refused."""
+    c_char_p), int / unsigned / size_t / float / double are their scalars, anything else is refused."""
     words = decl.replace("*", " * ").split()
     if "*" in words:
         return ctypes.c_char_p if words[:3] == ["const", "char", "*"] and words.count("*") == 1 else ctypes.c_void_p
